@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- ACS generations/sec on the BASELINE workload (config C3 per GPU; C4 across GPUs).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -60,6 +60,9 @@ def parse():
                     help="warm-up + timed region only: no continuation of the search behind the timed region (roofline samples), no walk_step, no secondary measurements "
                          "-- what a rocprofv3 kernel trace of the command should contain (tools/timed_window_stats.py)")
     ap.add_argument("--no-roofline-256", action="store_true", help="skip the 256^3 (past the Infinity Cache) sweep measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its search returns to a caller (best cost and path, per-generation trace, pheromone "
+                         "field) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--workload-index", type=int, default=None,
                     help="run rank R's C4 workload (grid seed 2024+R, colony seed 12345+R) on this GPU; default = own rank")
     return ap.parse_args()
@@ -561,6 +564,34 @@ def pair_planning_extra(ctx, grid, free, n):
             "identical_costs_and_paths": same}
 
 
+DUMP_FIELD_MAX = 12 << 20    # pheromone entries written in full (48 MiB: the whole 128^3 x 6 field) ...
+DUMP_FIELD_SAMPLE = 4 << 20  # ... a larger field: this many seeded draws of an entry index (16 MiB of values + 32 MiB of indices at most)
+
+
+def dump_outputs(d, solver, cost, path, trace, glob=None):
+    """What the timed search returns to a caller after its last generation, as DIR/<name>.npy: the best cost and path (wa_acs_result), the
+    per-generation trace (wa_acs_trace), the pheromone field (wa_acs_read_pheromone; past DUMP_FIELD_MAX entries a fixed, seeded sample of
+    sorted entry indices, written beside it) and, with several ranks, the MIN-reduced global-best history.  Ids and counts go out as float64
+    (exact), costs and the field as float32."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    ph = solver.pheromone()
+    arrs = {"best_cost": np.array([cost], np.float32), "best_path": path.astype(np.float64),
+            "trace_best_cost": trace["bestL"].astype(np.float32), "trace_iteration_best_cost": trace["iterbestL"].astype(np.float32),
+            "trace_colony": trace["colony"].astype(np.float64), "trace_finite": trace["finite"].astype(np.float64),
+            "trace_steps": trace["steps"].astype(np.float64)}
+    if ph.size > DUMP_FIELD_MAX:
+        idx = np.unique(np.random.default_rng(20240607).integers(0, ph.size, DUMP_FIELD_SAMPLE))
+        arrs["pheromone_sample"], arrs["pheromone_sample_index"] = ph[idx], idx.astype(np.float64)
+    else:
+        arrs["pheromone"] = ph
+    if glob is not None:
+        arrs["global_best_cost"] = np.asarray(glob, np.float32)
+    for k, v in arrs.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(v))
+    return sorted(arrs)
+
+
 def wait_for_device_memory(ctx, want=0.85, timeout_s=30.0):
     """A process that has just exited may still be giving its device memory back; allocations made meanwhile can end up in
     host-visible memory (measured: the whole run 4x slower).  Wait until most of the device memory is free."""
@@ -703,6 +734,7 @@ def main():
             allh = [torch.empty(K, dtype=torch.float32, device=cdev) for _ in range(world)]
             dist.all_gather(allh, torch.from_numpy(np.ascontiguousarray(trace["bestL"], np.float32)).to(cdev))
             assert np.array_equal(torch.stack(allh).min(0).values.cpu().numpy().view(np.uint32), glob.view(np.uint32)), "RCCL MIN != MIN of the gathered histories"
+    dumped = dump_outputs(args.dump_outputs, solver, cost, path, trace, glob if dist_on else None) if args.dump_outputs and rank == 0 else None
     best_all = wd.max_over_ranks(-float(cost), cdev) * -1.0  # min over ranks
     if rank == 0:
         # ---- the roofline kernel = the launch of the TIMED loop that carries the evaporation sweep (k_evap_rank_mark: 4096 sweep
@@ -791,6 +823,8 @@ def main():
             "steps_per_generation_first_last": [int(trace["steps"][0]), int(trace["steps"][-1])],
             "device": ctx.device_name,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if world == 1 and not args.no_extras:
             # the extras stand outside `value`: one that fails is reported under its key and must not cost the line
             def guarded(fn, *a):

@@ -82,3 +82,28 @@ def test_a_failing_extra_does_not_cost_the_line():
     for k in ("walk_step", "full_run", "ref_mode", "multi_start", "multi_start_curve", "c5_pair_planning", "c5_full"):
         assert "WA_BENCH_FAIL" in d[k]["error"], k
     assert "walk_step_extra failed" in r.stderr
+
+
+def test_dump_outputs_are_the_timed_search_and_repeat_exactly(tmp_path):
+    """--dump-outputs: the timed search's result (best cost and path, the trace of exactly --steps generations, the pheromone field) as .npy
+    files of float32 / float64, at most 64 MB in all; a second run with the same arguments writes the same arrays bit for bit"""
+    import numpy as np
+    got = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "2", "--no-cpu", "--no-extras",
+                            "--no-roofline-256", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 12 and line["ms_per_step"] > 0
+        files = sorted(d.glob("*.npy"))
+        assert sorted(f.stem for f in files) == sorted(line["dumped_outputs"]["arrays"])
+        assert sum(f.stat().st_size for f in files) <= 64 * 10 ** 6
+        arrs = {f.stem: np.load(f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert arrs["trace_best_cost"].shape == (12,) and arrs["best_cost"][0] == line["best_cost"] == arrs["trace_best_cost"][-1]
+        assert arrs["best_path"].shape == (line["path_nodes"],) and arrs["pheromone"].shape == (6 * 128 ** 3,)
+        got.append(arrs)
+    assert got[0].keys() == got[1].keys()
+    for k in got[0]:
+        assert np.array_equal(got[0][k].view(np.uint8), got[1][k].view(np.uint8)), k

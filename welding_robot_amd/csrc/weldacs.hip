@@ -143,6 +143,7 @@ struct wa_acs {
     // pipelined groups (wa_acs_run): the active slots split into groups, each with a stream of its own, so that one group's HBM-bound
     // sweep runs under another group's latency-bound walk.  Forked from / joined into the context's stream inside every wa_acs_run call.
     int32_t pipe_groups_env = 0;         // WA_PIPE_GROUPS, read at creation (0: by rule)
+    int32_t hw_queues = 4;               // GPU_MAX_HW_QUEUES as the HIP runtime reads it (default 4), read at creation: the rule's ceiling
     std::vector<hipStream_t> gstream;
     std::vector<hipEvent_t> gjoin;
     int32_t sweep_nt_env = -1;           // WA_SWEEP_NT: cache policy of the sweep (-1: by rule)
