@@ -95,6 +95,9 @@ def main():
     ap.add_argument("--neighbourhood", type=int, default=6, choices=(6, 26), help="26: the variant the reference stubs out (ACSRank_3D.hpp:361-388)")
     ap.add_argument("--lazy", action="store_true",
                     help="wa_acs_create_lazy: never-deposited voxels are not swept (same results, O(deposited voxels) per generation)")
+    ap.add_argument("--clearance", type=float, default=None,
+                    help="metres of clearance: plan on the grid inflated by it (weld points kept free), then check the final trajectory "
+                         "against the original grid (wa_traj_clearance)")
     args = ap.parse_args()
     rank, local_rank, world = wd.env_rank()
     ctx = api.Context(local_rank)
@@ -118,6 +121,10 @@ def main():
             free = grid.occupancy()
     pts = synth.synth_weld_points(free, n, args.points, seed=args.seed)
     predict = float(0.35 ** -1 * 24)  # 24 ants per search at precision 1 (ACSRank_3D.hpp:247)
+    metal = grid
+    if args.clearance is not None:
+        # plan with a safety margin: every voxel nearer the metal than the radius becomes an obstacle, except around the weld points
+        grid = metal.inflate(metal.clearance_radius(args.clearance), pts)
     t0 = time.perf_counter()
     cost, paths, n_mine = plan(ctx, grid, pts, args.generations, predict, args.seed, args.slots, rank, world, lazy=args.lazy, neighbourhood=args.neighbourhood)
     if comm is not None:
@@ -161,6 +168,13 @@ def main():
         out.update(stitched_nodes=len(path), coarse_points=len(coarse), trajectory_samples=int(ok.sum()),
                    trajectory_length=float(np.linalg.norm(np.diff(traj, axis=0), axis=1).sum()),
                    t_trajectory_s=time.perf_counter() - t2)
+        if args.clearance is not None:
+            # the curve the robot follows, against the real obstacles: how close it comes, and whether it cuts through any
+            final = api.Trajectory.from_points(ctx, traj[ok.astype(bool)])
+            summary = final.clearance(metal)[3]
+            summary["min_distance"] = float(np.sqrt(summary["min_d2"]) * metal.precision) if summary["min_d2"] != api.WA_D2_NONE else None
+            out.update(clearance=args.clearance, clearance_radius_voxels=metal.clearance_radius(args.clearance),
+                       free_voxels_inflated=grid.n_free, free_voxels=metal.n_free, trajectory_clearance=summary)
     if rank == 0:
         print(json.dumps(out))
     if comm is not None:

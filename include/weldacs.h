@@ -407,6 +407,44 @@ int wa_bspline_eval_host(wa_bspline *b, float u, int32_t der, float *out /* dim 
 int wa_bspline_sample(wa_bspline *b, float t0, float dt, int64_t count, int32_t der, float *out,
                       uint8_t *ok, wa_traj **out_traj);
 
+/* ---- obstacle clearance (not in the reference: its planner treats the torch as a point) ----
+ * Distances are in voxel-INDEX units.  The axis tables are uniform at `precision` except at the hi-side seam of the wall
+ * (model_grid_map.hpp:204-211, wa_axis_coords), so sqrt(d2) * precision is a distance in metres only up to that seam.
+ *
+ * wa_grid_distance_field: for every voxel v, min over occupied voxels o of (vx-ox)^2 + (vy-oy)^2 + (vz-oz)^2 (integers, exact);
+ * 0 on occupied voxels; WA_D2_NONE everywhere when the grid has no occupied voxel.  Space outside the grid is not an obstacle.
+ * Computed on the first call (or the first wa_grid_inflate / wa_traj_clearance) and kept on the device with the grid (freed by
+ * wa_grid_destroy).  d2_out (n = nx*ny*nz int32 in raster order, like wa_grid_read_occupancy) may be NULL: then it only builds the
+ * field.  WA_ERR_ARG when (nx-1)^2 + (ny-1)^2 + (nz-1)^2 >= 2^31 (a degenerate grid: the field would not fit int32). */
+#define WA_D2_NONE 0x7fffffff
+int wa_grid_distance_field(const wa_grid *g, int32_t *d2_out);
+/* New grid (same dims, axis tables, precision, wall; own buffers; n_free recounted): voxel v is free iff g's v is free AND
+ * (double)d2[v] > (double)radius * radius (WA_D2_NONE: no obstacle, farther than any radius) -- except inside keep bubbles: for each
+ * keep id k (must be a free voxel of g, else WA_ERR_ARG), every voxel v with |v-k|^2 <= (radius+1)^2 (index units, double) keeps
+ * g's state.  radius in voxels (>= 0, finite; 0 reproduces g's occupancy exactly).  g is not modified.  The result is an ordinary
+ * grid for every other entry point.  Keep bubbles exist for weld points on the workpiece's surface (pass the ids resolved on g);
+ * a bubble does not guarantee that a point in a concave corner connects to the free corridor around the part. */
+int wa_grid_inflate(const wa_grid *g, float radius, const int64_t *keep_ids, int32_t n_keep, wa_grid **out);
+typedef struct {
+    int32_t min_d2;           /* over samples (WA_D2_NONE if no obstacle, or no sample) */
+    int64_t argmin;           /* lowest sample index attaining it (-1 without samples) */
+    int64_t first_hit;        /* lowest segment index whose supercover meets an occupied voxel, -1 if none */
+    int64_t n_hit;            /* segments that do */
+    int64_t n_outside;        /* samples outside the grid's coordinate range on some axis */
+} wa_clearance_summary;
+/* Checks a trajectory t (t's n points; t and g from one context) against g.  Voxel of a sample: per axis, p is clamped into
+ * [smallest, largest] value of the axis table (NaN to the smallest; such samples count in n_outside), then the voxel index is the
+ * lowest j minimising |p - c[j]| (fp32 subtraction).  d2 of a sample = the distance field at its voxel.  Segment i = samples i, i+1;
+ * it hits iff some voxel of the 3-D supercover between their voxels a, b is occupied, where with d = b - a, per axis c the set of
+ * t is every t when d_c = 0 and v_c = a_c (none if v_c != a_c), else the closed interval between (2(v_c-a_c)-1)/(2d_c) and
+ * (2(v_c-a_c)+1)/(2d_c); v is in the supercover iff [0,1] and the three sets share a t (the segment between the voxel centres touches
+ * v's closed cube: conservative at edges and corners).  A stitched path of 6-neighbour free voxels has no hit as long as every node
+ * maps back to itself, which fails where an axis table holds one coordinate twice: at the hi seam when (hi - lo) / precision is an
+ * exact integer, lowest-j-on-ties maps the upper node to the one below it.  ids_out / d2_out (n) and hit_out (n-1) may be NULL;
+ * sum may not.  At most 2^33 samples. */
+int wa_traj_clearance(const wa_grid *g, const wa_traj *t, int64_t *ids_out, int32_t *d2_out, uint8_t *hit_out,
+                      wa_clearance_summary *sum);
+
 #ifdef __cplusplus
 }
 #endif

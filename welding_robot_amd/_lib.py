@@ -27,6 +27,14 @@ class GtspParams(C.Structure):
                 ("max_iterations", C.c_int32)]
 
 
+WA_D2_NONE = 0x7fffffff
+
+
+class ClearanceSummary(C.Structure):
+    _fields_ = [("min_d2", C.c_int32), ("argmin", C.c_int64), ("first_hit", C.c_int64), ("n_hit", C.c_int64),
+                ("n_outside", C.c_int64)]
+
+
 # every symbol include/weldacs.h declares: name -> (restype, argtypes)
 _V, _I, _I64, _F, _P = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_void_p
 SYMBOLS = {
@@ -120,6 +128,9 @@ SYMBOLS = {
     "wa_bspline_eval": (C.c_int, [_V, _P, _I64, _I, _P, _P]),
     "wa_bspline_eval_host": (C.c_int, [_V, _F, _I, _P, _P]),
     "wa_bspline_sample": (C.c_int, [_V, _F, _F, _I64, _I, _P, _P, C.POINTER(_V)]),
+    "wa_grid_distance_field": (C.c_int, [_V, _P]),
+    "wa_grid_inflate": (C.c_int, [_V, _F, _P, _I, C.POINTER(_V)]),
+    "wa_traj_clearance": (C.c_int, [_V, _V, _P, _P, _P, C.POINTER(ClearanceSummary)]),
 }
 
 _libs = {}

@@ -7,7 +7,7 @@ import weakref
 import numpy as np
 
 from . import _lib as L
-from ._lib import AcsParams, GtspParams, RNG_DEV, RNG_REF, WeldacsError  # noqa: F401
+from ._lib import AcsParams, GtspParams, RNG_DEV, RNG_REF, WA_D2_NONE, WeldacsError  # noqa: F401
 
 
 def _ptr(a):
@@ -167,6 +167,25 @@ class Grid:
         ids = np.empty(len(pts), np.int64)
         self.ctx.check(self.ctx.lib.wa_grid_resolve_points(self.h, _ptr(pts), len(pts), _ptr(ids)))
         return ids
+
+    def distance_field(self):
+        """exact squared distance to the nearest occupied voxel, in voxel-index units (flat int32, raster order like occupancy();
+        WA_D2_NONE everywhere on a grid without obstacles)"""
+        out = np.empty(self.n, np.int32)
+        self.ctx.check(self.ctx.lib.wa_grid_distance_field(self.h, _ptr(out)))
+        return out
+
+    def inflate(self, radius, keep_ids=None):
+        """a planning grid whose free voxels lie farther than `radius` voxels from every obstacle, except within radius + 1 of each
+        keep id (weld points resolved on this grid), where this grid's state is kept"""
+        keep = np.ascontiguousarray(keep_ids if keep_ids is not None else [], np.int64).reshape(-1)
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.lib.wa_grid_inflate(self.h, C.c_float(radius), _ptr(keep) if len(keep) else None, len(keep), C.byref(h)))
+        return Grid(self.ctx, h, self.bbox)
+
+    def clearance_radius(self, metres):
+        """a clearance in metres as a radius in voxels (exact up to the hi-side seam of the wall, see include/weldacs.h)"""
+        return float(metres) / float(self.precision)
 
     def close(self):
         if getattr(self, "h", None):
@@ -516,6 +535,15 @@ class Trajectory:
         out = np.empty((len(self), 3), np.float32)
         self.ctx.check(self.ctx.lib.wa_traj_read(self.h, _ptr(out)))
         return out
+
+    def clearance(self, grid):
+        """wa_traj_clearance: (voxel ids int64[n], d2 int32[n], hits uint8[n-1], summary dict)"""
+        n = len(self)
+        ids, d2, hit = np.empty(n, np.int64), np.empty(n, np.int32), np.empty(max(n - 1, 0), np.uint8)
+        s = L.ClearanceSummary()
+        self.ctx.check(self.ctx.lib.wa_traj_clearance(grid.h, self.h, _ptr(ids), _ptr(d2), _ptr(hit) if len(hit) else None, C.byref(s)))
+        summary = {k: int(getattr(s, k)) for k, _ in L.ClearanceSummary._fields_}
+        return ids, d2, hit, summary
 
     def close(self):
         if getattr(self, "h", None):

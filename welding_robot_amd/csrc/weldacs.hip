@@ -26,6 +26,7 @@
 #include "grid_kernels.hpp"
 #include "gtsp_kernels.hpp"
 #include "traj_kernels.hpp"
+#include "clearance_kernels.hpp"
 #include "stl_text.hpp"
 
 // ------------------------------------------------------------------ handles
@@ -72,6 +73,9 @@ struct wa_grid {
     mutable std::vector<uint8_t> h_occ;
     mutable bool h_valid = false;
     mutable std::mutex h_mu;   // guards the mirror's first fill (concurrent wa_grid_resolve_points calls on one grid)
+    // exact squared distance field of the occupancy (wa_grid_distance_field): built on the first call that needs it, freed with the grid
+    mutable int32_t *d2 = nullptr;   // device, n
+    mutable std::mutex d2_mu;
 };
 struct wa_traj {
     wa_ctx *ctx;
@@ -756,5 +760,6 @@ void *wa_ctx_stream(wa_ctx *c) { return c ? (void *)c->stream : nullptr; }
 #include "host_gtsp.inc"
 #include "host_traj.inc"
 #include "host_comm.inc"
+#include "host_clearance.inc"
 
 }  // extern "C"
