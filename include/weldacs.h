@@ -445,6 +445,25 @@ typedef struct {
 int wa_traj_clearance(const wa_grid *g, const wa_traj *t, int64_t *ids_out, int32_t *d2_out, uint8_t *hit_out,
                       wa_clearance_summary *sum);
 
+/* ---- any-angle path shortening (not in the reference: its paths are lattice staircases) ----
+ * A path is a sequence of node ids v_0 ... v_{L-1}, raster ids of grid g, L >= 1.
+ * visible(a, b): the 3-D supercover between voxels a and b contains no occupied voxel of g.  This is exactly the segment test of
+ *   wa_traj_clearance: same events, tied axes stepped together, the full product set at a tie, voxel a itself included.
+ * Greedy shortcut with a span cap max_span >= 1: start with w_0 = 0.  From an anchor a < L-1, next(a) is the largest j in
+ *   [a+1, min(a+max_span, L-1)] such that visible(v_a, v_k) holds for EVERY k in (a, j] (prefix visibility, not just the last node);
+ *   if no such j exists, next(a) = a+1 (a 26-neighbour diagonal step that grazes an occupied edge, or an occupied node).  Stop when
+ *   L-1 is reached: the first and last nodes are always kept.
+ * Length: the sum over consecutive waypoints of sqrt(dx^2 + dy^2 + dz^2), in float64 on the fp32 axis-table coordinates
+ *   (wa_grid_read_coords), every operation correctly rounded on its own (no contraction; (dx*dx + dy*dy) + dz*dz), summed
+ *   sequentially in waypoint order.
+ *
+ * n_paths paths back to back: path p = ids[off[p] .. off[p+1]) (n_paths+1 offsets, off[0] = 0, non-decreasing, empty paths allowed).
+ * wp_idx (off[n_paths] entries): for path p, its waypoints as indices INTO path p, written at wp_idx[off[p] .. off[p] + wp_count[p]);
+ * later entries of its range are left untouched.  length_out (may be NULL): the shortened length in metres.
+ * WA_ERR_ARG: NULL g/ids/off/wp_idx/wp_count, n_paths < 0, max_span < 1 or > 4096, off not non-decreasing, an id outside the grid. */
+int wa_grid_path_shortcut(const wa_grid *g, const int64_t *ids, const int64_t *off, int32_t n_paths, int32_t max_span,
+                          int64_t *wp_idx, int32_t *wp_count, double *length_out);
+
 #ifdef __cplusplus
 }
 #endif

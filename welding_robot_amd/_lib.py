@@ -131,6 +131,7 @@ SYMBOLS = {
     "wa_grid_distance_field": (C.c_int, [_V, _P]),
     "wa_grid_inflate": (C.c_int, [_V, _F, _P, _I, C.POINTER(_V)]),
     "wa_traj_clearance": (C.c_int, [_V, _V, _P, _P, _P, C.POINTER(ClearanceSummary)]),
+    "wa_grid_path_shortcut": (C.c_int, [_V, _P, _P, _I, _I, _P, _P, _P]),
 }
 
 _libs = {}

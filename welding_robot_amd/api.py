@@ -187,6 +187,11 @@ class Grid:
         """a clearance in metres as a radius in voxels (exact up to the hi-side seam of the wall, see include/weldacs.h)"""
         return float(metres) / float(self.precision)
 
+    def shortcut(self, path, max_span=128):
+        """wa_grid_path_shortcut of one path: (waypoint node ids, shortened length in metres)"""
+        wps, lengths = shortcut_paths(self, [path], max_span)
+        return wps[0], float(lengths[0])
+
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.wa_grid_destroy(self.h)
@@ -194,6 +199,20 @@ class Grid:
 
     def __del__(self):
         self.close()
+
+
+def shortcut_paths(grid, paths, max_span=128):
+    """wa_grid_path_shortcut of a batch of paths (node-id arrays) in one call: ([waypoint node ids per path], float64 lengths)"""
+    paths = [np.ascontiguousarray(p, np.int64).reshape(-1) for p in paths]
+    ids = np.concatenate(paths) if paths else np.zeros(0, np.int64)
+    off = np.concatenate([[0], np.cumsum([len(p) for p in paths])]).astype(np.int64)
+    wp = np.empty(max(len(ids), 1), np.int64)
+    cnt = np.empty(max(len(paths), 1), np.int32)
+    lengths = np.empty(len(paths), np.float64)
+    ctx = grid.ctx
+    ctx.check(ctx.lib.wa_grid_path_shortcut(grid.h, _ptr(ids), _ptr(off), len(paths), int(max_span), _ptr(wp), _ptr(cnt),
+                                       _ptr(lengths) if len(paths) else None))
+    return [p[wp[off[k]:off[k] + cnt[k]]] for k, p in enumerate(paths)], lengths
 
 
 def default_params(**kw):

@@ -202,46 +202,53 @@ __global__ __launch_bounds__(256) void k_clr_samples(const float *__restrict__ x
     }
 }
 
+// Does the 3-D supercover between voxels a and b meet an occupied voxel of free_ (1 = free)?  Axis c with d_c != 0 changes voxel at
+// t = (2m + 1) / (2 |d_c|), m = 0 .. |d_c| - 1; at such a t that axis holds both voxels around the boundary.  The walk visits the
+// events in order (compared by cross-multiplying), steps the axes tied at an event together and tests every voxel of the product of
+// the axes' sets there (up to 8 around a shared corner); with no event the cover is voxel a.  Returns at the first occupied voxel.
+// Shared by wa_traj_clearance (k_clr_segments) and wa_grid_path_shortcut (k_sc_reach): one definition of the segment test.
+__device__ inline bool clr_cover_hits(long long a, long long b, WaDims d, const uint8_t *__restrict__ free_)
+{
+    int32_t cur[3] = {(int32_t)(a % d.nx), (int32_t)((a / d.nx) % d.ny), (int32_t)(a / d.nxy)};
+    const int32_t end[3] = {(int32_t)(b % d.nx), (int32_t)((b / d.nx) % d.ny), (int32_t)(b / d.nxy)};
+    int32_t s[3], D[3], m[3];
+    for (int c = 0; c < 3; c++) {
+        const int32_t dd = end[c] - cur[c];
+        s[c] = dd > 0 ? 1 : (dd < 0 ? -1 : 0);
+        D[c] = dd > 0 ? dd : -dd;
+        m[c] = 0;
+    }
+    bool hit = !free_[a];
+    while (!hit) {
+        // the earliest pending event: t_c = (2 m_c + 1) / (2 D_c)
+        int best = -1;
+        for (int c = 0; c < 3; c++) {
+            if (m[c] >= D[c]) continue;
+            if (best < 0 || (int64_t)(2 * m[c] + 1) * D[best] < (int64_t)(2 * m[best] + 1) * D[c]) best = c;
+        }
+        if (best < 0) break;
+        bool tie[3];
+        for (int c = 0; c < 3; c++)
+            tie[c] = m[c] < D[c] && (int64_t)(2 * m[c] + 1) * D[best] == (int64_t)(2 * m[best] + 1) * D[c];
+        for (int q = 0; q < 8 && !hit; q++) {
+            if (((q & 1) && !tie[0]) || ((q & 2) && !tie[1]) || ((q & 4) && !tie[2])) continue;
+            const int32_t x = cur[0] + ((q & 1) ? s[0] : 0), y = cur[1] + ((q & 2) ? s[1] : 0), z = cur[2] + ((q & 4) ? s[2] : 0);
+            hit = !free_[(int64_t)z * d.nxy + (int64_t)y * d.nx + x];
+        }
+        for (int c = 0; c < 3; c++)
+            if (tie[c]) { cur[c] += s[c]; m[c]++; }
+    }
+    return hit;
+}
+
 // one lane per segment i (samples i, i+1): does the 3-D supercover between the two sample voxels meet an occupied voxel?
-// Axis c with d_c != 0 changes voxel at t = (2m + 1) / (2 |d_c|), m = 0 .. |d_c| - 1; at such a t that axis holds both voxels around
-// the boundary.  The walk visits the events in order (compared by cross-multiplying), steps the axes tied at an event together and
-// tests every voxel of the product of the axes' sets there (up to 8 around a shared corner); with no event the cover is voxel a.
 __global__ __launch_bounds__(256) void k_clr_segments(const long long *__restrict__ ids, int64_t n, WaDims d, const uint8_t *__restrict__ free_,
                                                       uint8_t *__restrict__ hit_out, unsigned long long *__restrict__ acc /* [1] first, [2] n_hit */)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     bool hit = false;
     if (i + 1 < n) {
-        const long long a = ids[i], b = ids[i + 1];
-        int32_t cur[3] = {(int32_t)(a % d.nx), (int32_t)((a / d.nx) % d.ny), (int32_t)(a / d.nxy)};
-        const int32_t end[3] = {(int32_t)(b % d.nx), (int32_t)((b / d.nx) % d.ny), (int32_t)(b / d.nxy)};
-        int32_t s[3], D[3], m[3];
-        for (int c = 0; c < 3; c++) {
-            const int32_t dd = end[c] - cur[c];
-            s[c] = dd > 0 ? 1 : (dd < 0 ? -1 : 0);
-            D[c] = dd > 0 ? dd : -dd;
-            m[c] = 0;
-        }
-        hit = !free_[a];
-        while (!hit) {
-            // the earliest pending event: t_c = (2 m_c + 1) / (2 D_c)
-            int best = -1;
-            for (int c = 0; c < 3; c++) {
-                if (m[c] >= D[c]) continue;
-                if (best < 0 || (int64_t)(2 * m[c] + 1) * D[best] < (int64_t)(2 * m[best] + 1) * D[c]) best = c;
-            }
-            if (best < 0) break;
-            bool tie[3];
-            for (int c = 0; c < 3; c++)
-                tie[c] = m[c] < D[c] && (int64_t)(2 * m[c] + 1) * D[best] == (int64_t)(2 * m[best] + 1) * D[c];
-            for (int q = 0; q < 8 && !hit; q++) {
-                if (((q & 1) && !tie[0]) || ((q & 2) && !tie[1]) || ((q & 4) && !tie[2])) continue;
-                const int32_t x = cur[0] + ((q & 1) ? s[0] : 0), y = cur[1] + ((q & 2) ? s[1] : 0), z = cur[2] + ((q & 4) ? s[2] : 0);
-                hit = !free_[(int64_t)z * d.nxy + (int64_t)y * d.nx + x];
-            }
-            for (int c = 0; c < 3; c++)
-                if (tie[c]) { cur[c] += s[c]; m[c]++; }
-        }
+        hit = clr_cover_hits(ids[i], ids[i + 1], d, free_);
         if (hit_out) hit_out[i] = hit ? 1 : 0;
     }
     unsigned long long first = hit ? (unsigned long long)i : ~0ull, cnt = hit ? 1 : 0;

@@ -27,6 +27,7 @@
 #include "gtsp_kernels.hpp"
 #include "traj_kernels.hpp"
 #include "clearance_kernels.hpp"
+#include "shortcut_kernels.hpp"
 #include "stl_text.hpp"
 
 // ------------------------------------------------------------------ handles
@@ -761,5 +762,6 @@ void *wa_ctx_stream(wa_ctx *c) { return c ? (void *)c->stream : nullptr; }
 #include "host_traj.inc"
 #include "host_comm.inc"
 #include "host_clearance.inc"
+#include "host_shortcut.inc"
 
 }  // extern "C"
