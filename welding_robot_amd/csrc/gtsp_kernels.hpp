@@ -164,18 +164,30 @@ __global__ __launch_bounds__(256) void k_gtsp(WaGtspDev G)
 //     banks; pheromone / heuristic stay in global memory (L2-resident, touched n^2 per iteration);
 //   * the unvisited set J[k] (a std::set in the reference, :98) is a register bitmask;
 //   * the two ordered passes of select_next (:127-142) are plain predicated loops over the
-//     cities: adding +0.0 for a visited city leaves the fp64 partial sums bit-identical;
+//     cities: adding +0.0 for a visited city leaves the fp64 partial sums bit-identical
+//     (they start at +0.0 and so never hold -0.0);
 //   * the tour length is accumulated while the tour is built -- same additions, same order as
 //     ACS_Tour::calc (:36-44), closing edge excluded.
 // NW = number of 64-bit words of the unvisited mask (n <= 64*NW).  INFO_LDS: info fits in LDS.
-// 1.0 or 0.0 from bit c of a 32-bit mask word, built with two integer ops (no compare / select):
-// the visited mask then enters the ordered sum as fma(x, m, sum) -- exact, because x * 1.0 and
-// x * 0.0 are exact for finite x, so the fma rounds once exactly like `sum + x` / leaves sum alone.
-__device__ __forceinline__ double wa_bit_as_double(uint32_t word, int c)
+// sum + (bit c of a 32-bit mask word ? x : +0.0), two ways (no compare / select in either):
+//   EXACT = false: fma(x, m, sum) with m = 1.0 or 0.0 built by two integer ops.  Exact for FINITE x
+//     (x * 1.0 and x * 0.0 are exact, the fma rounds once like `sum + x` or leaves sum alone), and the
+//     cheapest form of the serial chain;
+//   EXACT = true: x ANDed with the sign-extended bit (one bfe, two ANDs), then a plain add: a masked
+//     term is exactly +0.0 whatever x holds.  For an iteration whose info matrix holds +inf or NaN,
+//     which the reference skips for visited cities while fma(inf, 0.0, sum) is NaN -- e.g. every seam
+//     at one point: pheromone_0 = cnt / 0 = +inf.  About 7 % slower, so only taken there.
+template <bool EXACT>
+__device__ __forceinline__ double wa_masked_add(double sum, double x, uint32_t word, int c)
 {
+    if (EXACT) {
+        const int m = (int)(word << (31 - c)) >> 31;
+        return sum + __hiloint2double(__double2hiint(x) & m, __double2loint(x) & m);
+    }
     const uint32_t hi = ((word >> c) & 1u) * 0x3FF00000u;
-    return __hiloint2double((int)hi, 0);
+    return __builtin_fma(x, __hiloint2double((int)hi, 0), sum);
 }
+template <bool B> struct WaBoolTag { static constexpr bool value = B; };
 template <int NW, bool INFO_LDS, bool PREFIX>
 __global__ __launch_bounds__(256) void k_gtsp_fast(WaGtspDev G)
 {
@@ -231,14 +243,19 @@ __global__ __launch_bounds__(256) void k_gtsp_fast(WaGtspDev G)
         if (tid == 0) s_stop = s_bad > n ? 1 : 0;  // :263
         __syncthreads();
         if (s_stop) break;
+        int nonfinite = 0;
         for (int64_t e = tid; e < nn; e += blockDim.x) {  // reset :114-119
             int32_t i = (int32_t)(e / n), j = (int32_t)(e % n);
-            info[(int64_t)i * ld + j] = wa_powi(pher[e], 1) * h6[e];
+            const double v = wa_powi(pher[e], 1) * h6[e];
+            info[(int64_t)i * ld + j] = v;
+            nonfinite |= !__builtin_isfinite(v);
         }
         if (G.rng_mode == 0 && tid == 0)  // the libc draws of this iteration in (step, ant) order
             for (int32_t q = 0; q < n * (n - 1); q++) G.rbuf[q] = wa_glibc_next(rr, rf, rb);
-        __syncthreads();
-        if (k < n) {  // construct_solution :146-159 for ant k
+        const bool exact = __syncthreads_or(nonfinite) != 0;   // block-uniform: see wa_masked_add
+        // construct_solution :146-159 for ant k; returns the cities left unvisited (0 for a tour visiting each once)
+        auto construct = [&](auto exact_tag) -> int32_t {
+            constexpr bool EXACT = decltype(exact_tag)::value;
             const uint64_t antkey = wa_ctr_antkey(wa_ctr_key(G.seed, G.stream0 + (uint32_t)inst, (uint32_t)it), (uint32_t)k);
             unsigned long long J[NW];
 #pragma unroll
@@ -261,7 +278,7 @@ __global__ __launch_bounds__(256) void k_gtsp_fast(WaGtspDev G)
                         const uint32_t m16 = (uint32_t)(J[NW == 1 ? 0 : (c0 >> 6)] >> (c0 & 63));
 #pragma unroll
                         for (int32_t i = 0; i < 16; i++) {
-                            sum = __builtin_fma(row[c0 + i], wa_bit_as_double(m16, i), sum);
+                            sum = wa_masked_add<EXACT>(sum, row[c0 + i], m16, i);
                             if (PREFIX) prefix[c0 + i] = sum;
                         }
                     }
@@ -289,7 +306,7 @@ __global__ __launch_bounds__(256) void k_gtsp_fast(WaGtspDev G)
                             const uint32_t m16 = (uint32_t)(J[NW == 1 ? 0 : (c0 >> 6)] >> (c0 & 63));
 #pragma unroll
                             for (int32_t i = 0; i < 16; i++) {
-                                sp = __builtin_fma(row[c0 + i], wa_bit_as_double(m16, i), sp);
+                                sp = wa_masked_add<EXACT>(sp, row[c0 + i], m16, i);
                                 if (!found && ((m16 >> i) & 1u) && sp >= rnd) { next = c0 + i; found = true; }
                             }
                         }
@@ -304,10 +321,14 @@ __global__ __launch_bounds__(256) void k_gtsp_fast(WaGtspDev G)
                 tours[(int64_t)k * n + step] = next;
                 r = next;
             }
+            return left;
+        };
+        if (k < n) {
+            const int32_t left = exact ? construct(WaBoolTag<true>()) : construct(WaBoolTag<false>());
             // tour length (calc :36-44) after the walk: the same in-order fp64 sum, but its distance loads no longer
             // sit one global round trip deep inside every construction step
             double L = 0;
-            r = k;
+            int32_t r = k;
             for (int32_t step = 0; step < n - 1; step++) {
                 const int32_t nx2 = tours[(int64_t)k * n + step];
                 L += r == nx2 ? 0.0 : dist[(int64_t)r * n + nx2];
