@@ -94,7 +94,7 @@ int64_t wa_stl_read_file(const char *path, float *tris, int64_t cap_tris);
 int wa_grid_from_mesh(wa_ctx *ctx, const float *tris, int64_t n_tris, float precision, int32_t wall,
                       wa_grid **out, float *bbox6_out);
 /* adopt an existing occupancy (free_[id] != 0 <=> isFree) with per-axis node coordinates --
- * the readGridMap path and the synthetic benchmark grids */
+ * the readGridMap path and the synthetic benchmark grids.  Grids up to 2^29 voxels (ids 0 .. 2^29 - 1); WA_ERR_ARG above. */
 int wa_grid_from_occupancy(wa_ctx *ctx, const uint8_t *free_, int32_t nx, int32_t ny, int32_t nz,
                            const float *cx, const float *cy, const float *cz, float precision,
                            int32_t wall, wa_grid **out);
@@ -136,7 +136,8 @@ void wa_acs_default_params(wa_acs_params *p);
  * at most 8 ranks deposit, ACSRank_3D.hpp:200 -- 48 B/voxel otherwise) and its ants' paths (4 B * max_colony *
  * path_capacity); the heuristic fields (24 B/voxel) are a pool shared by the slots: one per distinct END point in use,
  * computed by wa_acs_begin when the pool does not hold it yet.  max_colony bounds the ants per generation,
- * path_capacity the nodes per walk (<= number of voxels). */
+ * path_capacity the nodes per walk (<= number of voxels).  Grids up to 89,478,485 voxels (the walk addresses a field with
+ * signed 32-bit byte offsets: 24 B * voxels < 2^31); WA_ERR_ARG above. */
 int wa_acs_create(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, int32_t max_colony,
                   int64_t path_capacity, wa_acs **out);
 /* Same with an explicit neighbourhood: 6 = face neighbours (what wa_acs_create builds, the reference as

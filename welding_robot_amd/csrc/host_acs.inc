@@ -96,7 +96,7 @@ static int acs_create_once(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, in
         delete s;
         return fail(ctx, WA_ERR_ARG, "wa_acs_create: grids above 89,478,485 voxels (~447^3) are not supported");
     }
-    if (nb == 26 && n > (int64_t)WaNbT<26>::IDM) {  // path word = 27-bit voxel id + 5-bit edge index
+    if (nb == 26 && n > (int64_t)WaNbT<26>::IDM + 1) {  // path word = 27-bit voxel id + 5-bit edge index: ids 0 .. 2^27 - 1
         delete s;
         return fail(ctx, WA_ERR_ARG, "wa_acs_create: 26-neighbour grids above 2^27 voxels (512^3) are not supported");
     }

@@ -46,7 +46,7 @@ static int grid_alloc(wa_ctx *ctx, int32_t nx, int32_t ny, int32_t nz, const flo
 {
     if (nx < 1 || ny < 1 || nz < 1) return fail(ctx, WA_ERR_ARG, "grid dimensions must be >= 1");
     int64_t n = (int64_t)nx * ny * nz;
-    if (n > (int64_t)WA_ID_MASK) return fail(ctx, WA_ERR_ARG, "grid larger than 2^29 voxels");
+    if (n > (int64_t)WA_ID_MASK + 1) return fail(ctx, WA_ERR_ARG, "grid larger than 2^29 voxels");   // ids 0 .. 2^29 - 1 fit WA_ID_MASK
     wa_grid *g = new wa_grid();
     g->ctx = ctx;
     g->d.nx = nx; g->d.ny = ny; g->d.nz = nz; g->d.nxy = nx * ny; g->d.n = n;
