@@ -30,7 +30,8 @@ from welding_robot_amd import dist as wd  # noqa: E402
 
 
 def plan(ctx, grid, point_ids, generations, predict, seed, slots, rank=0, world=1, fixed_colony=0, lazy=False, neighbourhood=6,
-         shortcut=0):
+         shortcut=0, skip=()):
+    """skip: pairs (i, j) known to have no path (--geodesic): not searched, their cost is +inf and their path empty"""
     P = len(point_ids)
     pairs = [(i, j) for i in range(P) for j in range(i + 1, P)]
     # dealing and order: longest-processing-time-first over end-point groups (welding_robot_amd/dist.py: deal_pairs -- the rule
@@ -40,6 +41,8 @@ def plan(ctx, grid, point_ids, generations, predict, seed, slots, rank=0, world=
     weights = [1 + sum(abs(a - b) for a, b in zip(vox[i], vox[j])) for i, j in pairs]
     shards, _ = wd.deal_pairs(pairs, weights, world)
     mine = shards[rank]
+    if skip:
+        mine = [k for k in mine if pairs[k] not in skip]
     colony = fixed_colony or max(1, int(0.35 * predict / float(grid.precision)))
     by_length = os.environ.get("WA_PLAN_ORDER", "") == "length"
     if by_length:   # experiment (round 6): batches of searches of similar length -- a batch-generation lasts as long as its longest walk
@@ -56,8 +59,12 @@ def plan(ctx, grid, point_ids, generations, predict, seed, slots, rank=0, world=
                            rng_mode=api.RNG_DEV, seed=seed)
     cost = np.zeros((P, P), np.float64)
     paths = {}
+    for i, j in skip:
+        cost[i, j] = cost[j, i] = np.inf
+        if pairs.index((i, j)) in shards[rank]:
+            paths[(i, j)] = np.zeros(0, np.int32)
     plan.last_batch_s = []                             # seconds per batch: solve / reset / read-back (tools/walk_direct_ab.py --batches)
-    plan.last_shortcut = {}                            # shortcut > 0: {(i, j): waypoint node ids} (the pair's cost is then their length)
+    plan.last_shortcut = {ij: paths[ij] for ij in paths} if shortcut else {}   # shortcut > 0: {(i, j): waypoint node ids} (the pair's cost is then their length)
     for b0 in range(0, len(mine), slots):
         idx = mine[b0:b0 + slots] if by_length else wd.order_batch(mine[b0:b0 + slots], weights)   # (longest searches first in each half of the slots)
         tb = [time.perf_counter()]
@@ -78,6 +85,28 @@ def plan(ctx, grid, point_ids, generations, predict, seed, slots, rank=0, world=
             if shortcut:
                 plan.last_shortcut[(i, j)] = wps[q]
     solver.close()
+    return cost, paths, len(mine)
+
+
+def plan_exact(grid, point_ids, rank=0, world=1, shortcut=0):
+    """--exact-paths: the pair paths from the exact planner (wa_grid_geodesic_paths: one breadth-first field per start point) instead of
+    the colony; a pair's cost is the length of its path in metres (span-1 length from shortcut_paths), or of its shortened path.
+    Same return values as plan(); pair k belongs to rank k % world."""
+    P = len(point_ids)
+    pairs = [(i, j) for i in range(P) for j in range(i + 1, P)]
+    mine = [k for k in range(len(pairs)) if k % world == rank]
+    hops, ids_all = api.geodesic_paths(grid, [point_ids[pairs[k][0]] for k in mine], [point_ids[pairs[k][1]] for k in mine])
+    ids_all = [np.zeros(0, np.int64) if p is None else p for p in ids_all]
+    wps, lengths = api.shortcut_paths(grid, ids_all, shortcut or 1)
+    cost = np.zeros((P, P), np.float64)
+    paths = {}
+    plan.last_slots, plan.last_create_s, plan.last_batch_s, plan.last_shortcut = 0, 0.0, [], {}
+    for q, k in enumerate(mine):
+        i, j = pairs[k]
+        cost[i, j] = cost[j, i] = lengths[q] if hops[q] >= 0 else np.inf
+        paths[(i, j)] = ids_all[q]
+        if shortcut:
+            plan.last_shortcut[(i, j)] = wps[q]
     return cost, paths, len(mine)
 
 
@@ -109,6 +138,11 @@ def main():
                     help="shorten every pair path by line of sight on the planning grid (wa_grid_path_shortcut): the shortened lengths are "
                          "the pair costs of the seam order, and the waypoints are the coarse points of the cubic fit")
     ap.add_argument("--max-span", type=int, default=128, help="--shortcut: the farthest node an anchor may see (1..4096)")
+    ap.add_argument("--geodesic", action="store_true",
+                    help="exact hop matrix of the weld points on the planning grid first (wa_grid_geodesic_matrix): pairs without any path "
+                         "are not searched and are listed, and every search is held against the optimum")
+    ap.add_argument("--exact-paths", action="store_true",
+                    help="take the pair paths from the exact planner (wa_grid_geodesic_paths) instead of the colony")
     args = ap.parse_args()
     rank, local_rank, world = wd.env_rank()
     ctx = api.Context(local_rank)
@@ -136,9 +170,21 @@ def main():
     if args.clearance is not None:
         # plan with a safety margin: every voxel nearer the metal than the radius becomes an obstacle, except around the weld points
         grid = metal.inflate(metal.clearance_radius(args.clearance), pts)
+    hop_matrix, unreachable = None, []
+    if args.geodesic:
+        t_geo = time.perf_counter()
+        hop_matrix = grid.geodesic_matrix(pts)
+        t_geo = time.perf_counter() - t_geo
+        unreachable = [(i, j) for i in range(args.points) for j in range(i + 1, args.points) if hop_matrix[i, j] == api.WA_HOPS_NONE]
     t0 = time.perf_counter()
-    cost, paths, n_mine = plan(ctx, grid, pts, args.generations, predict, args.seed, args.slots, rank, world, lazy=args.lazy, neighbourhood=args.neighbourhood,
-                               shortcut=args.max_span if args.shortcut else 0)
+    if args.exact_paths:
+        cost, paths, n_mine = plan_exact(grid, pts, rank, world, shortcut=args.max_span if args.shortcut else 0)
+    elif args.geodesic:
+        cost, paths, n_mine = plan(ctx, grid, pts, args.generations, predict, args.seed, args.slots, rank, world, lazy=args.lazy, neighbourhood=args.neighbourhood,
+                                   shortcut=args.max_span if args.shortcut else 0, skip=unreachable)
+    else:
+        cost, paths, n_mine = plan(ctx, grid, pts, args.generations, predict, args.seed, args.slots, rank, world, lazy=args.lazy, neighbourhood=args.neighbourhood,
+                                   shortcut=args.max_span if args.shortcut else 0)
     short = plan.last_shortcut
     if comm is not None:
         # every pair is owned by exactly one rank: its cost goes to every rank, its path to rank 0 (the library's own collectives)
@@ -160,6 +206,24 @@ def main():
     t_pairs -= plan.last_create_s
     out = dict(grid=n, points=args.points, neighbourhood=args.neighbourhood, slots=plan.last_slots, lazy_evaporation=bool(args.lazy), t_solver_create_s=plan.last_create_s, pairs=args.points * (args.points - 1) // 2, world=world,
                pairs_this_rank=n_mine, t_pairs_s=t_pairs, all_reached=bool(finite))
+    if args.exact_paths:
+        out.update(exact_paths=True)
+    if rank == 0 and args.geodesic:
+        # every search against the optimum: a lattice path of len nodes has len - 1 steps, never fewer than the hop count
+        gone = set(unreachable)
+        ratios, at_opt, left = [], 0, []
+        for (i, j), ids in sorted(paths.items()):
+            if (i, j) in gone:
+                continue
+            if not np.isfinite(cost[i, j]):
+                left.append([i, j])
+                continue
+            steps, h = len(ids) - 1, int(hop_matrix[i, j])
+            at_opt += steps == h
+            ratios.append(steps / h if h else 1.0)
+        out.update(geodesic=dict(t_matrix_s=t_geo, unreachable_pairs=[list(ij) for ij in unreachable], reachable_pairs=out["pairs"] - len(unreachable),
+                                 searches_at_optimum=int(at_opt), ratio_mean=float(np.mean(ratios)) if ratios else None,
+                                 ratio_max=float(np.max(ratios)) if ratios else None, left_at_inf=left))
     if rank == 0 and finite:
         t1 = time.perf_counter()
         tour = api.gtsp_solve(ctx, cost, mode=api.RNG_DEV, seed=args.seed)

@@ -465,6 +465,41 @@ int wa_traj_clearance(const wa_grid *g, const wa_traj *t, int64_t *ids_out, int3
 int wa_grid_path_shortcut(const wa_grid *g, const int64_t *ids, const int64_t *off, int32_t n_paths, int32_t max_span,
                           int64_t *wp_idx, int32_t *wp_count, double *length_out);
 
+/* ---- exact shortest-path fields (not in the reference: its planner is the colony alone) ----
+ * The graph: the free voxels of g (wa_grid_read_occupancy != 0); voxel (x, y, z) has raster id x + nx * (y + ny * z).  Two free voxels are
+ * joined iff they differ by 1 in exactly one coordinate (the 6-neighbour lattice), every step costs 1.  Neighbours are taken in the fixed
+ * order -x, +x, -y, +y, -z, +z; a neighbour outside the grid does not exist.  26-neighbour lattices have step weights 1, sqrt 2, sqrt 3
+ * and need a different algorithm (unit steps make this breadth-first search): out of scope here.
+ * hops(s, v): the number of steps of a shortest such path from s to v; 0 for v = s; WA_HOPS_NONE when there is none (v lies in another
+ *   component, or is occupied).  An int32, exact at any length a grid allows (also beyond 65 535).
+ * path(s, e), for hops(s, e) = h >= 0: the h + 1 ids p_0 ... p_h with p_h = e and, for k = h ... 1, p_{k-1} = the first neighbour
+ *   n of p_k in the order above that is inside the grid, free and has hops(s, n) = k - 1.  With s == e it is the one id.
+ * Sources, starts and ends must be free voxels: an occupied one is WA_ERR_ARG (wa_last_error says so), like an id outside the grid, a
+ * NULL id array (also with a count of 0), a NULL output or a negative count; on WA_ERR_ARG no output has been written.  Counts of 0
+ * with valid pointers succeed and write nothing.
+ *
+ * Everything runs on the context's stream and g is not modified; a bit-packed copy of its occupancy (one bit per voxel, rows in x
+ * padded to 64) is built by the first call and kept with the grid like the distance field (freed by wa_grid_destroy).  Per source the
+ * search keeps three such bitmaps on the device, and a field of 4 bytes per voxel where one is needed (_fields, _paths); sources are
+ * processed in chunks of at most half of what wa_ctx_memory_info reports free over that cost, at least 1, at most 65 535
+ * (WA_ERR_ALLOC when one source does not fit).  Results do not depend on the chunking and are the same bytes on every call.
+ *
+ * wa_grid_geodesic_fields: hops_out[s * n + v] = hops(src_ids[s], v) for every voxel v (n = nx * ny * nz; n_src * n int32 on the host).
+ * wa_grid_geodesic_matrix: hops_out[i * n_pts + j] = hops(point_ids[i], point_ids[j]): symmetric, 0 on the diagonal, WA_HOPS_NONE where
+ *   the two points are not connected.  No field is stored; a point's search ends as soon as every point has been reached.
+ * wa_grid_geodesic_paths: pair p = (start_ids[p], end_ids[p]); off holds n_pairs + 1 non-decreasing offsets (off[0] need not be 0) and
+ *   gives pair p the range ids_out[off[p] .. off[p+1]).  hops_out[p] = hops(start, end) is filled for every pair.  A pair with
+ *   hops >= 0 whose range holds at least hops + 1 ids gets path(start, end) at ids_out[off[p] .. off[p] + hops]; later entries of its
+ *   range are left untouched.  An unreachable pair writes nothing and is no error.  If some reachable pair's range is too short, nothing
+ *   is written into that pair's range, all other pairs are written as usual and the call returns WA_ERR_CAPACITY: size off from
+ *   hops_out (or from the matrix) and call again.  Pairs that share a start share one field, in whatever order they come.
+ *   Also WA_ERR_ARG: off decreasing. */
+#define WA_HOPS_NONE (-1)
+int wa_grid_geodesic_fields(const wa_grid *g, const int64_t *src_ids, int32_t n_src, int32_t *hops_out);
+int wa_grid_geodesic_matrix(const wa_grid *g, const int64_t *point_ids, int32_t n_pts, int32_t *hops_out);
+int wa_grid_geodesic_paths(const wa_grid *g, const int64_t *start_ids, const int64_t *end_ids, int32_t n_pairs,
+                           const int64_t *off, int64_t *ids_out, int32_t *hops_out);
+
 #ifdef __cplusplus
 }
 #endif

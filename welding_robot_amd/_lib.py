@@ -28,6 +28,7 @@ class GtspParams(C.Structure):
 
 
 WA_D2_NONE = 0x7fffffff
+WA_HOPS_NONE = -1
 
 
 class ClearanceSummary(C.Structure):
@@ -132,6 +133,9 @@ SYMBOLS = {
     "wa_grid_inflate": (C.c_int, [_V, _F, _P, _I, C.POINTER(_V)]),
     "wa_traj_clearance": (C.c_int, [_V, _V, _P, _P, _P, C.POINTER(ClearanceSummary)]),
     "wa_grid_path_shortcut": (C.c_int, [_V, _P, _P, _I, _I, _P, _P, _P]),
+    "wa_grid_geodesic_fields": (C.c_int, [_V, _P, _I, _P]),
+    "wa_grid_geodesic_matrix": (C.c_int, [_V, _P, _I, _P]),
+    "wa_grid_geodesic_paths": (C.c_int, [_V, _P, _P, _I, _P, _P, _P]),
 }
 
 _libs = {}

@@ -7,7 +7,7 @@ import weakref
 import numpy as np
 
 from . import _lib as L
-from ._lib import AcsParams, GtspParams, RNG_DEV, RNG_REF, WA_D2_NONE, WeldacsError  # noqa: F401
+from ._lib import AcsParams, GtspParams, RNG_DEV, RNG_REF, WA_D2_NONE, WA_HOPS_NONE, WeldacsError  # noqa: F401
 
 
 def _ptr(a):
@@ -192,6 +192,24 @@ class Grid:
         wps, lengths = shortcut_paths(self, [path], max_span)
         return wps[0], float(lengths[0])
 
+    def geodesic_fields(self, ids):
+        """wa_grid_geodesic_fields: int32 [len(ids), n], exact hop counts on the 6-neighbour lattice of free voxels from each source
+        (free voxels) to every voxel; WA_HOPS_NONE (-1) where there is no path"""
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        out = np.empty((len(ids), self.n), np.int32)
+        self.ctx.check(self.ctx.lib.wa_grid_geodesic_fields(self.h, _ptr(ids if len(ids) else np.zeros(1, np.int64)), len(ids),
+                                                            _ptr(out if out.size else np.zeros(1, np.int32))))
+        return out
+
+    def geodesic_matrix(self, ids):
+        """wa_grid_geodesic_matrix: int32 [P, P] hop counts between the points (symmetric, 0 on the diagonal, WA_HOPS_NONE (-1) where
+        two points are not connected)"""
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        out = np.empty((len(ids), len(ids)), np.int32)
+        self.ctx.check(self.ctx.lib.wa_grid_geodesic_matrix(self.h, _ptr(ids if len(ids) else np.zeros(1, np.int64)), len(ids),
+                                                            _ptr(out if out.size else np.zeros(1, np.int32))))
+        return out
+
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.wa_grid_destroy(self.h)
@@ -213,6 +231,29 @@ def shortcut_paths(grid, paths, max_span=128):
     ctx.check(ctx.lib.wa_grid_path_shortcut(grid.h, _ptr(ids), _ptr(off), len(paths), int(max_span), _ptr(wp), _ptr(cnt),
                                        _ptr(lengths) if len(paths) else None))
     return [p[wp[off[k]:off[k] + cnt[k]]] for k, p in enumerate(paths)], lengths
+
+
+def geodesic_paths(grid, starts, ends):
+    """wa_grid_geodesic_paths of a batch of pairs: (int32 hops, [node-id array per pair, start first; None where hops is WA_HOPS_NONE]).
+    Two calls: the first, with empty ranges, returns the hop counts (WA_ERR_CAPACITY is its expected status when any pair is
+    reachable), the second writes the paths into ranges of hops + 1 ids."""
+    starts = np.ascontiguousarray(starts, np.int64).reshape(-1)
+    ends = np.ascontiguousarray(ends, np.int64).reshape(-1)
+    assert len(starts) == len(ends)
+    n = len(starts)
+    ctx = grid.ctx
+    hops = np.empty(max(n, 1), np.int32)
+    off = np.zeros(n + 1, np.int64)
+    pad = np.zeros(1, np.int64)
+    rc = ctx.lib.wa_grid_geodesic_paths(grid.h, _ptr(starts if n else pad), _ptr(ends if n else pad), n, _ptr(off), _ptr(pad), _ptr(hops))
+    if rc not in (0, 7):
+        ctx.check(rc)
+    hops = hops[:n]
+    off[1:] = np.cumsum(np.maximum(hops.astype(np.int64) + 1, 0))
+    ids = np.empty(max(int(off[-1]), 1), np.int64)
+    if rc == 7:
+        ctx.check(ctx.lib.wa_grid_geodesic_paths(grid.h, _ptr(starts), _ptr(ends), n, _ptr(off), _ptr(ids), _ptr(hops)))
+    return hops, [ids[off[k]:off[k + 1]].copy() if hops[k] >= 0 else None for k in range(n)]
 
 
 def default_params(**kw):

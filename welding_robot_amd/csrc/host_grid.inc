@@ -163,7 +163,7 @@ void wa_grid_destroy(wa_grid *g)
 {
     WaDevGuard dev_guard_(g ? g->ctx : nullptr);
     if (!g) return;
-    hipFree(g->cx); hipFree(g->cy); hipFree(g->cz); hipFree(g->occ); hipFree(g->d2);
+    hipFree(g->cx); hipFree(g->cy); hipFree(g->cz); hipFree(g->occ); hipFree(g->d2); hipFree(g->fbits);
     delete g;
 }
 int wa_grid_info(const wa_grid *g, int32_t dims3[3], float *precision, int32_t *wall, int64_t *n_free)

@@ -28,6 +28,7 @@
 #include "traj_kernels.hpp"
 #include "clearance_kernels.hpp"
 #include "shortcut_kernels.hpp"
+#include "geodesic_kernels.hpp"
 #include "stl_text.hpp"
 
 // ------------------------------------------------------------------ handles
@@ -77,6 +78,10 @@ struct wa_grid {
     // exact squared distance field of the occupancy (wa_grid_distance_field): built on the first call that needs it, freed with the grid
     mutable int32_t *d2 = nullptr;   // device, n
     mutable std::mutex d2_mu;
+    // bit-packed copy of the occupancy (1 = free, 64 voxels of a row in x per word, rows padded to whole words) for the geodesic
+    // searches: built on the first wa_grid_geodesic_* call, freed with the grid
+    mutable unsigned long long *fbits = nullptr;   // device
+    mutable std::mutex fbits_mu;
 };
 struct wa_traj {
     wa_ctx *ctx;
@@ -763,5 +768,6 @@ void *wa_ctx_stream(wa_ctx *c) { return c ? (void *)c->stream : nullptr; }
 #include "host_comm.inc"
 #include "host_clearance.inc"
 #include "host_shortcut.inc"
+#include "host_geodesic.inc"
 
 }  // extern "C"
