@@ -110,6 +110,70 @@ def plan_exact(grid, point_ids, rank=0, world=1, shortcut=0):
     return cost, paths, len(mine)
 
 
+def plan_safe(grid, point_ids, radius, rank=0, world=1, shortcut=0):
+    """--safe-paths R: the pair paths that minimise the sum of clearance costs (wa_grid_clearance_costs with bands at 1^2 .. R^2, then
+    wa_grid_weighted_paths) instead of the number of steps: they keep away from the metal where there is room and squeeze through where
+    there is not.  A pair's cost for the seam order is a length, as in plan_exact (the weighted distance is not one).
+    Same return values as plan(); pair k belongs to rank k % world."""
+    P = len(point_ids)
+    pairs = [(i, j) for i in range(P) for j in range(i + 1, P)]
+    mine = [k for k in range(len(pairs)) if k % world == rank]
+    bands = [k * k for k in range(1, radius + 1)]
+    t0 = time.perf_counter()
+    costs = grid.clearance_costs(bands)
+    t1 = time.perf_counter()
+    dist, lens, ids_all = api.weighted_paths(grid, costs, [point_ids[pairs[k][0]] for k in mine], [point_ids[pairs[k][1]] for k in mine])
+    plan.last_safe = dict(t_costs_s=t1 - t0, t_paths_s=time.perf_counter() - t1, bands=bands)
+    ids_all = [np.zeros(0, np.int64) if p is None else p for p in ids_all]
+    wps, lengths = api.shortcut_paths(grid, ids_all, shortcut or 1)
+    cost = np.zeros((P, P), np.float64)
+    paths = {}
+    plan.last_slots, plan.last_create_s, plan.last_batch_s, plan.last_shortcut = 0, 0.0, [], {}
+    for q, k in enumerate(mine):
+        i, j = pairs[k]
+        cost[i, j] = cost[j, i] = lengths[q] if dist[q] >= 0 else np.inf
+        paths[(i, j)] = ids_all[q]
+        if shortcut:
+            plan.last_shortcut[(i, j)] = wps[q]
+    return cost, paths, len(mine)
+
+
+def smooth(ctx, grid, segs, wsegs, rev):
+    """main.cpp:283-352 on the device: the tour's segments stitched, then the two smoothing passes; wsegs (--shortcut): the shortened
+    segments, whose waypoints are then the coarse points of the cubic fit.  Returns (samples, ok flags, what goes into the JSON)."""
+    info = {}
+    path = api.Trajectory.stitch(grid, segs, rev)
+    ends = path.points()[[0, -1]]
+    s2 = None
+    if wsegs is not None:
+        # the shortened segments stitched the same way: their waypoints are the coarse points of the cubic fit
+        wpath = api.Trajectory.stitch(grid, wsegs, rev)
+        # float64 lengths on rank 0 (the gathered costs are fp32): with a span of 1 a path's length is the sum over all its nodes,
+        # so over the waypoints it is the shortened length bit for bit, and over the pair paths the unshortened (lattice) one
+        lens = api.shortcut_paths(grid, wsegs, 1)[1]
+        lattice = api.shortcut_paths(grid, segs, 1)[1]
+        info.update(shortened_length_total=float(lens.sum()), lattice_length_total=float(lattice.sum()), waypoints=len(wpath))
+        try:
+            s2 = api.Bspline(ctx, 3, 3, 2, 2, len(wpath))
+            coarse = wpath
+        except api.WeldacsError as e:
+            if e.code != 1:
+                raise
+        info.update(shortcut_smoothing=s2 is not None)
+    if s2 is None:   # today's coarse points: every 8th node of the stitched path
+        s1 = api.Bspline(ctx, 3, 0, 0, 0, len(path))          # BS_Basic<float,3,0,0,0>: time-indexed resampling
+        s1.set_param(ends[0], ends[1], path, 150.0)
+        n1 = max(16, len(path) // 8)
+        _, _, coarse = s1.sample(150.0 / n1, 150.0 / n1, n1, host=False, device=True)
+        s2 = api.Bspline(ctx, 3, 3, 2, 2, len(coarse))        # cubic with zero end velocity / acceleration
+    z = np.zeros((2, 3), np.float32)
+    s2.set_param(np.vstack([ends[:1], z]), np.vstack([ends[1:], z]), coarse, 6000.0)
+    traj, ok = s2.sample(0.0, 1.0, 6001)                  # 1 kHz over 6 s
+    info.update(stitched_nodes=len(path), coarse_points=len(coarse), trajectory_samples=int(ok.sum()),
+                trajectory_length=float(np.linalg.norm(np.diff(traj, axis=0), axis=1).sum()))
+    return traj, ok, info
+
+
 def wait_for_device_memory(ctx, want=0.85, timeout_s=30.0):
     """A process that has just exited may still be giving its device memory back; allocations made meanwhile can end up in
     host-visible memory (measured: the whole run 4x slower).  Wait until most of the device memory is free."""
@@ -143,6 +207,9 @@ def main():
                          "are not searched and are listed, and every search is held against the optimum")
     ap.add_argument("--exact-paths", action="store_true",
                     help="take the pair paths from the exact planner (wa_grid_geodesic_paths) instead of the colony")
+    ap.add_argument("--safe-paths", type=int, default=0, choices=range(1, 8), metavar="R",
+                    help="take the pair paths from the clearance-weighted exact planner (wa_grid_weighted_paths) instead of the colony: "
+                         "entering a voxel costs 1 + the number of bands 1^2 .. R^2 (voxels squared) its distance to the metal lies within")
     args = ap.parse_args()
     rank, local_rank, world = wd.env_rank()
     ctx = api.Context(local_rank)
@@ -177,7 +244,9 @@ def main():
         t_geo = time.perf_counter() - t_geo
         unreachable = [(i, j) for i in range(args.points) for j in range(i + 1, args.points) if hop_matrix[i, j] == api.WA_HOPS_NONE]
     t0 = time.perf_counter()
-    if args.exact_paths:
+    if args.safe_paths:
+        cost, paths, n_mine = plan_safe(grid, pts, args.safe_paths, rank, world, shortcut=args.max_span if args.shortcut else 0)
+    elif args.exact_paths:
         cost, paths, n_mine = plan_exact(grid, pts, rank, world, shortcut=args.max_span if args.shortcut else 0)
     elif args.geodesic:
         cost, paths, n_mine = plan(ctx, grid, pts, args.generations, predict, args.seed, args.slots, rank, world, lazy=args.lazy, neighbourhood=args.neighbourhood,
@@ -235,37 +304,32 @@ def main():
         edges = tour["edges"][0][:-1]
         segs = [paths[(min(a, b), max(a, b))] for a, b in edges]
         rev = [1 if a > b else 0 for a, b in edges]          # stored i<j; walk them in tour direction
-        path = api.Trajectory.stitch(grid, segs, rev)
-        ends = path.points()[[0, -1]]
-        s2 = None
-        if args.shortcut:
-            # the shortened segments stitched the same way: their waypoints are the coarse points of the cubic fit
-            wsegs = [short[(min(a, b), max(a, b))] for a, b in edges]
-            wpath = api.Trajectory.stitch(grid, wsegs, rev)
-            # float64 lengths on rank 0 (the gathered costs are fp32): with a span of 1 a path's length is the sum over all its nodes,
-            # so over the waypoints it is the shortened length bit for bit, and over the pair paths the unshortened (lattice) one
-            lens = api.shortcut_paths(grid, wsegs, 1)[1]
-            lattice = api.shortcut_paths(grid, segs, 1)[1]
-            out.update(shortened_length_total=float(lens.sum()), lattice_length_total=float(lattice.sum()), waypoints=len(wpath))
-            try:
-                s2 = api.Bspline(ctx, 3, 3, 2, 2, len(wpath))
-                coarse = wpath
-            except api.WeldacsError as e:
-                if e.code != 1:
-                    raise
-            out.update(shortcut_smoothing=s2 is not None)
-        if s2 is None:   # today's coarse points: every 8th node of the stitched path
-            s1 = api.Bspline(ctx, 3, 0, 0, 0, len(path))          # BS_Basic<float,3,0,0,0>: time-indexed resampling
-            s1.set_param(ends[0], ends[1], path, 150.0)
-            n1 = max(16, len(path) // 8)
-            _, _, coarse = s1.sample(150.0 / n1, 150.0 / n1, n1, host=False, device=True)
-            s2 = api.Bspline(ctx, 3, 3, 2, 2, len(coarse))        # cubic with zero end velocity / acceleration
-        z = np.zeros((2, 3), np.float32)
-        s2.set_param(np.vstack([ends[:1], z]), np.vstack([ends[1:], z]), coarse, 6000.0)
-        traj, ok = s2.sample(0.0, 1.0, 6001)                  # 1 kHz over 6 s
-        out.update(stitched_nodes=len(path), coarse_points=len(coarse), trajectory_samples=int(ok.sum()),
-                   trajectory_length=float(np.linalg.norm(np.diff(traj, axis=0), axis=1).sum()),
-                   t_trajectory_s=time.perf_counter() - t2)
+        wsegs = [short[(min(a, b), max(a, b))] for a, b in edges] if args.shortcut else None
+        traj, ok, info = smooth(ctx, grid, segs, wsegs, rev)
+        out.update(info, t_trajectory_s=time.perf_counter() - t2)
+        if args.safe_paths:
+            # what the soft margin buys and costs, against the hop-optimal paths of the same pairs in the same seam order: steps over
+            # the optimum, path nodes inside the outermost band, and (--shortcut) segments of the smoothed curve that cut the metal
+            P = args.points
+            ii, jj = np.triu_indices(P, 1)
+            hop_matrix_all = grid.geodesic_matrix(pts)
+            _, hop_paths = api.geodesic_paths(grid, pts[ii], pts[jj])
+            hop_paths = {(int(i), int(j)): (np.zeros(0, np.int64) if p is None else p) for i, j, p in zip(ii, jj, hop_paths)}
+            d2 = metal.distance_field()
+            r2 = args.safe_paths ** 2
+            within = lambda ps, lim=r2: int(sum((d2[np.asarray(p, np.int64)] <= lim).sum() for p in ps))
+            reach = [ij for ij in sorted(paths) if len(paths[ij])]
+            q = dict(plan.last_safe, nodes_total=int(sum(len(paths[ij]) for ij in reach)),
+                     extra_steps_total=int(sum(len(paths[ij]) - 1 - int(hop_matrix_all[ij]) for ij in reach)),
+                     nodes_within_bands=within(paths[ij] for ij in reach), nodes_within_bands_hop_optimal=within(hop_paths[ij] for ij in reach),
+                     nodes_next_to_metal=within((paths[ij] for ij in reach), 1), nodes_next_to_metal_hop_optimal=within((hop_paths[ij] for ij in reach), 1))
+            if args.shortcut:
+                hsegs = [hop_paths[(min(a, b), max(a, b))] for a, b in edges]
+                hw = api.shortcut_paths(grid, hsegs, args.max_span)[0]
+                htraj, hok, _ = smooth(ctx, grid, hsegs, hw, rev)
+                n_hit = lambda t, k: int(api.Trajectory.from_points(ctx, t[k.astype(bool)]).clearance(metal)[3]["n_hit"])
+                q.update(n_hit=n_hit(traj, ok), n_hit_hop_optimal=n_hit(htraj, hok))
+            out.update(safe_paths=q)
         if args.clearance is not None:
             # the curve the robot follows, against the real obstacles: how close it comes, and whether it cuts through any
             final = api.Trajectory.from_points(ctx, traj[ok.astype(bool)])

@@ -500,6 +500,52 @@ int wa_grid_geodesic_matrix(const wa_grid *g, const int64_t *point_ids, int32_t 
 int wa_grid_geodesic_paths(const wa_grid *g, const int64_t *start_ids, const int64_t *end_ids, int32_t n_pairs,
                            const int64_t *off, int64_t *ids_out, int32_t *hops_out);
 
+/* ---- clearance-weighted exact shortest paths (not in the reference) ----
+ * The graph is the one of the section above: the free voxels of g on the 6-neighbour lattice, neighbours in the fixed order -x, +x, -y,
+ * +y, -z, +z.  Here ENTERING voxel v costs cost[v], a small integer, instead of 1.
+ * WA_COST_MAX = 8.  A cost array is n = nx * ny * nz bytes on the host in raster order, like wa_grid_read_occupancy.  Every free voxel
+ *   must hold a value in 1 .. WA_COST_MAX; the bytes of occupied voxels are ignored.
+ * dist(s, v): the minimum, over lattice paths of free voxels s = p_0, p_1 ... p_h = v, of cost[p_1] + ... + cost[p_h].  The start is not
+ *   paid for, so dist(s, s) = 0.  WA_DIST_NONE where there is no such path or v is occupied.  With every cost 1 this is hops(s, v), bit
+ *   for bit.  It is not symmetric: dist(s, e) - dist(e, s) = cost[e] - cost[s]; cost[s] + dist(s, e) is.
+ * path(s, e), for dist(s, e) >= 0: walking back from e, the predecessor of a node p with dist(s, p) = D > 0 is the first neighbour q in
+ *   the order above that is inside the grid, free and has dist(s, q) = D - cost[p]; the walk ends at s (D = 0).  The path is returned
+ *   start first.  Its number of nodes is an output of its own: it does not follow from the distance.
+ * Clearance costs: cost[v] = 0 on occupied voxels, else 1 + #{k < n_thr : d2[v] <= thr2[k]} with d2 the field of
+ *   wa_grid_distance_field.  0 <= n_thr <= WA_COST_MAX - 1, every 0 <= thr2[k] < WA_D2_NONE, in any order.  Thresholds 1, 4, 9 give
+ *   cost 4 next to an obstacle, then 3, 2, and 1 from a distance of more than 3 voxels on (and everywhere on a grid without obstacles).
+ *
+ * The calls are stateless: the cost array comes in with each call and nothing about it is kept with the grid; an array from
+ * wa_grid_clearance_costs and a hand-made one are treated alike.  WA_ERR_ARG, before any output is written: a NULL pointer (also with a
+ * count of 0), a negative count, an id outside the grid or on an occupied voxel, decreasing offsets, a free voxel whose cost is 0 or
+ * above WA_COST_MAX, a threshold out of range, n_thr above WA_COST_MAX - 1, and a grid for which (largest cost present on a free
+ * voxel) * (n_free - 1) exceeds 2^31 - 1: a distance might not fit int32.  Counts of 0 with valid pointers succeed and write nothing
+ * (the cost array is not looked at then).
+ *
+ * Memory: a call keeps the cost bytes (n) and three bitmaps of them on the device; with W the largest cost present, a source costs W + 2
+ * bitmaps of n / 8 bytes (rows in x padded to 64 voxels), plus 4 n bytes where a field is kept (_fields, _paths), plus its matrix row.
+ * Sources are processed in chunks by the rule of the section above (half of the free memory, at least 1, at most 65 535, WA_ERR_ALLOC
+ * when one source does not fit).  Results do not depend on the chunking and are the same bytes on every call.
+ *
+ * wa_grid_clearance_costs: cost_out[v] (n bytes on the host) by the rule above; builds the distance field if the grid has none yet.
+ * wa_grid_weighted_fields: dist_out[s * n + v] = dist(src_ids[s], v) for every voxel v (n_src * n int32 on the host).
+ * wa_grid_weighted_matrix: dist_out[i * n_pts + j] = dist(point_ids[i], point_ids[j]); 0 on the diagonal, WA_DIST_NONE where the two
+ *   points are not connected.  No field is stored; a point's search ends as soon as its row is full.
+ * wa_grid_weighted_paths: the protocol of wa_grid_geodesic_paths.  Pair p = (start_ids[p], end_ids[p]); off holds n_pairs + 1
+ *   non-decreasing offsets and gives pair p the range ids_out[off[p] .. off[p+1]).  dist_out[p] = dist(start, end) and len_out[p] = the
+ *   nodes of path(start, end) (0 when unreachable) are filled for every pair.  A reachable pair whose range holds at least len_out[p] ids
+ *   gets its path at ids_out[off[p] .. off[p] + len_out[p]); later entries of its range are left untouched.  An unreachable pair writes
+ *   nothing and is no error.  If some reachable pair's range is too short, nothing is written into that pair's range, all other pairs
+ *   are written as usual and the call returns WA_ERR_CAPACITY: size off from len_out and call again.  Pairs that share a start share one
+ *   field, in whatever order they come. */
+#define WA_COST_MAX 8
+#define WA_DIST_NONE (-1)
+int wa_grid_clearance_costs(const wa_grid *g, const int32_t *thr2, int32_t n_thr, uint8_t *cost_out);
+int wa_grid_weighted_fields(const wa_grid *g, const uint8_t *cost, const int64_t *src_ids, int32_t n_src, int32_t *dist_out);
+int wa_grid_weighted_matrix(const wa_grid *g, const uint8_t *cost, const int64_t *point_ids, int32_t n_pts, int32_t *dist_out);
+int wa_grid_weighted_paths(const wa_grid *g, const uint8_t *cost, const int64_t *start_ids, const int64_t *end_ids, int32_t n_pairs,
+                           const int64_t *off, int64_t *ids_out, int32_t *dist_out, int32_t *len_out);
+
 #ifdef __cplusplus
 }
 #endif

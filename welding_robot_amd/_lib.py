@@ -29,6 +29,8 @@ class GtspParams(C.Structure):
 
 WA_D2_NONE = 0x7fffffff
 WA_HOPS_NONE = -1
+WA_DIST_NONE = -1
+WA_COST_MAX = 8
 
 
 class ClearanceSummary(C.Structure):
@@ -136,6 +138,10 @@ SYMBOLS = {
     "wa_grid_geodesic_fields": (C.c_int, [_V, _P, _I, _P]),
     "wa_grid_geodesic_matrix": (C.c_int, [_V, _P, _I, _P]),
     "wa_grid_geodesic_paths": (C.c_int, [_V, _P, _P, _I, _P, _P, _P]),
+    "wa_grid_clearance_costs": (C.c_int, [_V, _P, _I, _P]),
+    "wa_grid_weighted_fields": (C.c_int, [_V, _P, _P, _I, _P]),
+    "wa_grid_weighted_matrix": (C.c_int, [_V, _P, _P, _I, _P]),
+    "wa_grid_weighted_paths": (C.c_int, [_V, _P, _P, _P, _I, _P, _P, _P, _P]),
 }
 
 _libs = {}

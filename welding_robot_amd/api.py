@@ -7,7 +7,7 @@ import weakref
 import numpy as np
 
 from . import _lib as L
-from ._lib import AcsParams, GtspParams, RNG_DEV, RNG_REF, WA_D2_NONE, WA_HOPS_NONE, WeldacsError  # noqa: F401
+from ._lib import AcsParams, GtspParams, RNG_DEV, RNG_REF, WA_COST_MAX, WA_D2_NONE, WA_DIST_NONE, WA_HOPS_NONE, WeldacsError  # noqa: F401
 
 
 def _ptr(a):
@@ -210,6 +210,39 @@ class Grid:
                                                             _ptr(out if out.size else np.zeros(1, np.int32))))
         return out
 
+    def clearance_costs(self, thr2):
+        """wa_grid_clearance_costs: uint8 [n], 0 on occupied voxels, else 1 + the number of thresholds (squared distances in voxels, at
+        most WA_COST_MAX - 1 of them) that the voxel's entry in distance_field() does not exceed"""
+        thr2 = np.ascontiguousarray(thr2, np.int32).reshape(-1)
+        out = np.empty(self.n, np.uint8)
+        self.ctx.check(self.ctx.lib.wa_grid_clearance_costs(self.h, _ptr(thr2 if len(thr2) else np.zeros(1, np.int32)), len(thr2), _ptr(out)))
+        return out
+
+    def _cost(self, cost):
+        cost = np.ascontiguousarray(cost, np.uint8).reshape(-1)
+        assert cost.size == self.n, "a cost array holds one byte per voxel"
+        return cost
+
+    def weighted_fields(self, cost, ids):
+        """wa_grid_weighted_fields: int32 [len(ids), n], the exact least sum of entry costs (cost: uint8 [n], 1 .. WA_COST_MAX on free
+        voxels) from each source to every voxel; WA_DIST_NONE (-1) where there is no path"""
+        cost = self._cost(cost)
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        out = np.empty((len(ids), self.n), np.int32)
+        self.ctx.check(self.ctx.lib.wa_grid_weighted_fields(self.h, _ptr(cost), _ptr(ids if len(ids) else np.zeros(1, np.int64)), len(ids),
+                                                            _ptr(out if out.size else np.zeros(1, np.int32))))
+        return out
+
+    def weighted_matrix(self, cost, ids):
+        """wa_grid_weighted_matrix: int32 [P, P], [i, j] = dist(point i, point j) (not symmetric: [i, j] - [j, i] = cost[j] - cost[i]);
+        WA_DIST_NONE (-1) where two points are not connected"""
+        cost = self._cost(cost)
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        out = np.empty((len(ids), len(ids)), np.int32)
+        self.ctx.check(self.ctx.lib.wa_grid_weighted_matrix(self.h, _ptr(cost), _ptr(ids if len(ids) else np.zeros(1, np.int64)), len(ids),
+                                                            _ptr(out if out.size else np.zeros(1, np.int32))))
+        return out
+
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.wa_grid_destroy(self.h)
@@ -254,6 +287,32 @@ def geodesic_paths(grid, starts, ends):
     if rc == 7:
         ctx.check(ctx.lib.wa_grid_geodesic_paths(grid.h, _ptr(starts), _ptr(ends), n, _ptr(off), _ptr(ids), _ptr(hops)))
     return hops, [ids[off[k]:off[k + 1]].copy() if hops[k] >= 0 else None for k in range(n)]
+
+
+def weighted_paths(grid, cost, starts, ends):
+    """wa_grid_weighted_paths of a batch of pairs: (int32 dist, int32 node counts, [node-id array per pair, start first; None where dist
+    is WA_DIST_NONE]).  Two calls like geodesic_paths: the first, with empty ranges, returns distances and node counts
+    (WA_ERR_CAPACITY is its expected status when any pair is reachable), the second writes the paths into ranges of len ids."""
+    cost = grid._cost(cost)
+    starts = np.ascontiguousarray(starts, np.int64).reshape(-1)
+    ends = np.ascontiguousarray(ends, np.int64).reshape(-1)
+    assert len(starts) == len(ends)
+    n = len(starts)
+    ctx = grid.ctx
+    dist = np.empty(max(n, 1), np.int32)
+    lens = np.zeros(max(n, 1), np.int32)
+    off = np.zeros(n + 1, np.int64)
+    pad = np.zeros(1, np.int64)
+    rc = ctx.lib.wa_grid_weighted_paths(grid.h, _ptr(cost), _ptr(starts if n else pad), _ptr(ends if n else pad), n, _ptr(off), _ptr(pad),
+                                        _ptr(dist), _ptr(lens))
+    if rc not in (0, 7):
+        ctx.check(rc)
+    dist, lens = dist[:n], lens[:n]
+    off[1:] = np.cumsum(lens.astype(np.int64))
+    ids = np.empty(max(int(off[-1]), 1), np.int64)
+    if rc == 7:
+        ctx.check(ctx.lib.wa_grid_weighted_paths(grid.h, _ptr(cost), _ptr(starts), _ptr(ends), n, _ptr(off), _ptr(ids), _ptr(dist), _ptr(lens)))
+    return dist, lens, [ids[off[k]:off[k + 1]].copy() if dist[k] >= 0 else None for k in range(n)]
 
 
 def default_params(**kw):

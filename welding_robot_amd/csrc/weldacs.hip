@@ -29,6 +29,7 @@
 #include "clearance_kernels.hpp"
 #include "shortcut_kernels.hpp"
 #include "geodesic_kernels.hpp"
+#include "weighted_kernels.hpp"
 #include "stl_text.hpp"
 
 // ------------------------------------------------------------------ handles
@@ -769,5 +770,6 @@ void *wa_ctx_stream(wa_ctx *c) { return c ? (void *)c->stream : nullptr; }
 #include "host_clearance.inc"
 #include "host_shortcut.inc"
 #include "host_geodesic.inc"
+#include "host_weighted.inc"
 
 }  // extern "C"
