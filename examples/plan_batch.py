@@ -138,13 +138,32 @@ def plan_safe(grid, point_ids, radius, rank=0, world=1, shortcut=0):
     return cost, paths, len(mine)
 
 
-def smooth(ctx, grid, segs, wsegs, rev):
+def smooth(ctx, grid, segs, wsegs, rev, fit=None):
     """main.cpp:283-352 on the device: the tour's segments stitched, then the two smoothing passes; wsegs (--shortcut): the shortened
-    segments, whose waypoints are then the coarse points of the cubic fit.  Returns (samples, ok flags, what goes into the JSON)."""
+    segments, whose waypoints are then the coarse points of the cubic fit.  fit = (metal grid, max_level, dump path or None) (--fit):
+    the curve is wa_grid_fit_trajectory's instead, control points ON the waypoints' polyline, refined until its samples clear the metal.
+    Returns (samples, ok flags, what goes into the JSON)."""
     info = {}
     path = api.Trajectory.stitch(grid, segs, rev)
     ends = path.points()[[0, -1]]
     s2 = None
+    if wsegs is not None and fit is not None:
+        metal, max_level, dump = fit
+        wpath = api.Trajectory.stitch(grid, wsegs, rev)
+        _, samples, _, summary = wpath.fit(metal, degree=3, max_level=max_level, n_samples=6001)
+        traj = samples.points()
+        if dump:
+            np.save(dump, wpath.points())
+        # today's fit of the same waypoints, for the comparison
+        plain, pok, _ = smooth(ctx, grid, segs, wsegs, rev)
+        before = api.Trajectory.from_points(ctx, plain[pok.astype(bool)]).clearance(metal)[3]["n_hit"]
+        smooth.plain = (plain, pok)
+        lens = api.shortcut_paths(grid, wsegs, 1)[1]
+        lattice = api.shortcut_paths(grid, segs, 1)[1]
+        info.update(shortened_length_total=float(lens.sum()), lattice_length_total=float(lattice.sum()))
+        info.update(fit=dict(summary, max_level=max_level, n_hit_plain_fit=int(before)), waypoints=len(wpath), stitched_nodes=len(path),
+                    trajectory_samples=len(traj), trajectory_length=float(np.linalg.norm(np.diff(traj, axis=0), axis=1).sum()))
+        return traj, np.ones(len(traj), np.uint8), info
     if wsegs is not None:
         # the shortened segments stitched the same way: their waypoints are the coarse points of the cubic fit
         wpath = api.Trajectory.stitch(grid, wsegs, rev)
@@ -210,7 +229,13 @@ def main():
     ap.add_argument("--safe-paths", type=int, default=0, choices=range(1, 8), metavar="R",
                     help="take the pair paths from the clearance-weighted exact planner (wa_grid_weighted_paths) instead of the colony: "
                          "entering a voxel costs 1 + the number of bands 1^2 .. R^2 (voxels squared) its distance to the metal lies within")
+    ap.add_argument("--fit", type=int, nargs="?", const=6, default=None, choices=range(0, 9), metavar="MAX_LEVEL",
+                    help="needs --shortcut: the trajectory is wa_grid_fit_trajectory's (control points on the waypoints' polyline, refined "
+                         "leg by leg up to MAX_LEVEL until the sampled curve clears the metal) instead of the cubic through the waypoints")
+    ap.add_argument("--fit-dump", default=None, help="--fit: write the fitted polyline (n x 3 float32) to this .npy file")
     args = ap.parse_args()
+    if args.fit is not None and not args.shortcut:
+        ap.error("--fit needs the waypoints of --shortcut")
     rank, local_rank, world = wd.env_rank()
     ctx = api.Context(local_rank)
     comm = None
@@ -305,7 +330,7 @@ def main():
         segs = [paths[(min(a, b), max(a, b))] for a, b in edges]
         rev = [1 if a > b else 0 for a, b in edges]          # stored i<j; walk them in tour direction
         wsegs = [short[(min(a, b), max(a, b))] for a, b in edges] if args.shortcut else None
-        traj, ok, info = smooth(ctx, grid, segs, wsegs, rev)
+        traj, ok, info = smooth(ctx, grid, segs, wsegs, rev, fit=(metal, args.fit, args.fit_dump) if args.fit is not None else None)
         out.update(info, t_trajectory_s=time.perf_counter() - t2)
         if args.safe_paths:
             # what the soft margin buys and costs, against the hop-optimal paths of the same pairs in the same seam order: steps over
@@ -328,7 +353,9 @@ def main():
                 hw = api.shortcut_paths(grid, hsegs, args.max_span)[0]
                 htraj, hok, _ = smooth(ctx, grid, hsegs, hw, rev)
                 n_hit = lambda t, k: int(api.Trajectory.from_points(ctx, t[k.astype(bool)]).clearance(metal)[3]["n_hit"])
-                q.update(n_hit=n_hit(traj, ok), n_hit_hop_optimal=n_hit(htraj, hok))
+                # (n_hit stays what it is without --fit, the cubic through the waypoints; the fit's own figure is under "fit")
+                ptraj, pok = smooth.plain if args.fit is not None else (traj, ok)
+                q.update(n_hit=n_hit(ptraj, pok), n_hit_hop_optimal=n_hit(htraj, hok))
             out.update(safe_paths=q)
         if args.clearance is not None:
             # the curve the robot follows, against the real obstacles: how close it comes, and whether it cuts through any

@@ -546,6 +546,57 @@ int wa_grid_weighted_matrix(const wa_grid *g, const uint8_t *cost, const int64_t
 int wa_grid_weighted_paths(const wa_grid *g, const uint8_t *cost, const int64_t *start_ids, const int64_t *end_ids, int32_t n_pairs,
                            const int64_t *off, int64_t *ids_out, int32_t *dist_out, int32_t *len_out);
 
+/* ---- trajectory fit that refines the spline until it clears the grid (not in the reference: main.cpp:337 fits through the path
+ *      points as they are) ----
+ * A B-spline of degree D lies in the convex hull of D + 1 consecutive control points.  Control points placed ON a collision-free
+ * polyline, closely enough where the curve hits, pull the curve onto that polyline.  The call does that on the device: control
+ * polygon -> fit -> sample -> check -> blame -> refine, until no segment of the sampled curve hits or nothing can be refined.
+ *
+ * g is the grid the curve is CHECKED against (the metal, not an inflated planning grid).  poly holds n >= 2 points; leg k joins
+ * points k and k + 1, k = 0 .. n - 2; zero-length legs are legal.  Every leg k has a level s_k, 0 at the start.  One round:
+ * 1. Pieces.  len_k = the length of leg k as wa_grid_path_shortcut defines one: float64 on the fp32 coordinates, dx = (double)b_x -
+ *    (double)a_x and so on, sqrt((dx*dx + dy*dy) + dz*dz), every operation rounded on its own.  In float64, each operation rounded on its
+ *    own: q = (len_k * (double)(1 << s_k)) / (double)spacing; m_k = (int64)ceil(q) if ceil(q) >= 1, else 1.
+ * 2. Control polygon.  Leg k (from a to b) contributes j = 0 .. m_k - 1: per axis a + (b - a) * ((float)j / (float)m_k), in fp32, each of
+ *    the four operations rounded on its own (no contraction); behind the last leg comes the polyline's last point.  Point 0 is the
+ *    spline's initial position, the last point its final position, all points between are its middle points, in order.
+ *    owner[c] = the leg control point c came from; the constrained control points at either end belong to the first / the last leg.
+ * 3. Fit.  BS_Basic<float, 3, D, D-1, D-1> (D = degree, 2 or 3) on those points, end derivatives of every constrained level zero,
+ *    fin_time = (float)(number of knot spans) = (float)(middle points + D): the knot step is exactly 1.0f and knot i is the integer
+ *    min(max(i - D, 0), fin_time).  A fit of more than 2^24 control points (in any round) is refused with WA_ERR_ARG.
+ * 4. Sample and check.  u_i = (float)i * dt, dt = fin_time / (float)(n_samples - 1) (fp32), i = 0 .. n_samples - 1, evaluated as
+ *    wa_bspline_sample(b, 0, dt, n_samples) does; then wa_traj_clearance of those samples against g: the same voxel lookup, the same
+ *    segment test.  No hit: the loop ends.
+ * 5. Blame.  For a hit segment i, take the knot span the evaluation used for u_i and for u_(i+1) (_findSpan, BSplineBasic.h:358-385,
+ *    after the clamp into the knot range); the control points with a non-zero basis there are span - D .. span; every leg that owns
+ *    one of them is marked.
+ * 6. Refine.  n_legs_at_cap = the marked legs with s_k = max_level.  Every marked leg with s_k < max_level gets s_k + 1.  If no level
+ *    changed, or this was round 32, the loop ends (in round 32 no level is raised); otherwise the next round starts at 1.
+ * max_level is in 0 .. 8 (0: one plain fit on the given spacing).  Every round but the last raises at least one leg, so the loop ends.
+ *
+ * Results: *spline_out = the last round's spline, an ordinary wa_bspline owned by the caller (eval, derivatives, wa_bspline_read);
+ * *samples_out (may be NULL) = its n_samples samples as a device-resident polyline owned by the caller; leg_level_out (n - 1 int32, may
+ * be NULL) = the levels that spline was built with; *sum as below.  The call does NOT promise final.n_hit == 0: the segment test is
+ * conservative (two consecutive samples in diagonal voxels test the whole product set), so a curve arbitrarily close to a visible leg
+ * can still be reported, and inside the keep bubbles of wa_grid_inflate a path touches the metal by design.  rounds == 32 or
+ * n_legs_at_cap > 0 with final.n_hit > 0 tell the caller so.  Where control points are dense the curve is slow (time runs one knot
+ * span per unit): the fit shapes the curve, it does not re-time it.
+ *
+ * WA_ERR_ARG, before anything is written: NULL g / poly / sum / spline_out, poly and g from different contexts, n < 2, degree outside
+ * {2, 3}, spacing not finite or <= 0, max_level outside 0 .. 8, n_samples < 2 or > 2^33, a coordinate of poly that is not finite.
+ * Same bytes on every call; everything runs on the context's stream. */
+typedef struct {
+    int32_t rounds;         /* fits made (>= 1) */
+    int32_t max_level_used; /* the highest level of any leg */
+    int64_t n_legs;         /* n - 1 */
+    int64_t n_legs_at_cap;  /* legs at max_level that were still blamed in the last round */
+    int64_t n_cps;          /* control points of the final spline */
+    int64_t n_hit_first;    /* hit segments of round 1: the unrefined fit on the same control spacing */
+    wa_clearance_summary final; /* of the final samples against g: n_hit == 0 is the success case */
+} wa_fit_summary;
+int wa_grid_fit_trajectory(const wa_grid *g, const wa_traj *poly, int32_t degree, float spacing, int32_t max_level, int64_t n_samples,
+                           int32_t *leg_level_out, wa_bspline **spline_out, wa_traj **samples_out, wa_fit_summary *sum);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,11 @@ class ClearanceSummary(C.Structure):
                 ("n_outside", C.c_int64)]
 
 
+class FitSummary(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("max_level_used", C.c_int32), ("n_legs", C.c_int64), ("n_legs_at_cap", C.c_int64),
+                ("n_cps", C.c_int64), ("n_hit_first", C.c_int64), ("final", ClearanceSummary)]
+
+
 # every symbol include/weldacs.h declares: name -> (restype, argtypes)
 _V, _I, _I64, _F, _P = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_void_p
 SYMBOLS = {
@@ -142,6 +147,7 @@ SYMBOLS = {
     "wa_grid_weighted_fields": (C.c_int, [_V, _P, _P, _I, _P]),
     "wa_grid_weighted_matrix": (C.c_int, [_V, _P, _P, _I, _P]),
     "wa_grid_weighted_paths": (C.c_int, [_V, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "wa_grid_fit_trajectory": (C.c_int, [_V, _V, _I, _F, _I, _I64, _P, C.POINTER(_V), C.POINTER(_V), C.POINTER(FitSummary)]),
 }
 
 _libs = {}

@@ -664,6 +664,19 @@ class Trajectory:
         summary = {k: int(getattr(s, k)) for k, _ in L.ClearanceSummary._fields_}
         return ids, d2, hit, summary
 
+    def fit(self, grid, degree=3, spacing=None, max_level=6, n_samples=6001):
+        """wa_grid_fit_trajectory with this polyline: control points on the polyline, refined leg by leg until the sampled curve clears
+        `grid` (the metal).  spacing=None: one voxel (grid.precision).  Returns (Bspline, samples Trajectory, levels int32[n-1], summary dict;
+        summary["final"] is the clearance summary of the samples)."""
+        spacing = grid.precision if spacing is None else spacing
+        levels = np.empty(max(len(self) - 1, 0), np.int32)
+        bh, th, s = C.c_void_p(), C.c_void_p(), L.FitSummary()
+        self.ctx.check(self.ctx.lib.wa_grid_fit_trajectory(grid.h, self.h, degree, C.c_float(spacing), max_level, n_samples, _ptr(levels),
+                                                           C.byref(bh), C.byref(th), C.byref(s)))
+        summary = {k: int(getattr(s, k)) for k, _ in L.FitSummary._fields_ if k != "final"}
+        summary["final"] = {k: int(getattr(s.final, k)) for k, _ in L.ClearanceSummary._fields_}
+        return Bspline.adopt(self.ctx, bh, 3, degree, summary["n_cps"] - 2 * degree), Trajectory(self.ctx, th), levels, summary
+
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.wa_traj_destroy(self.h)
@@ -684,6 +697,14 @@ class Bspline:
         ctx._children.add(self)
         if uninit_bits:
             ctx.check(ctx.lib.wa_bspline_set_uninit(self.h, uninit_bits))
+
+    @classmethod
+    def adopt(cls, ctx, handle, dim, degree, n_middle):
+        """a wa_bspline the library created (wa_grid_fit_trajectory); owned and destroyed by the wrapper like any other"""
+        b = cls.__new__(cls)
+        b.ctx, b.dim, b.degree, b.n_middle, b.h = ctx, dim, degree, n_middle, handle
+        ctx._children.add(b)
+        return b
 
     def set_param(self, init, fin, middle, fin_time):
         """SetParam; `middle` is an (n_middle, stride >= dim) array or a Trajectory."""

@@ -99,6 +99,28 @@ int wa_grid_inflate(const wa_grid *g, float radius, const int64_t *keep_ids, int
 }
 
 // ------------------------------------------------------------------ trajectory check
+// per axis: the table's range and whether it is non-decreasing (binary search) -- the hi-side seam of the wall is where a table
+// built by wa_axis_coords can hold one value twice, which is still non-decreasing
+static int clr_axes(const wa_grid *g, WaClrAxes *A)
+{
+    std::vector<float> ax[3] = {std::vector<float>((size_t)g->d.nx), std::vector<float>((size_t)g->d.ny), std::vector<float>((size_t)g->d.nz)};
+    int rc = wa_grid_read_coords(g, ax[0].data(), ax[1].data(), ax[2].data());
+    if (rc) return rc;
+    for (int c = 0; c < 3; c++) {
+        float lo = ax[c][0], hi = ax[c][0];
+        int mono = 1;
+        for (size_t j = 1; j < ax[c].size(); j++) {
+            const float v = ax[c][j];
+            lo = v < lo ? v : lo;
+            hi = v > hi ? v : hi;
+            if (!(v >= ax[c][j - 1])) mono = 0;
+        }
+        if (lo != lo || hi != hi) mono = 0;
+        A->lo[c] = lo; A->hi[c] = hi; A->mono[c] = mono;
+    }
+    return WA_OK;
+}
+
 int wa_traj_clearance(const wa_grid *g, const wa_traj *t, int64_t *ids_out, int32_t *d2_out, uint8_t *hit_out, wa_clearance_summary *sum)
 {
     WaDevGuard dev_guard_(g ? g->ctx : nullptr);
@@ -113,26 +135,9 @@ int wa_traj_clearance(const wa_grid *g, const wa_traj *t, int64_t *ids_out, int3
     if (rc) return rc;
     sum->min_d2 = WA_D2_NONE; sum->argmin = -1; sum->first_hit = -1; sum->n_hit = 0; sum->n_outside = 0;
     if (n == 0) return WA_OK;
-    // per axis: the table's range and whether it is non-decreasing (binary search) -- the hi-side seam of the wall is where a table
-    // built by wa_axis_coords can hold one value twice, which is still non-decreasing
     WaClrAxes A;
-    {
-        std::vector<float> ax[3] = {std::vector<float>((size_t)g->d.nx), std::vector<float>((size_t)g->d.ny), std::vector<float>((size_t)g->d.nz)};
-        rc = wa_grid_read_coords(g, ax[0].data(), ax[1].data(), ax[2].data());
-        if (rc) return rc;
-        for (int c = 0; c < 3; c++) {
-            float lo = ax[c][0], hi = ax[c][0];
-            int mono = 1;
-            for (size_t j = 1; j < ax[c].size(); j++) {
-                const float v = ax[c][j];
-                lo = v < lo ? v : lo;
-                hi = v > hi ? v : hi;
-                if (!(v >= ax[c][j - 1])) mono = 0;
-            }
-            if (lo != lo || hi != hi) mono = 0;
-            A.lo[c] = lo; A.hi[c] = hi; A.mono[c] = mono;
-        }
-    }
+    rc = clr_axes(g, &A);
+    if (rc) return rc;
     long long *d_ids = nullptr;
     int32_t *d_d2 = nullptr;
     uint8_t *d_hit = nullptr;

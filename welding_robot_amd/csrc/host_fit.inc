@@ -1,0 +1,159 @@
+// host_fit.inc -- C ABI: the trajectory fit that refines its control polygon until the sampled curve clears the grid
+// (included by weldacs.hip inside extern "C").  Everything between the arguments and the results stays on the device, on the
+// context's stream; per round the host reads one WaFitRec (the next fit's size, the hit count, whether a level changed).
+struct FitBuffers {
+    int32_t *level = nullptr, *owner = nullptr, *d2 = nullptr;
+    uint8_t *mark = nullptr, *hit = nullptr;
+    long long *off = nullptr, *bsum = nullptr, *ids = nullptr;
+    WaFitRec *rec = nullptr;
+    wa_traj *samples = nullptr;
+    wa_bspline *b = nullptr;
+    long long cap_cps = 0;
+    ~FitBuffers()
+    {
+        hipFree(level); hipFree(owner); hipFree(d2); hipFree(mark); hipFree(hit); hipFree(off); hipFree(bsum); hipFree(ids); hipFree(rec);
+        wa_traj_destroy(samples);
+        wa_bspline_destroy(b);
+    }
+};
+
+// pieces at the current levels, scanned: off[0 .. n_legs], rec->total
+static hipError_t fit_pieces(wa_ctx *ctx, const wa_traj *poly, FitBuffers &B, double spacing)
+{
+    const long long n_legs = poly->n - 1;
+    const unsigned blocks = (unsigned)((n_legs + 255) / 256);
+    k_fit_pieces<<<blocks, 256, 0, ctx->stream>>>(poly->xyz, n_legs, B.level, spacing, B.off, B.bsum, B.rec);
+    k_fit_scan_sums<<<1, 256, 0, ctx->stream>>>(B.bsum, (long long)blocks, B.rec);
+    k_fit_scan_add<<<(unsigned)((n_legs + 1 + 255) / 256), 256, 0, ctx->stream>>>(B.off, n_legs, B.bsum, B.rec);
+    return hipGetLastError();
+}
+
+// room for a spline of n_cps control points in B.b (kept from round to round, grown by half when a round needs more)
+static hipError_t fit_spline_room(wa_ctx *ctx, FitBuffers &B, int32_t degree, long long n_cps)
+{
+    if (!B.b) {
+        B.b = new wa_bspline();
+        B.b->ctx = ctx;
+        B.b->S.knots = nullptr; B.b->S.cps = nullptr; B.b->S.uninit = 0.0f;
+        B.b->d_ends = nullptr;
+        B.b->set = false;
+    }
+    WaSpline &S = B.b->S;
+    S.dim = 3; S.degree = degree; S.ci = degree - 1; S.cf = degree - 1;
+    S.n_cps = n_cps;
+    S.n_middle = n_cps - 2 * degree;              // BSplineBasic.h:40
+    S.n_knots = n_cps + degree + 1;               // :38-39
+    if (n_cps <= B.cap_cps) return hipSuccess;
+    hipFree(S.knots); hipFree(S.cps); hipFree(B.owner);
+    S.knots = nullptr; S.cps = nullptr; B.owner = nullptr;
+    B.cap_cps = 0;
+    const long long cap = std::min(n_cps + n_cps / 2, (long long)WA_FIT_MAX_CPS);
+    hipError_t e = dalloc(&S.knots, (size_t)(cap + degree + 1));
+    e = e ? e : dalloc(&S.cps, (size_t)cap * 3);
+    e = e ? e : dalloc(&B.owner, (size_t)cap);
+    if (e == hipSuccess && !B.b->d_ends) e = dalloc(&B.b->d_ends, (size_t)(2 * degree) * 3);
+    if (e == hipSuccess) B.cap_cps = cap;
+    return e;
+}
+
+int wa_grid_fit_trajectory(const wa_grid *g, const wa_traj *poly, int32_t degree, float spacing, int32_t max_level, int64_t n_samples,
+                           int32_t *leg_level_out, wa_bspline **spline_out, wa_traj **samples_out, wa_fit_summary *sum)
+{
+    WaDevGuard dev_guard_(g ? g->ctx : nullptr);
+    if (!dev_guard_.ok) return WA_ERR_DEVICE;   // the context's device could not be made current
+    if (!g) return WA_ERR_ARG;
+    wa_ctx *ctx = g->ctx;
+    if (!poly || !sum || !spline_out) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: NULL polyline, summary or spline output");
+    if (poly->ctx != ctx) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: polyline and grid belong to different contexts");
+    if (poly->n < 2) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: a polyline needs at least 2 points");
+    if (degree != 2 && degree != 3) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: degree must be 2 or 3");
+    if (!(spacing > 0.0f) || !isfinite(spacing)) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: spacing must be finite and > 0");
+    if (max_level < 0 || max_level > WA_FIT_MAX_LEVEL) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: max_level must be 0..8");
+    if (n_samples < 2 || n_samples > ((int64_t)1 << 33)) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: n_samples must be 2..2^33");
+    const long long n_legs = poly->n - 1;
+    if (n_legs > WA_FIT_MAX_CPS) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: more than 2^24 control points");
+    int rc = grid_build_d2(g);
+    if (rc) return rc;
+    WaClrAxes A;
+    rc = clr_axes(g, &A);
+    if (rc) return rc;
+
+    FitBuffers B;
+    const long long n_seg = n_samples - 1;
+    hipError_t e = dalloc(&B.level, (size_t)n_legs);
+    e = e ? e : dalloc(&B.mark, (size_t)n_legs);
+    e = e ? e : dalloc(&B.off, (size_t)n_legs + 1);
+    e = e ? e : dalloc(&B.bsum, (size_t)((n_legs + 255) / 256));
+    e = e ? e : dalloc(&B.rec, 1);
+    e = e ? e : dalloc(&B.ids, (size_t)n_samples);
+    e = e ? e : dalloc(&B.d2, (size_t)n_samples);
+    e = e ? e : dalloc(&B.hit, (size_t)n_seg);
+    if (e != hipSuccess) return fail(ctx, WA_ERR_ALLOC, "wa_grid_fit_trajectory: device buffers");
+    rc = traj_alloc(ctx, n_samples, &B.samples);
+    if (rc) return rc;
+    e = hipMemsetAsync(B.level, 0, sizeof(int32_t) * n_legs, ctx->stream);
+    e = e ? e : hipMemsetAsync(B.mark, 0, (size_t)n_legs, ctx->stream);
+    e = e ? e : hipMemsetAsync(B.rec, 0, sizeof(WaFitRec), ctx->stream);
+    e = e ? e : fit_pieces(ctx, poly, B, (double)spacing);
+    WaFitRec rec;
+    e = e ? e : hipMemcpyAsync(&rec, B.rec, sizeof rec, hipMemcpyDeviceToHost, ctx->stream);
+    e = e ? e : hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_grid_fit_trajectory: %s", hipGetErrorString(e));
+    if (rec.bad) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: a coordinate of the polyline is not finite");
+
+    wa_fit_summary s;
+    memset(&s, 0, sizeof s);
+    s.n_legs = n_legs;
+    for (int32_t round = 0;; round++) {
+        // the control polygon has rec.total + 1 points: two end positions and rec.total - 1 middle points
+        const long long n_cps = rec.total - 1 + 2 * degree;
+        if (rec.total > WA_FIT_MAX_CPS || n_cps > WA_FIT_MAX_CPS) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: more than 2^24 control points");
+        e = fit_spline_room(ctx, B, degree, n_cps);
+        if (e != hipSuccess) return fail(ctx, WA_ERR_ALLOC, "wa_grid_fit_trajectory: spline buffers");
+        const WaSpline &S = B.b->S;
+        const float fin_time = (float)(S.n_knots - 2 * degree - 1);   // the number of knot spans: the chain's step is exactly 1.0f
+        const float dt = fin_time / (float)(n_samples - 1);
+        const int32_t last = round == WA_FIT_MAX_ROUNDS - 1;
+        k_fit_emit<<<(unsigned)((rec.total + 1 + 255) / 256), 256, 0, ctx->stream>>>(poly->xyz, n_legs, B.off, S, B.owner);
+        k_fit_knots<<<(unsigned)((S.n_knots + 255) / 256), 256, 0, ctx->stream>>>(S, fin_time);
+        k_fit_ends<<<1, 64, 0, ctx->stream>>>(poly->xyz, n_legs, S, B.b->d_ends, fin_time, B.owner, B.rec);
+        e = hipGetLastError();
+        e = e ? e : bspline_launch(B.b, nullptr, 0.0f, dt, n_samples, 0, B.samples->xyz, nullptr);
+        if (e == hipSuccess) {
+            k_clr_samples<<<(unsigned)((n_samples + 255) / 256), 256, 0, ctx->stream>>>(B.samples->xyz, n_samples, g->d, g->cx, g->cy, g->cz, A, g->d2,
+                                                                                       B.ids, B.d2, B.rec->acc);
+            k_clr_segments<<<(unsigned)((n_seg + 255) / 256), 256, 0, ctx->stream>>>(B.ids, n_samples, g->d, g->occ, B.hit, B.rec->acc);
+            if (degree == 2) k_fit_blame<2><<<(unsigned)((n_seg + 255) / 256), 256, 0, ctx->stream>>>(S, B.hit, n_seg, dt, B.owner, B.mark);
+            else k_fit_blame<3><<<(unsigned)((n_seg + 255) / 256), 256, 0, ctx->stream>>>(S, B.hit, n_seg, dt, B.owner, B.mark);
+            k_fit_bump<<<(unsigned)((n_legs + 255) / 256), 256, 0, ctx->stream>>>(B.level, B.mark, n_legs, max_level, last ? 0 : 1, B.rec);
+            e = hipGetLastError();
+        }
+        e = e ? e : fit_pieces(ctx, poly, B, (double)spacing);   // (the next round's, should there be one)
+        e = e ? e : hipMemcpyAsync(&rec, B.rec, sizeof rec, hipMemcpyDeviceToHost, ctx->stream);
+        e = e ? e : hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_grid_fit_trajectory: %s", hipGetErrorString(e));
+        const int64_t n_hit = (int64_t)rec.acc[2];
+        if (round == 0) s.n_hit_first = n_hit;
+        s.rounds = round + 1;
+        if (n_hit == 0 || rec.changed == 0 || last) break;
+    }
+    s.n_legs_at_cap = rec.at_cap;
+    s.n_cps = B.b->S.n_cps;
+    s.final.min_d2 = (int32_t)(rec.acc[0] >> 33);
+    s.final.argmin = (int64_t)(rec.acc[0] & ((1ull << 33) - 1));
+    s.final.first_hit = rec.acc[1] == ~0ull ? -1 : (int64_t)rec.acc[1];
+    s.final.n_hit = (int64_t)rec.acc[2];
+    s.final.n_outside = (int64_t)rec.acc[3];
+    std::vector<int32_t> lv((size_t)n_legs);
+    e = hipMemcpy(lv.data(), B.level, sizeof(int32_t) * n_legs, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_grid_fit_trajectory: %s", hipGetErrorString(e));
+    for (int32_t v : lv) s.max_level_used = std::max(s.max_level_used, v);
+    if (leg_level_out) memcpy(leg_level_out, lv.data(), sizeof(int32_t) * n_legs);
+    B.b->set = true;
+    B.b->h_valid = false;
+    *spline_out = B.b;
+    B.b = nullptr;
+    if (samples_out) { *samples_out = B.samples; B.samples = nullptr; }
+    *sum = s;
+    return WA_OK;
+}

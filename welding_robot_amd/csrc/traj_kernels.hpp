@@ -146,38 +146,12 @@ __host__ __device__ inline void wa_bs_basis_ders(const float *K, int D, float un
     }
 }
 
-// SetParam (:72-78) = _CalcKnot (:150-171) + _CalcConstrainedCPoints (:387-447), one wavefront.  The knot chain
-// K[i] = K[i-1] + step is a sequential fp32 recurrence (its rounding is part of the result: it drifts from i*step).
-// ends = init rows then fin rows, (level+1) x dim each.
-__global__ void __launch_bounds__(64) k_bspline_setup(WaSpline S, const float *__restrict__ ends, float fin_time)
+// _CalcConstrainedCPoints (:387-447) on finished knots, one lane: the end positions and the control points that the end
+// derivatives fix.  init / fin: (level+1) x dim rows.  Shared by k_bspline_setup and the trajectory fit (fit_kernels.hpp).
+__device__ inline void wa_bs_constrained_cps(const WaSpline &S, const float *__restrict__ init, const float *__restrict__ fin, float fin_time)
 {
     const int D = S.degree, dim = S.dim;
     float *K = S.knots, *C = S.cps;
-    const float *init = ends, *fin = ends + (size_t)(S.ci + 1) * dim;
-    {
-        // every lane runs the same recurrence; lane l keeps the value of step 64*c + l, so the chain costs
-        // three VALU operations per knot and the stores are one coalesced 256-B row per 64 knots
-        const int lane = threadIdx.x;
-        const long long nmid = S.n_knots - 2 * D - 2;
-        const float step = fin_time / (float)(nmid + 1);
-        float k = 0.0f;
-        for (long long base = 0; base < nmid; base += 64) {
-            float mine = 0.0f;
-#pragma unroll
-            for (int q = 0; q < 64; ++q) {
-                k = k + step;
-                mine = (lane == q) ? k : mine;
-            }
-            if (base + lane < nmid) K[D + 1 + base + lane] = mine;
-        }
-        if (lane < D + 1) {
-            K[lane] = 0.0f;
-            K[D + 1 + nmid + lane] = fin_time;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    __threadfence();
     for (int m = 0; m < dim; ++m) {
         C[m] = init[m];
         C[(S.n_cps - 1) * dim + m] = fin[m];
@@ -205,6 +179,41 @@ __global__ void __launch_bounds__(64) k_bspline_setup(WaSpline S, const float *_
         }
         ++idx;
     }
+}
+
+// SetParam (:72-78) = _CalcKnot (:150-171) + _CalcConstrainedCPoints (:387-447), one wavefront.  The knot chain
+// K[i] = K[i-1] + step is a sequential fp32 recurrence (its rounding is part of the result: it drifts from i*step).
+// ends = init rows then fin rows, (level+1) x dim each.
+__global__ void __launch_bounds__(64) k_bspline_setup(WaSpline S, const float *__restrict__ ends, float fin_time)
+{
+    const int D = S.degree, dim = S.dim;
+    float *K = S.knots;
+    const float *init = ends, *fin = ends + (size_t)(S.ci + 1) * dim;
+    {
+        // every lane runs the same recurrence; lane l keeps the value of step 64*c + l, so the chain costs
+        // three VALU operations per knot and the stores are one coalesced 256-B row per 64 knots
+        const int lane = threadIdx.x;
+        const long long nmid = S.n_knots - 2 * D - 2;
+        const float step = fin_time / (float)(nmid + 1);
+        float k = 0.0f;
+        for (long long base = 0; base < nmid; base += 64) {
+            float mine = 0.0f;
+#pragma unroll
+            for (int q = 0; q < 64; ++q) {
+                k = k + step;
+                mine = (lane == q) ? k : mine;
+            }
+            if (base + lane < nmid) K[D + 1 + base + lane] = mine;
+        }
+        if (lane < D + 1) {
+            K[lane] = 0.0f;
+            K[D + 1 + nmid + lane] = fin_time;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    __threadfence();
+    wa_bs_constrained_cps(S, init, fin, fin_time);
 }
 
 // _CalcCPoints (:458-464): control point ci+1+i <- first dim floats of middle row i

@@ -30,6 +30,7 @@
 #include "shortcut_kernels.hpp"
 #include "geodesic_kernels.hpp"
 #include "weighted_kernels.hpp"
+#include "fit_kernels.hpp"
 #include "stl_text.hpp"
 
 // ------------------------------------------------------------------ handles
@@ -771,5 +772,6 @@ void *wa_ctx_stream(wa_ctx *c) { return c ? (void *)c->stream : nullptr; }
 #include "host_shortcut.inc"
 #include "host_geodesic.inc"
 #include "host_weighted.inc"
+#include "host_fit.inc"
 
 }  // extern "C"
