@@ -232,6 +232,13 @@ def main():
     ap.add_argument("--fit", type=int, nargs="?", const=6, default=None, choices=range(0, 9), metavar="MAX_LEVEL",
                     help="needs --shortcut: the trajectory is wa_grid_fit_trajectory's (control points on the waypoints' polyline, refined "
                          "leg by leg up to MAX_LEVEL until the sampled curve clears the metal) instead of the cubic through the waypoints")
+    ap.add_argument("--retime", action="store_true",
+                    help="re-time the trajectory's samples on the device (wa_traj_retime): rest to rest under --retime-limits, slow near the metal "
+                         "and round bends, and the positions every --retime-tick seconds, checked against the metal")
+    ap.add_argument("--retime-limits", type=float, nargs=6, default=[10.0, 20.0, 20.0, 10.0, 2.0, 4.0],
+                    metavar=("V_MAX", "ACC", "DEC", "A_LAT", "V_NEAR", "NEAR_D2"),
+                    help="--retime: coordinate units per s, per s^2 (up), per s^2 (down), per s^2 (lateral), per s where the distance field is <= NEAR_D2 (voxels squared)")
+    ap.add_argument("--retime-tick", type=float, default=0.001, help="--retime: the controller period in seconds")
     ap.add_argument("--fit-dump", default=None, help="--fit: write the fitted polyline (n x 3 float32) to this .npy file")
     args = ap.parse_args()
     if args.fit is not None and not args.shortcut:
@@ -332,6 +339,20 @@ def main():
         wsegs = [short[(min(a, b), max(a, b))] for a, b in edges] if args.shortcut else None
         traj, ok, info = smooth(ctx, grid, segs, wsegs, rev, fit=(metal, args.fit, args.fit_dump) if args.fit is not None else None)
         out.update(info, t_trajectory_s=time.perf_counter() - t2)
+        if args.retime:
+            # what the controller is sent: the same curve at a fixed period, as fast as the limits allow
+            t3 = time.perf_counter()
+            v_max, acc, dec, a_lat, v_near, near_d2 = args.retime_limits
+            curve = api.Trajectory.from_points(ctx, traj[ok.astype(bool)])
+            _, _, _, ticks, rs = curve.retime(v_max, acc, dec, args.retime_tick, a_lat=a_lat, grid=metal, v_near=v_near, near_d2=int(near_d2))
+            out.update(retime=dict(duration_s=rs["time_q"] / api.RETIME_Q, length=rs["length_q"] / api.RETIME_Q, n_ticks=rs["n_ticks"],
+                                   tick_s=args.retime_tick, peak_speed=float(np.sqrt(rs["peak_w_q"] / api.RETIME_Q)),
+                                   n_bound=dict(zip(("end", "v_max", "curvature", "clearance"), rs["n_bound"])),
+                                   n_on_cap=rs["n_on_cap"], n_on_ramp=rs["n_on_ramp"], n_triangle=rs["n_triangle"],
+                                   samples_clearance=curve.clearance(metal)[3],
+                                   ticks_clearance=ticks.clearance(metal)[3] if ticks is not None else None,   # (None: more than 2^31 ticks)
+                                   limits=dict(v_max=v_max, acc=acc, dec=dec, a_lat=a_lat, v_near=v_near, near_d2=int(near_d2))),
+                       t_retime_s=time.perf_counter() - t3)
         if args.safe_paths:
             # what the soft margin buys and costs, against the hop-optimal paths of the same pairs in the same seam order: steps over
             # the optimum, path nodes inside the outermost band, and (--shortcut) segments of the smoothed curve that cut the metal

@@ -597,6 +597,66 @@ typedef struct {
 int wa_grid_fit_trajectory(const wa_grid *g, const wa_traj *poly, int32_t degree, float spacing, int32_t max_level, int64_t n_samples,
                            int32_t *leg_level_out, wa_bspline **spline_out, wa_traj **samples_out, wa_fit_summary *sum);
 
+/* ---- re-timing a sampled trajectory: speed caps, ramps, controller ticks (not in the reference: main.cpp:341-351 and :117-131 pace
+ *      their loops by clock()) ----
+ * t holds samples p_0 ... p_(n-1) (fp32, 2 <= n <= 2^31), segment i joins p_i and p_(i+1).  The call finds the fastest speed profile along
+ * the samples that starts and ends at rest, stays below every cap and within the tangential acceleration / deceleration limits, the
+ * time at which every sample is reached, and the positions at a fixed controller period.  Everything is defined in integers of
+ * Q = 2^30 quanta per unit (of length, of squared speed, of time) so that the result is the same bytes whatever computes it.
+ * "double" is IEEE float64, every operation rounded on its own (no contraction); rint rounds ties to even.
+ * 1. Lengths.  ds_i = the length of segment i as wa_grid_path_shortcut defines one (double on the fp32 coordinates,
+ *    sqrt((dx*dx + dy*dy) + dz*dz)).  L_i = (int64)rint(ds_i * Q), A_i = (int64)rint(((2 * acc) * ds_i) * Q), D_i likewise with dec (each 2^61
+ *    where the product is 2^61 or more); where L_i > 0 both A_i and D_i are raised to at least 1, where L_i = 0 both are 0.  GA, GD = the
+ *    exclusive prefix sums of A, D over segments (GA_0 = 0, n entries).
+ * 2. Caps, as squared speeds in double, per sample; the cap of a sample is the minimum, its kind the lowest-numbered kind attaining it.
+ *    Kind 0: samples 0 and n-1 have cap 0 (rest to rest).  Kind 1: m * m with m = min(v_max, (double)v_limit[i]).  Kind 2, interior
+ *    samples only and only when a_lat is finite and not 0: with u = p_i - p_(i-1), v = p_(i+1) - p_i, w = p_(i+1) - p_(i-1) in double,
+ *    c = |u x v| (components u_y v_z - u_z v_y, u_z v_x - u_x v_z, u_x v_y - u_y v_x; every norm sqrt((x*x + y*y) + z*z)),
+ *    den = (|u| * |v|) * |w|: if c > 0 and den > 0 the cap is a_lat / ((2 * c) / den) (Menger curvature), else none.  Kind 3, when g is given
+ *    and near_d2 >= 0: the sample's voxel by the lookup of wa_traj_clearance; if its d2 <= near_d2 the cap is v_near * v_near.
+ *    C_i = (int64)floor(cap * Q), and 2^61 where that product is infinite or >= 2^61.
+ * 3. Forward and backward pass.  F_0 = C_0, F_i = min(C_i, F_(i-1) + A_(i-1)); B_(n-1) = F_(n-1), B_i = min(F_i, B_(i+1) + D_i).  In integers
+ *    these are exactly F_i = min_(j <= i) (C_j - GA_j) + GA_i and B_i = min_(j >= i) (F_j + GD_j) - GD_i, a prefix and a suffix minimum, which
+ *    is what the device computes.  w_q_out[i] = B_i, the squared speed at sample i.
+ * 4. bound_out[i]: bit 0 B_i = C_i; bit 1 i > 0 and B_i - B_(i-1) = A_(i-1); bit 2 i < n-1 and B_i - B_(i+1) = D_i; bits 4-5 the kind of the
+ *    sample's cap.  Every sample has at least one of bits 0-2: the profile is on a cap or on a ramp everywhere, which is what makes it
+ *    the fastest one.
+ * 5. Times.  v_i = sqrt((double)B_i / Q).  (a) L_i = 0: dt_i = 0.  (b) L_i > 0 and v_i + v_(i+1) = 0 (a segment from rest to rest):
+ *    w_p = (((2 * ds_i) * acc) * dec) / (acc + dec), t_up = sqrt(w_p) / acc, dt_i = t_up + sqrt(w_p) / dec.  (c) otherwise
+ *    dt_i = (2 * ds_i) / (v_i + v_(i+1)).  T_i = (int64)rint(dt_i * Q); time_q_out = the exclusive prefix sum of T (entry 0 is 0, entry n-1
+ *    the duration).
+ * 6. Ticks.  tick_q = (int64)rint(tick * Q), in 1 .. 2^61.  Outputs at tau_k = k * tick_q for k = 0 .. floor(duration / tick_q), and one
+ *    more at the duration if that is no multiple of tick_q.  For a tau: i = the largest index in 0 .. n-2 with time_q[i] <= tau;
+ *    e = (double)(tau - time_q[i]) / Q.  If tau >= time_q[i+1] the output is p_(i+1) exactly; else if L_i = 0 it is p_i exactly.  Else, in
+ *    case (c), s = (v_i * e) + ((0.5 * a) * e) * e with a = ((double)(B_(i+1) - B_i) / Q) / (2 * ds_i); in case (b) s = ((0.5 * acc) * e) * e for
+ *    e <= t_up, else ds_i - ((0.5 * dec) * r) * r with r = dt_i - e.  lambda = s / ds_i clamped into [0, 1]; per axis
+ *    out = (float)((double)a_c + ((double)b_c - (double)a_c) * lambda) with a = p_i, b = p_(i+1).  *ticks_out is an ordinary device-resident
+ *    wa_traj owned by the caller: wa_traj_clearance can check what the controller will actually be sent.
+ * 7. Errors.  WA_ERR_ARG before anything is written: NULL t / lim / sum, g and t from different contexts, n < 2 or > 2^31, v_max / acc /
+ *    dec not finite or <= 0, a_lat negative or NaN, v_near not finite or <= 0 where it is used (g given and near_d2 >= 0), a v_limit
+ *    entry not finite or <= 0, a coordinate that is not finite, tick not finite or tick_q outside 1 .. 2^61, the sum of L, of A, of D or
+ *    of T reaching 2^61.  More than 2^31 ticks: WA_ERR_CAPACITY with *sum and the per-sample outputs filled and *ticks_out = NULL.
+ * time_q_out, w_q_out, bound_out (n entries each, host) and ticks_out may be NULL.  Same bytes on every call; everything runs on the
+ * context's stream; g and t are not modified.  g may be NULL: then there is no clearance cap and n_outside is 0. */
+typedef struct {
+    double v_max;     /* speed cap everywhere, coordinate units per second, > 0, finite */
+    double acc, dec;  /* tangential acceleration / deceleration, > 0, finite */
+    double a_lat;     /* lateral (centripetal) acceleration allowed; +inf or 0: no curvature cap */
+    double v_near;    /* speed cap where the distance field says "near the metal"; ignored when g == NULL or near_d2 < 0 */
+    int32_t near_d2;  /* "near": d2 of the sample's voxel <= near_d2 (voxel-index units squared, as wa_traj_clearance reports); < 0: off */
+} wa_retime_limits;
+typedef struct {
+    int64_t n, n_ticks;          /* samples in, positions out */
+    int64_t length_q, time_q;    /* total arc length and duration in quanta of 2^-30 (units, seconds) */
+    int64_t n_bound[4];          /* samples whose cap is of kind: 0 an end point, 1 v_max / v_limit, 2 curvature, 3 clearance */
+    int64_t n_on_cap, n_on_ramp; /* samples with B == C; samples with a tight ramp on either side (may overlap) */
+    int64_t n_triangle;          /* segments travelled rest -> peak -> rest (rule 5b) */
+    int64_t n_outside;           /* as wa_clearance_summary (0 when g == NULL) */
+    int64_t peak_w_q;            /* largest squared speed reached, in quanta */
+} wa_retime_summary;
+int wa_traj_retime(const wa_grid *g, const wa_traj *t, const wa_retime_limits *lim, const float *v_limit, double tick,
+                   int64_t *time_q_out, int64_t *w_q_out, uint8_t *bound_out, wa_traj **ticks_out, wa_retime_summary *sum);
+
 #ifdef __cplusplus
 }
 #endif

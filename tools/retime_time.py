@@ -1,0 +1,193 @@
+#!/usr/bin/env python3
+"""Time wa_traj_retime against the same computation composed from what existed before it: wa_traj_read, the definition of
+include/weldacs.h in numpy on the host (below; the grid's distance field and axis tables are fetched once, outside the timed part),
+wa_traj_from_points for the ticks.  Both run in the same process on the same samples and must end on the same bytes.
+  (a) 96^3 synth_grid, 16 points, --safe-paths 3 --shortcut --fit: the fit's 6 001 samples
+  (b) 256^3 synth_grid, 64 points, --exact-paths --shortcut --fit: 100 001 samples
+  (c) a synthetic curve of 2^24 samples, no grid: the bytes the kernels must move over the time, as a share of 8 TB/s
+Whole calls, HIP events on the context's stream, one warm-up, median and range.  Kernel times: run it alone under
+`rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/retime_time.py --reps 3 --only c`.
+
+    python tools/retime_time.py [--reps N] [--only a|b|c] [--limits V_MAX ACC DEC A_LAT V_NEAR NEAR_D2]"""
+import ctypes as C
+import importlib.util
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+
+from welding_robot_amd import api, build, synth
+
+reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 10
+only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else "abc"
+spec = importlib.util.spec_from_file_location("plan_batch", os.path.join(ROOT, "examples", "plan_batch.py"))
+pb = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(pb)
+hip = C.CDLL(os.path.join(build.rocm_lib_dir(), "libamdhip64.so"))
+ctx = api.Context(0)
+print("device:", ctx.device_name)
+stream = C.c_void_p(ctx.stream)
+ev = [C.c_void_p(), C.c_void_p()]
+assert hip.hipEventCreate(C.byref(ev[0])) == 0 and hip.hipEventCreate(C.byref(ev[1])) == 0
+Q, QF, CAP = 1 << 30, np.float64(1 << 30), 1 << 61
+
+
+def timed(fn):
+    out, times = None, []
+    for r in range(reps + 1):          # the first call warms up
+        ctx.sync()
+        hip.hipEventRecord(ev[0], stream)
+        out = fn()
+        hip.hipEventRecord(ev[1], stream)
+        hip.hipEventSynchronize(ev[1])
+        ms = C.c_float()
+        hip.hipEventElapsedTime(C.byref(ms), ev[0], ev[1])
+        if r:
+            times.append(ms.value)
+    return out, float(np.median(times)), "median %.3f ms (min %.3f, max %.3f, %d calls)" % (np.median(times), min(times), max(times), reps)
+
+
+# ---- the definition's steps on the host (include/weldacs.h, rules 1 - 6), for the composed call
+def norm(d):
+    return np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+
+
+def quanta(x):
+    q = np.rint(x * QF)
+    return np.where(q < float(CAP), q, float(CAP)).astype(np.int64)
+
+
+def axis_nodes(c, p):
+    p = np.clip(p, c.min(), c.max())
+    j = np.empty(len(p), np.int64)
+    for s in range(0, len(p), 1 << 16):
+        j[s:s + (1 << 16)] = np.argmin(np.abs(p[s:s + (1 << 16), None] - c[None, :]), axis=1)
+    return j
+
+
+def host_retime(p32, lim, tick, field=None):
+    v_max, acc, dec, a_lat, v_near, near_d2 = lim
+    p = p32.astype(np.float64)
+    n = len(p)
+    ds = norm(p[1:] - p[:-1])
+    L = quanta(ds)
+    A = np.where(L > 0, np.maximum(quanta((2.0 * acc) * ds), 1), 0)
+    D = np.where(L > 0, np.maximum(quanta((2.0 * dec) * ds), 1), 0)
+    cap = np.full(n, v_max * v_max)
+    kind = np.ones(n, np.uint8)
+    if np.isfinite(a_lat) and a_lat != 0 and n > 2:
+        u, v, w = p[1:-1] - p[:-2], p[2:] - p[1:-1], p[2:] - p[:-2]
+        c = norm(np.stack([u[:, 1] * v[:, 2] - u[:, 2] * v[:, 1], u[:, 2] * v[:, 0] - u[:, 0] * v[:, 2], u[:, 0] * v[:, 1] - u[:, 1] * v[:, 0]], 1))
+        den = (norm(u) * norm(v)) * norm(w)
+        with np.errstate(all="ignore"):
+            k2 = np.where((c > 0) & (den > 0), a_lat / ((2.0 * c) / den), np.inf)
+        take = k2 < cap[1:-1]
+        cap[1:-1] = np.where(take, k2, cap[1:-1])
+        kind[1:-1] = np.where(take, 2, kind[1:-1])
+    n_outside = 0
+    if field is not None:
+        d2, (nx, ny, nz), (cx, cy, cz) = field
+        ids = (axis_nodes(cz, p32[:, 2]) * ny + axis_nodes(cy, p32[:, 1])) * nx + axis_nodes(cx, p32[:, 0])
+        n_outside = int(((p32 < [cx.min(), cy.min(), cz.min()]) | (p32 > [cx.max(), cy.max(), cz.max()])).any(1).sum())
+        take = (d2[ids] <= near_d2) & (v_near * v_near < cap) if near_d2 >= 0 else np.zeros(n, bool)
+        cap = np.where(take, v_near * v_near, cap)
+        kind = np.where(take, 3, kind).astype(np.uint8)
+    cap[[0, -1]] = 0.0
+    kind[[0, -1]] = 0
+    q = cap * QF
+    Cq = np.where(q < float(CAP), np.floor(np.minimum(q, float(CAP))), float(CAP)).astype(np.int64)
+    GA = np.concatenate([[0], np.cumsum(A)])
+    GD = np.concatenate([[0], np.cumsum(D)])
+    F = np.minimum.accumulate(Cq - GA) + GA
+    B = np.minimum.accumulate((F + GD)[::-1])[::-1] - GD
+    bound = (B == Cq).astype(np.uint8) | (kind << 4)
+    bound[1:] |= ((B[1:] - B[:-1]) == A).astype(np.uint8) << 1
+    bound[:-1] |= ((B[:-1] - B[1:]) == D).astype(np.uint8) << 2
+    v = np.sqrt(B.astype(np.float64) / QF)
+    vs = v[:-1] + v[1:]
+    tri = (L > 0) & (vs == 0)
+    wp = (((2.0 * ds) * acc) * dec) / (acc + dec)
+    t_up = np.sqrt(wp) / acc
+    with np.errstate(all="ignore"):
+        dt = np.where(tri, t_up + np.sqrt(wp) / dec, np.where(L > 0, (2.0 * ds) / vs, 0.0))
+    time_q = np.concatenate([[0], np.cumsum(quanta(dt))])
+    total, tick_q = int(time_q[-1]), int(np.rint(tick * QF))
+    taus = np.arange(total // tick_q + 1, dtype=np.int64) * tick_q
+    if total % tick_q:
+        taus = np.concatenate([taus, [total]])
+    i = np.searchsorted(time_q[:n - 1], taus, side="right") - 1
+    e = (taus - time_q[i]).astype(np.float64) / QF
+    with np.errstate(all="ignore"):
+        a = ((B[i + 1] - B[i]).astype(np.float64) / QF) / (2.0 * ds[i])
+        r = dt[i] - e
+        s = np.where(tri[i], np.where(e <= t_up[i], ((0.5 * acc) * e) * e, ds[i] - ((0.5 * dec) * r) * r), (v[i] * e) + ((0.5 * a) * e) * e)
+        lam = np.clip(np.nan_to_num(s / ds[i]), 0.0, 1.0)
+    end, still = taus >= time_q[i + 1], L[i] == 0
+    ticks = (p[i] + (p[i + 1] - p[i]) * lam[:, None]).astype(np.float32)
+    ticks[still] = p32[i[still]]
+    ticks[end] = p32[i[end] + 1]
+    return time_q, B, bound, ticks, n_outside
+
+
+def compare(tag, traj, lim, tick, grid=None, field=None):
+    n = len(traj)
+    kw = dict(a_lat=lim[3], grid=grid, v_near=lim[4], near_d2=int(lim[5]))
+
+    def fused():
+        tq, w, b, ticks, s = traj.retime(lim[0], lim[1], lim[2], tick, **kw)
+        return tq, w, b, ticks, s
+
+    def composed():
+        tq, w, b, pts, _ = host_retime(traj.points(), lim, tick, field)
+        return tq, w, b, api.Trajectory.from_points(ctx, pts)
+
+    f, f_ms, t_fused = timed(fused)
+    c, c_ms, t_comp = timed(composed)
+    same = all(np.array_equal(x, y) for x, y in zip(f[:3], c[:3])) and f[3].points().tobytes() == c[3].points().tobytes()
+    s = f[4]
+    print("(%s) %d samples: duration %.3f s, %d ticks of %g s, kinds %s, on cap %d, on ramp %d" %
+          (tag, n, s["time_q"] / Q, s["n_ticks"], tick, s["n_bound"], s["n_on_cap"], s["n_on_ramp"]))
+    print("    fused call (+ read of time_q, w_q, bound): %s" % t_fused)
+    print("    composed (read, numpy, upload of ticks):    %s; same bytes: %s" % (t_comp, same))
+    return s, f_ms
+
+
+def planned(n, P, safe, n_samples):
+    free, cx, cy, cz, prec, wall = synth.synth_grid(n, seed=2024, occ_prob=0.10)
+    grid = api.Grid.from_occupancy(ctx, free, cx, cy, cz, prec, wall)
+    pts = synth.synth_weld_points(free, n, P, seed=7)
+    cost, paths, _ = pb.plan_safe(grid, pts, 3, shortcut=128) if safe else pb.plan_exact(grid, pts, shortcut=128)
+    short = pb.plan.last_shortcut
+    edges = api.gtsp_solve(ctx, cost, mode=api.RNG_DEV, seed=7)["edges"][0][:-1]
+    wsegs = [short[(min(a, b), max(a, b))] for a, b in edges]
+    poly = api.Trajectory.stitch(grid, wsegs, [1 if a > b else 0 for a, b in edges])
+    _, samples, _, _ = poly.fit(grid, 3, None, 6, n_samples)
+    field = (grid.distance_field().ravel(), (grid.nx, grid.ny, grid.nz), grid.coords())
+    return grid, samples, field
+
+
+# v_max, acc, dec, a_lat, v_near (coordinate units and seconds), near_d2 (voxels squared); default: those of examples/plan_batch.py --retime
+LIMITS = tuple(float(v) for v in sys.argv[sys.argv.index("--limits") + 1:sys.argv.index("--limits") + 7]) if "--limits" in sys.argv \
+    else (10.0, 20.0, 20.0, 10.0, 2.0, 4.0)
+print("limits (a), (b):", LIMITS)
+for tag, n, P, safe, n_samples in (("a", 96, 16, True, 6001), ("b", 256, 64, False, 100001)):
+    if tag in only:
+        grid, samples, field = planned(n, P, safe, n_samples)
+        compare(tag, samples, LIMITS, 0.001, grid, field)
+if "c" in only:
+    n = 1 << 24
+    t = np.arange(n, dtype=np.float64) * (40.0 / n)
+    xyz = np.stack([t * 0.05, 0.3 * np.sin(t), 0.2 * np.cos(0.037 * t * t)], 1).astype(np.float32)
+    s, ms = compare("c", api.Trajectory.from_points(ctx, xyz), (0.8, 1.0, 1.5, 0.6, 0.0, -1.0), 0.001)
+    # bytes the kernels must move, from the arrays of rules 1 - 6 (int64 unless said; xyz 12 B, kind / bound 1 B per sample):
+    per_sample = {"k_rt_segments": 12 + 16, "k_rt_caps": 12 + 8 + 1, "k_rt_scan forward (reduce + add)": 2 * 16 + 8,
+                  "k_rt_scan backward (reduce + add)": 2 * 16 + 8, "k_rt_times": 12 + 4 * 8 + 1 + 1 + 8, "k_rt_scan times (reduce + add)": 2 * 8 + 8}
+    total = n * sum(per_sample.values()) + s["n_ticks"] * (12 + 12 + 3 * 8) + n * (8 + 8 + 1)
+    for k, v in per_sample.items():
+        print("    %-36s %6.1f MB" % (k, n * v / 1e6))
+    print("    k_rt_ticks (per tick: 2 points, B x 2, time_q, 12 B out; the search's reads not counted) %6.1f MB" % (s["n_ticks"] * 48 / 1e6))
+    print("    outputs to the host (time_q, w_q, bound) %6.1f MB" % (n * 17 / 1e6))
+    print("    whole call: %.1f MB in %.3f ms = %.1f GB/s = %.2f %% of 8 TB/s (the copy to the host runs at the link's rate, not HBM's)"
+          % (total / 1e6, ms, total / ms / 1e6, 100 * total / ms / 1e6 / 8000))

@@ -43,6 +43,17 @@ class FitSummary(C.Structure):
                 ("n_cps", C.c_int64), ("n_hit_first", C.c_int64), ("final", ClearanceSummary)]
 
 
+class RetimeLimits(C.Structure):
+    _fields_ = [("v_max", C.c_double), ("acc", C.c_double), ("dec", C.c_double), ("a_lat", C.c_double), ("v_near", C.c_double),
+                ("near_d2", C.c_int32)]
+
+
+class RetimeSummary(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_ticks", C.c_int64), ("length_q", C.c_int64), ("time_q", C.c_int64), ("n_bound", C.c_int64 * 4),
+                ("n_on_cap", C.c_int64), ("n_on_ramp", C.c_int64), ("n_triangle", C.c_int64), ("n_outside", C.c_int64),
+                ("peak_w_q", C.c_int64)]
+
+
 # every symbol include/weldacs.h declares: name -> (restype, argtypes)
 _V, _I, _I64, _F, _P = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_void_p
 SYMBOLS = {
@@ -148,6 +159,7 @@ SYMBOLS = {
     "wa_grid_weighted_matrix": (C.c_int, [_V, _P, _P, _I, _P]),
     "wa_grid_weighted_paths": (C.c_int, [_V, _P, _P, _P, _I, _P, _P, _P, _P]),
     "wa_grid_fit_trajectory": (C.c_int, [_V, _V, _I, _F, _I, _I64, _P, C.POINTER(_V), C.POINTER(_V), C.POINTER(FitSummary)]),
+    "wa_traj_retime": (C.c_int, [_V, _V, C.POINTER(RetimeLimits), _P, C.c_double, _P, _P, _P, C.POINTER(_V), C.POINTER(RetimeSummary)]),
 }
 
 _libs = {}

@@ -10,6 +10,9 @@ from . import _lib as L
 from ._lib import AcsParams, GtspParams, RNG_DEV, RNG_REF, WA_COST_MAX, WA_D2_NONE, WA_DIST_NONE, WA_HOPS_NONE, WeldacsError  # noqa: F401
 
 
+RETIME_Q = 1 << 30   # quanta per unit in wa_traj_retime's integers
+
+
 def _ptr(a):
     return a.ctypes.data if a is not None else None
 
@@ -676,6 +679,26 @@ class Trajectory:
         summary = {k: int(getattr(s, k)) for k, _ in L.FitSummary._fields_ if k != "final"}
         summary["final"] = {k: int(getattr(s.final, k)) for k, _ in L.ClearanceSummary._fields_}
         return Bspline.adopt(self.ctx, bh, 3, degree, summary["n_cps"] - 2 * degree), Trajectory(self.ctx, th), levels, summary
+
+    def retime(self, v_max, acc, dec, tick, a_lat=float("inf"), grid=None, v_near=0.0, near_d2=-1, v_limit=None, ticks=True):
+        """wa_traj_retime with these samples: the fastest rest-to-rest speed profile under the caps (v_max, the per-sample v_limit, a_lat
+        over the curvature, v_near where `grid`'s distance field is <= near_d2) and the ramps acc / dec, and the positions every `tick`
+        seconds.  Returns (time_q int64[n], w_q int64[n], bound uint8[n], ticks Trajectory or None, summary dict); times and squared
+        speeds are in quanta of 2^-30 (RETIME_Q)."""
+        n = len(self)
+        lim = L.RetimeLimits(v_max, acc, dec, a_lat, v_near, near_d2)
+        if v_limit is not None:
+            v_limit = np.ascontiguousarray(v_limit, np.float32).reshape(-1)
+            if len(v_limit) != n:
+                raise ValueError("v_limit needs one entry per sample")
+        time_q, w_q, bound = np.empty(n, np.int64), np.empty(n, np.int64), np.empty(n, np.uint8)
+        th, s = C.c_void_p(), L.RetimeSummary()
+        rc = self.ctx.lib.wa_traj_retime(grid.h if grid is not None else None, self.h, C.byref(lim), _ptr(v_limit), C.c_double(tick),
+                                         _ptr(time_q), _ptr(w_q), _ptr(bound), C.byref(th) if ticks else None, C.byref(s))
+        if rc != 7:   # WA_ERR_CAPACITY: everything but the ticks is there
+            self.ctx.check(rc)
+        summary = {k: (list(getattr(s, k)) if k == "n_bound" else int(getattr(s, k))) for k, _ in L.RetimeSummary._fields_}
+        return time_q, w_q, bound, Trajectory(self.ctx, th) if th.value else None, summary
 
     def close(self):
         if getattr(self, "h", None):

@@ -1,0 +1,139 @@
+// host_retime.inc -- C ABI: wa_traj_retime, speed caps, ramps and controller ticks along a sampled trajectory (included by weldacs.hip
+// inside extern "C").  Everything between the arguments and the results stays on the device, on the context's stream; the host reads
+// ONE WaRtRec (sums, counters, what was refused), sizes the tick buffer from it and launches the ticks.
+struct RetimeBuffers {
+    long long *A = nullptr, *D = nullptr, *C = nullptr, *F = nullptr, *B = nullptr, *T = nullptr, *time_q = nullptr;
+    uint8_t *kind = nullptr, *bound = nullptr;
+    float *v_limit = nullptr;
+    RtPair *scratch = nullptr;
+    WaRtRec *rec = nullptr;
+    wa_traj *ticks = nullptr;
+    ~RetimeBuffers()
+    {
+        hipFree(A); hipFree(D); hipFree(C); hipFree(F); hipFree(B); hipFree(T); hipFree(time_q); hipFree(kind); hipFree(bound);
+        hipFree(v_limit); hipFree(scratch); hipFree(rec);
+        wa_traj_destroy(ticks);
+    }
+};
+
+static long long rt_scratch_pairs(long long n)
+{
+    long long total = 0;
+    for (long long m = (n + WA_RT_TILE - 1) / WA_RT_TILE; m > 1; m = (m + WA_RT_TILE - 1) / WA_RT_TILE) total += m;
+    return total + 1;
+}
+
+static bool rt_sum_fits(const unsigned long long w[2], int64_t *out)
+{
+    const unsigned __int128 v = ((unsigned __int128)w[1] << 32) + w[0];
+    if (v >= (unsigned __int128)WA_RT_CAP) return false;
+    *out = (int64_t)v;
+    return true;
+}
+
+static bool rt_pos_finite(double x) { return x > 0.0 && std::isfinite(x); }
+
+int wa_traj_retime(const wa_grid *g, const wa_traj *t, const wa_retime_limits *lim, const float *v_limit, double tick,
+                   int64_t *time_q_out, int64_t *w_q_out, uint8_t *bound_out, wa_traj **ticks_out, wa_retime_summary *sum)
+{
+    WaDevGuard dev_guard_(t ? t->ctx : nullptr);
+    if (!dev_guard_.ok) return WA_ERR_DEVICE;   // the context's device could not be made current
+    if (!t) return WA_ERR_ARG;
+    wa_ctx *ctx = t->ctx;
+    if (!lim || !sum) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: NULL limits or summary");
+    if (g && g->ctx != ctx) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: trajectory and grid belong to different contexts");
+    const int64_t n = t->n;
+    if (n < 2 || n > WA_RT_MAX_N) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: a trajectory needs 2 .. 2^31 samples");
+    if (!rt_pos_finite(lim->v_max) || !rt_pos_finite(lim->acc) || !rt_pos_finite(lim->dec))
+        return fail(ctx, WA_ERR_ARG, "wa_traj_retime: v_max, acc and dec must be finite and > 0");
+    if (!(lim->a_lat >= 0.0)) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: a_lat must be >= 0 (0 or +inf: no curvature cap)");
+    if (g && lim->near_d2 >= 0 && !rt_pos_finite(lim->v_near)) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: v_near must be finite and > 0");
+    if (!std::isfinite(tick)) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: tick must be finite");
+    const double tq = rint(tick * WA_RT_Q);
+    if (!(tq >= 1.0 && tq <= (double)WA_RT_CAP)) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: tick must be 2^-30 .. 2^31 seconds");
+    const long long tick_q = (long long)tq;
+    WaClrAxes ax = {};
+    WaDims dims = {};
+    if (g) {
+        int rc = grid_build_d2(g);
+        if (rc) return rc;
+        rc = clr_axes(g, &ax);
+        if (rc) return rc;
+        dims = g->d;
+    }
+
+    RetimeBuffers R;
+    hipError_t e = dalloc(&R.A, (size_t)n);
+    e = e ? e : dalloc(&R.D, (size_t)n);
+    e = e ? e : dalloc(&R.C, (size_t)n);
+    e = e ? e : dalloc(&R.F, (size_t)n);
+    e = e ? e : dalloc(&R.B, (size_t)n);
+    e = e ? e : dalloc(&R.T, (size_t)n);
+    e = e ? e : dalloc(&R.time_q, (size_t)n);
+    e = e ? e : dalloc(&R.kind, (size_t)n);
+    e = e ? e : dalloc(&R.bound, (size_t)n);
+    e = e ? e : dalloc(&R.scratch, (size_t)rt_scratch_pairs(n));
+    e = e ? e : dalloc(&R.rec, 1);
+    if (v_limit) e = e ? e : dalloc(&R.v_limit, (size_t)n);
+    if (e != hipSuccess) return fail(ctx, WA_ERR_ALLOC, "wa_traj_retime: device buffers");
+    e = hipMemsetAsync(R.rec, 0, sizeof(WaRtRec), ctx->stream);
+    if (v_limit) e = e ? e : hipMemcpyAsync(R.v_limit, v_limit, sizeof(float) * n, hipMemcpyHostToDevice, ctx->stream);
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    WaRtLimits dl;
+    dl.v_max = lim->v_max; dl.acc = lim->acc; dl.dec = lim->dec; dl.a_lat = lim->a_lat; dl.v_near = lim->v_near;
+    dl.near_d2 = g ? lim->near_d2 : -1;
+    dl.curv = std::isfinite(lim->a_lat) && lim->a_lat != 0.0;
+    if (e == hipSuccess) {
+        k_rt_segments<<<blocks, 256, 0, ctx->stream>>>(t->xyz, n, dl.acc, dl.dec, R.A, R.D, R.rec);
+        k_rt_caps<<<blocks, 256, 0, ctx->stream>>>(t->xyz, n, dl, R.v_limit, g ? 1 : 0, dims, g ? g->cx : nullptr, g ? g->cy : nullptr,
+                                                   g ? g->cz : nullptr, ax, g ? g->d2 : nullptr, R.C, R.kind, R.rec);
+        e = hipGetLastError();
+    }
+    const RtSamples fwd = {R.A, R.C, R.F, n, 0}, bwd = {R.D, R.F, R.B, n, 1}, tim = {R.T, nullptr, R.time_q, n, 0};
+    e = e ? e : rt_scan(ctx->stream, fwd, R.scratch);
+    e = e ? e : rt_scan(ctx->stream, bwd, R.scratch);
+    if (e == hipSuccess) {
+        k_rt_times<<<blocks, 256, 0, ctx->stream>>>(t->xyz, n, dl.acc, dl.dec, R.A, R.D, R.C, R.B, R.kind, R.bound, R.T, R.rec);
+        e = hipGetLastError();
+    }
+    e = e ? e : rt_scan(ctx->stream, tim, R.scratch);
+    WaRtRec rec;
+    e = e ? e : hipMemcpyAsync(&rec, R.rec, sizeof rec, hipMemcpyDeviceToHost, ctx->stream);
+    e = e ? e : hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_traj_retime: %s", hipGetErrorString(e));
+    if (rec.bad & 1) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: a coordinate of the trajectory is not finite");
+    if (rec.bad & 4) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: v_limit entries must be finite and > 0");   // (k_rt_caps looked at every entry)
+    wa_retime_summary s;
+    memset(&s, 0, sizeof s);
+    int64_t sum_a = 0, sum_d = 0;
+    if (!rt_sum_fits(rec.sumL, &s.length_q) || !rt_sum_fits(rec.sumA, &sum_a) || !rt_sum_fits(rec.sumD, &sum_d))
+        return fail(ctx, WA_ERR_ARG, "wa_traj_retime: the sum of L, A or D reaches 2^61 quanta");
+    if ((rec.bad & 2) || !rt_sum_fits(rec.sumT, &s.time_q)) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: the duration reaches 2^61 quanta");
+    s.n = n;
+    const long long n_full = s.time_q / tick_q + 1;
+    s.n_ticks = n_full + (s.time_q % tick_q ? 1 : 0);
+    for (int k = 0; k < 4; k++) s.n_bound[k] = (int64_t)rec.n_bound[k];
+    s.n_on_cap = (int64_t)rec.n_on_cap;
+    s.n_on_ramp = (int64_t)rec.n_on_ramp;
+    s.n_triangle = (int64_t)rec.n_triangle;
+    s.n_outside = (int64_t)rec.n_outside;
+    s.peak_w_q = rec.peak;
+    const bool too_many = s.n_ticks > ((int64_t)1 << 31);
+    if (ticks_out && !too_many) {
+        int rc = traj_alloc(ctx, s.n_ticks, &R.ticks);
+        if (rc) return rc;
+        k_rt_ticks<<<(unsigned)((s.n_ticks + 255) / 256), 256, 0, ctx->stream>>>(t->xyz, n, dl.acc, dl.dec, R.B, R.time_q, tick_q, n_full,
+                                                                                 s.n_ticks, R.ticks->xyz);
+        e = hipGetLastError();
+    }
+    // (every WA_ERR_ARG has been answered by now: nothing was written before this line)
+    if (time_q_out) e = e ? e : hipMemcpyAsync(time_q_out, R.time_q, sizeof(int64_t) * n, hipMemcpyDeviceToHost, ctx->stream);
+    if (w_q_out) e = e ? e : hipMemcpyAsync(w_q_out, R.B, sizeof(int64_t) * n, hipMemcpyDeviceToHost, ctx->stream);
+    if (bound_out) e = e ? e : hipMemcpyAsync(bound_out, R.bound, (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
+    e = e ? e : hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_traj_retime: %s", hipGetErrorString(e));
+    if (ticks_out) { *ticks_out = R.ticks; R.ticks = nullptr; }
+    *sum = s;
+    if (too_many) return fail(ctx, WA_ERR_CAPACITY, "wa_traj_retime: more than 2^31 ticks");
+    return WA_OK;
+}

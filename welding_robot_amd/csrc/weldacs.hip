@@ -31,6 +31,7 @@
 #include "geodesic_kernels.hpp"
 #include "weighted_kernels.hpp"
 #include "fit_kernels.hpp"
+#include "retime_kernels.hpp"
 #include "stl_text.hpp"
 
 // ------------------------------------------------------------------ handles
@@ -773,5 +774,6 @@ void *wa_ctx_stream(wa_ctx *c) { return c ? (void *)c->stream : nullptr; }
 #include "host_geodesic.inc"
 #include "host_weighted.inc"
 #include "host_fit.inc"
+#include "host_retime.inc"
 
 }  // extern "C"
