@@ -195,23 +195,23 @@ class Grid:
         wps, lengths = shortcut_paths(self, [path], max_span)
         return wps[0], float(lengths[0])
 
+    def _search_rows(self, fn, lead, ids, points):
+        """the marshalling of the four fields / matrix calls: fn(grid, *lead, ids, len(ids), out), out int32 [len(ids), n] or, points,
+        [len(ids), len(ids)]; an empty array is passed as a one-element stand-in (the C side wants pointers that are not NULL)"""
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        out = np.empty((len(ids), len(ids) if points else self.n), np.int32)
+        self.ctx.check(fn(self.h, *lead, _ptr(ids if len(ids) else np.zeros(1, np.int64)), len(ids), _ptr(out if out.size else np.zeros(1, np.int32))))
+        return out
+
     def geodesic_fields(self, ids):
         """wa_grid_geodesic_fields: int32 [len(ids), n], exact hop counts on the 6-neighbour lattice of free voxels from each source
         (free voxels) to every voxel; WA_HOPS_NONE (-1) where there is no path"""
-        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
-        out = np.empty((len(ids), self.n), np.int32)
-        self.ctx.check(self.ctx.lib.wa_grid_geodesic_fields(self.h, _ptr(ids if len(ids) else np.zeros(1, np.int64)), len(ids),
-                                                            _ptr(out if out.size else np.zeros(1, np.int32))))
-        return out
+        return self._search_rows(self.ctx.lib.wa_grid_geodesic_fields, (), ids, False)
 
     def geodesic_matrix(self, ids):
         """wa_grid_geodesic_matrix: int32 [P, P] hop counts between the points (symmetric, 0 on the diagonal, WA_HOPS_NONE (-1) where
         two points are not connected)"""
-        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
-        out = np.empty((len(ids), len(ids)), np.int32)
-        self.ctx.check(self.ctx.lib.wa_grid_geodesic_matrix(self.h, _ptr(ids if len(ids) else np.zeros(1, np.int64)), len(ids),
-                                                            _ptr(out if out.size else np.zeros(1, np.int32))))
-        return out
+        return self._search_rows(self.ctx.lib.wa_grid_geodesic_matrix, (), ids, True)
 
     def clearance_costs(self, thr2):
         """wa_grid_clearance_costs: uint8 [n], 0 on occupied voxels, else 1 + the number of thresholds (squared distances in voxels, at
@@ -230,21 +230,13 @@ class Grid:
         """wa_grid_weighted_fields: int32 [len(ids), n], the exact least sum of entry costs (cost: uint8 [n], 1 .. WA_COST_MAX on free
         voxels) from each source to every voxel; WA_DIST_NONE (-1) where there is no path"""
         cost = self._cost(cost)
-        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
-        out = np.empty((len(ids), self.n), np.int32)
-        self.ctx.check(self.ctx.lib.wa_grid_weighted_fields(self.h, _ptr(cost), _ptr(ids if len(ids) else np.zeros(1, np.int64)), len(ids),
-                                                            _ptr(out if out.size else np.zeros(1, np.int32))))
-        return out
+        return self._search_rows(self.ctx.lib.wa_grid_weighted_fields, (_ptr(cost),), ids, False)
 
     def weighted_matrix(self, cost, ids):
         """wa_grid_weighted_matrix: int32 [P, P], [i, j] = dist(point i, point j) (not symmetric: [i, j] - [j, i] = cost[j] - cost[i]);
         WA_DIST_NONE (-1) where two points are not connected"""
         cost = self._cost(cost)
-        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
-        out = np.empty((len(ids), len(ids)), np.int32)
-        self.ctx.check(self.ctx.lib.wa_grid_weighted_matrix(self.h, _ptr(cost), _ptr(ids if len(ids) else np.zeros(1, np.int64)), len(ids),
-                                                            _ptr(out if out.size else np.zeros(1, np.int32))))
-        return out
+        return self._search_rows(self.ctx.lib.wa_grid_weighted_matrix, (_ptr(cost),), ids, True)
 
     def close(self):
         if getattr(self, "h", None):
@@ -269,53 +261,43 @@ def shortcut_paths(grid, paths, max_span=128):
     return [p[wp[off[k]:off[k] + cnt[k]]] for k, p in enumerate(paths)], lengths
 
 
-def geodesic_paths(grid, starts, ends):
-    """wa_grid_geodesic_paths of a batch of pairs: (int32 hops, [node-id array per pair, start first; None where hops is WA_HOPS_NONE]).
-    Two calls: the first, with empty ranges, returns the hop counts (WA_ERR_CAPACITY is its expected status when any pair is
-    reachable), the second writes the paths into ranges of hops + 1 ids."""
+def _paths_two_calls(grid, fn, lead, starts, ends, n_counts, lengths):
+    """The protocol of the _paths calls, fn(grid, *lead, starts, ends, n, off, ids, *counts) with n_counts int32 arrays of per-pair counts
+    (the first is negative where there is no path): the first call, with empty ranges, returns the counts (WA_ERR_CAPACITY is its
+    expected status when any pair is reachable); lengths(*counts) then sizes the ranges and the second call writes the paths into them.
+    Returns (counts, [node-id array per pair, start first; None where there is no path])."""
     starts = np.ascontiguousarray(starts, np.int64).reshape(-1)
     ends = np.ascontiguousarray(ends, np.int64).reshape(-1)
     assert len(starts) == len(ends)
     n = len(starts)
     ctx = grid.ctx
-    hops = np.empty(max(n, 1), np.int32)
+    counts = [np.zeros(max(n, 1), np.int32) for _ in range(n_counts)]
     off = np.zeros(n + 1, np.int64)
     pad = np.zeros(1, np.int64)
-    rc = ctx.lib.wa_grid_geodesic_paths(grid.h, _ptr(starts if n else pad), _ptr(ends if n else pad), n, _ptr(off), _ptr(pad), _ptr(hops))
+    rc = fn(grid.h, *lead, _ptr(starts if n else pad), _ptr(ends if n else pad), n, _ptr(off), _ptr(pad), *[_ptr(c) for c in counts])
     if rc not in (0, 7):
         ctx.check(rc)
-    hops = hops[:n]
-    off[1:] = np.cumsum(np.maximum(hops.astype(np.int64) + 1, 0))
+    off[1:] = np.cumsum(lengths(*[c[:n].astype(np.int64) for c in counts]))
     ids = np.empty(max(int(off[-1]), 1), np.int64)
     if rc == 7:
-        ctx.check(ctx.lib.wa_grid_geodesic_paths(grid.h, _ptr(starts), _ptr(ends), n, _ptr(off), _ptr(ids), _ptr(hops)))
-    return hops, [ids[off[k]:off[k + 1]].copy() if hops[k] >= 0 else None for k in range(n)]
+        ctx.check(fn(grid.h, *lead, _ptr(starts), _ptr(ends), n, _ptr(off), _ptr(ids), *[_ptr(c) for c in counts]))
+    counts = [c[:n] for c in counts]
+    return counts, [ids[off[k]:off[k + 1]].copy() if counts[0][k] >= 0 else None for k in range(n)]
+
+
+def geodesic_paths(grid, starts, ends):
+    """wa_grid_geodesic_paths of a batch of pairs: (int32 hops, [node-id array per pair, start first; None where hops is WA_HOPS_NONE]),
+    the paths in ranges of hops + 1 ids (_paths_two_calls)"""
+    (hops,), paths = _paths_two_calls(grid, grid.ctx.lib.wa_grid_geodesic_paths, (), starts, ends, 1, lambda hops: np.maximum(hops + 1, 0))
+    return hops, paths
 
 
 def weighted_paths(grid, cost, starts, ends):
     """wa_grid_weighted_paths of a batch of pairs: (int32 dist, int32 node counts, [node-id array per pair, start first; None where dist
-    is WA_DIST_NONE]).  Two calls like geodesic_paths: the first, with empty ranges, returns distances and node counts
-    (WA_ERR_CAPACITY is its expected status when any pair is reachable), the second writes the paths into ranges of len ids."""
+    is WA_DIST_NONE]), the paths in ranges of len ids (_paths_two_calls)"""
     cost = grid._cost(cost)
-    starts = np.ascontiguousarray(starts, np.int64).reshape(-1)
-    ends = np.ascontiguousarray(ends, np.int64).reshape(-1)
-    assert len(starts) == len(ends)
-    n = len(starts)
-    ctx = grid.ctx
-    dist = np.empty(max(n, 1), np.int32)
-    lens = np.zeros(max(n, 1), np.int32)
-    off = np.zeros(n + 1, np.int64)
-    pad = np.zeros(1, np.int64)
-    rc = ctx.lib.wa_grid_weighted_paths(grid.h, _ptr(cost), _ptr(starts if n else pad), _ptr(ends if n else pad), n, _ptr(off), _ptr(pad),
-                                        _ptr(dist), _ptr(lens))
-    if rc not in (0, 7):
-        ctx.check(rc)
-    dist, lens = dist[:n], lens[:n]
-    off[1:] = np.cumsum(lens.astype(np.int64))
-    ids = np.empty(max(int(off[-1]), 1), np.int64)
-    if rc == 7:
-        ctx.check(ctx.lib.wa_grid_weighted_paths(grid.h, _ptr(cost), _ptr(starts), _ptr(ends), n, _ptr(off), _ptr(ids), _ptr(dist), _ptr(lens)))
-    return dist, lens, [ids[off[k]:off[k + 1]].copy() if dist[k] >= 0 else None for k in range(n)]
+    (dist, lens), paths = _paths_two_calls(grid, grid.ctx.lib.wa_grid_weighted_paths, (_ptr(cost),), starts, ends, 2, lambda dist, lens: lens)
+    return dist, lens, paths
 
 
 def default_params(**kw):

@@ -14,6 +14,69 @@ struct WaGeoDims {
     int64_t n;        // voxels
 };
 
+// ---- what the kernels of this file and of weighted_kernels.hpp share
+// voxel id -> its word within a bitmap; *bit = its bit in that word
+__device__ __forceinline__ int64_t geo_word_of(long long v, const WaGeoDims &g, int32_t *bit)
+{
+    const long long row = v / g.nx;
+    const int32_t x = (int32_t)(v - row * g.nx);
+    *bit = x & 63;
+    return row * g.W + (x >> 6);
+}
+
+// The matrix's targets, by all 256 threads of the first block of a source: `value` goes to row_out[t] for every target t in the frontier
+// cur (which the launch before completed); once no entry of the row is missing, stop[s] = 1.
+__device__ __forceinline__ void geo_lookup_targets(const unsigned long long *__restrict__ cur, const WaGeoDims &g, const long long *__restrict__ tgt,
+                                                   int32_t n_tgt, int32_t *__restrict__ row_out, int32_t value, int32_t *__restrict__ stop_s)
+{
+    int missing = 0;
+    for (int32_t t = (int32_t)threadIdx.x; t < n_tgt; t += 256) {
+        int32_t bit;
+        const int64_t w = geo_word_of(tgt[t], g, &bit);
+        if ((cur[w] >> bit) & 1ull) row_out[t] = value;
+        else if (row_out[t] < 0) missing = 1;
+    }
+    if (!__syncthreads_or(missing) && threadIdx.x == 0) *stop_s = 1;
+}
+
+// the six neighbours of the voxels of cur, at word w = row * W + wx of one bitmap: the word shifted both ways with the carries of the
+// words beside it in the row, ORed with the words at +-1 row and +-1 slab (none across the grid's faces).  *own = cur[w].
+__device__ __forceinline__ unsigned long long geo_neighbours(const unsigned long long *__restrict__ cur, const WaGeoDims &g, int64_t w, int64_t row,
+                                                             int32_t wx, unsigned long long *own)
+{
+    const int32_t z = (int32_t)(row / g.ny), y = (int32_t)(row - (int64_t)z * g.ny);
+    const int64_t slab = (int64_t)g.W * g.ny;
+    const unsigned long long c = cur[w];
+    const unsigned long long l = wx > 0 ? cur[w - 1] : 0ull, r = wx < g.W - 1 ? cur[w + 1] : 0ull;
+    const unsigned long long ym = y > 0 ? cur[w - g.W] : 0ull, yp = y < g.ny - 1 ? cur[w + g.W] : 0ull;
+    const unsigned long long zm = z > 0 ? cur[w - slab] : 0ull, zp = z < g.nz - 1 ? cur[w + slab] : 0ull;
+    *own = c;
+    return ((c << 1) | (l >> 63)) | ((c >> 1) | (r << 63)) | ym | yp | zm | zp;
+}
+
+// f[b] = level for every set bit b of m (m != 0; f: the field at the word's first voxel)
+__device__ __forceinline__ void geo_store_level(int32_t *__restrict__ f, unsigned long long m, int32_t level)
+{
+    do {
+        f[__builtin_ctzll(m)] = level;
+        m &= m - 1;
+    } while (m);
+}
+
+// the walk-backs' predecessor of v: the first neighbour in the order -x, +x, -y, +y, -z, +z that is inside the grid and holds `want` in
+// the field f; -1 when there is none
+__device__ __forceinline__ long long geo_predecessor(const int32_t *__restrict__ f, const WaGeoDims &g, int64_t nxy, long long v, int32_t want)
+{
+    const int32_t x = (int32_t)(v % g.nx), y = (int32_t)((v / g.nx) % g.ny), z = (int32_t)(v / nxy);
+    if (x > 0 && f[v - 1] == want) return v - 1;
+    if (x < g.nx - 1 && f[v + 1] == want) return v + 1;
+    if (y > 0 && f[v - g.nx] == want) return v - g.nx;
+    if (y < g.ny - 1 && f[v + g.nx] == want) return v + g.nx;
+    if (z > 0 && f[v - nxy] == want) return v - nxy;
+    if (z < g.nz - 1 && f[v + nxy] == want) return v + nxy;
+    return -1;
+}
+
 // free bytes (1 = free) to the bit-packed copy: one wavefront per word, lane b reads voxel 64 wx + b of the row, the ballot is the word
 __global__ __launch_bounds__(256) void k_geo_pack(const uint8_t *__restrict__ free_, WaGeoDims g, unsigned long long *__restrict__ bits)
 {
@@ -43,10 +106,9 @@ __global__ __launch_bounds__(256) void k_geo_seed(const long long *__restrict__ 
     const int32_t s = (int32_t)(blockIdx.x * 256 + threadIdx.x);
     if (s >= n_src) return;
     const long long v = src[s];
-    const long long row = v / g.nx;
-    const int32_t x = (int32_t)(v - row * g.nx);
-    const int64_t w = (int64_t)s * g.nw + row * g.W + (x >> 6);
-    const unsigned long long b = 1ull << (x & 63);
+    int32_t bit;
+    const int64_t w = (int64_t)s * g.nw + geo_word_of(v, g, &bit);
+    const unsigned long long b = 1ull << bit;
     visited[w] = b;
     frontier[w] = b;
     if (field) field[(int64_t)s * g.n + v] = 0;
@@ -76,42 +138,20 @@ __global__ __launch_bounds__(256) void k_geo_level(const unsigned long long *__r
     if (last[s] < level - 1 || stop[s]) return;   // (blocks of this launch may already have stored `level`: never !=)
     const int64_t sb = (int64_t)s * g.nw;
     cur += sb;
-    if (tgt && blockIdx.x == 0) {
-        int32_t *row_out = mat + (int64_t)s * n_tgt;
-        int missing = 0;
-        for (int32_t t = (int32_t)threadIdx.x; t < n_tgt; t += 256) {
-            const long long v = tgt[t];
-            const long long row = v / g.nx;
-            const int32_t x = (int32_t)(v - row * g.nx);
-            if ((cur[row * g.W + (x >> 6)] >> (x & 63)) & 1ull) row_out[t] = level - 1;
-            else if (row_out[t] < 0) missing = 1;
-        }
-        if (!__syncthreads_or(missing) && threadIdx.x == 0) stop[s] = 1;
-    }
+    if (tgt && blockIdx.x == 0) geo_lookup_targets(cur, g, tgt, n_tgt, mat + (int64_t)s * n_tgt, level - 1, stop + s);
     const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (w >= g.nw) return;
     const int64_t row = w / g.W;
     const int32_t wx = (int32_t)(w - row * g.W);
-    const int32_t z = (int32_t)(row / g.ny), y = (int32_t)(row - (int64_t)z * g.ny);
-    const int64_t slab = (int64_t)g.W * g.ny;
-    const unsigned long long c = cur[w];
-    const unsigned long long l = wx > 0 ? cur[w - 1] : 0ull, r = wx < g.W - 1 ? cur[w + 1] : 0ull;
-    const unsigned long long ym = y > 0 ? cur[w - g.W] : 0ull, yp = y < g.ny - 1 ? cur[w + g.W] : 0ull;
-    const unsigned long long zm = z > 0 ? cur[w - slab] : 0ull, zp = z < g.nz - 1 ? cur[w + slab] : 0ull;
+    unsigned long long c;
+    unsigned long long m = geo_neighbours(cur, g, w, row, wx, &c);
     const unsigned long long vis = visited[sb + w];
-    unsigned long long m = ((c << 1) | (l >> 63)) | ((c >> 1) | (r << 63)) | ym | yp | zm | zp;
     m &= freeb[w] & ~vis;
     nxt[sb + w] = m;
     if (m) {
         visited[sb + w] = vis | m;
         last[s] = level;
-        if (field) {
-            int32_t *f = field + (int64_t)s * g.n + row * g.nx + (int64_t)wx * 64;
-            do {
-                f[__builtin_ctzll(m)] = level;
-                m &= m - 1;
-            } while (m);
-        }
+        if (field) geo_store_level(field + (int64_t)s * g.n + row * g.nx + (int64_t)wx * 64, m, level);
     }
 }
 
@@ -140,14 +180,7 @@ __global__ __launch_bounds__(256) void k_geo_walkback(const int32_t *__restrict_
     for (int32_t k = f[v]; k >= 0; k--) {
         o[k] = v;
         if (k == 0) break;
-        const int32_t x = (int32_t)(v % g.nx), y = (int32_t)((v / g.nx) % g.ny), z = (int32_t)(v / nxy);
-        const int32_t want = k - 1;
-        if (x > 0 && f[v - 1] == want) v -= 1;
-        else if (x < g.nx - 1 && f[v + 1] == want) v += 1;
-        else if (y > 0 && f[v - g.nx] == want) v -= g.nx;
-        else if (y < g.ny - 1 && f[v + g.nx] == want) v += g.nx;
-        else if (z > 0 && f[v - nxy] == want) v -= nxy;
-        else if (z < g.nz - 1 && f[v + nxy] == want) v += nxy;
-        else break;
+        v = geo_predecessor(f, g, nxy, v, k - 1);
+        if (v < 0) break;
     }
 }

@@ -73,11 +73,9 @@ __global__ __launch_bounds__(256) void k_wgt_seed(const long long *__restrict__ 
 {
     const int32_t s = (int32_t)(blockIdx.x * 256 + threadIdx.x);
     if (s >= n_src) return;
-    const long long v = src[s];
-    const long long row = v / g.nx;
-    const int32_t x = (int32_t)(v - row * g.nx);
-    const int64_t w = row * g.W + (x >> 6);
-    const unsigned long long b = 1ull << (x & 63);
+    int32_t bit;
+    const int64_t w = geo_word_of(src[s], g, &bit);
+    const unsigned long long b = 1ull << bit;
     touched[(int64_t)s * g.nw + w] = b;
     ring[(int64_t)s * R * g.nw + w] = b;
     last[s] = 0;
@@ -107,43 +105,20 @@ __global__ __launch_bounds__(256) void k_wgt_level(const unsigned long long *__r
     if (last[s] < level - R || stop[s]) return;   // (blocks of this launch may already have stored `level`: never !=)
     unsigned long long *rs = ring + (int64_t)s * R * g.nw;
     const unsigned long long *cur = rs + (int64_t)slot * g.nw;
-    if (tgt && blockIdx.x == 0) {
-        int32_t *row_out = mat + (int64_t)s * n_tgt;
-        int missing = 0;
-        for (int32_t t = (int32_t)threadIdx.x; t < n_tgt; t += 256) {
-            const long long v = tgt[t];
-            const long long row = v / g.nx;
-            const int32_t x = (int32_t)(v - row * g.nx);
-            if ((cur[row * g.W + (x >> 6)] >> (x & 63)) & 1ull) row_out[t] = level;
-            else if (row_out[t] < 0) missing = 1;
-        }
-        if (!__syncthreads_or(missing) && threadIdx.x == 0) stop[s] = 1;
-    }
+    if (tgt && blockIdx.x == 0) geo_lookup_targets(cur, g, tgt, n_tgt, mat + (int64_t)s * n_tgt, level, stop + s);
     const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (w >= g.nw) return;
     const int64_t row = w / g.W;
     const int32_t wx = (int32_t)(w - row * g.W);
-    const int32_t z = (int32_t)(row / g.ny), y = (int32_t)(row - (int64_t)z * g.ny);
-    const int64_t slab = (int64_t)g.W * g.ny;
-    const unsigned long long c = cur[w];
-    const unsigned long long l = wx > 0 ? cur[w - 1] : 0ull, r = wx < g.W - 1 ? cur[w + 1] : 0ull;
-    const unsigned long long ym = y > 0 ? cur[w - g.W] : 0ull, yp = y < g.ny - 1 ? cur[w + g.W] : 0ull;
-    const unsigned long long zm = z > 0 ? cur[w - slab] : 0ull, zp = z < g.nz - 1 ? cur[w + slab] : 0ull;
+    unsigned long long c;
+    unsigned long long T = geo_neighbours(cur, g, w, row, wx, &c);
     const int64_t sw = (int64_t)s * g.nw + w;
     const unsigned long long tch = touched[sw];
-    unsigned long long T = ((c << 1) | (l >> 63)) | ((c >> 1) | (r << 63)) | ym | yp | zm | zp;
     T &= freeb[w] & ~tch;
     const int32_t top = slot == 0 ? W : slot - 1;   // (L + W) mod R
     if (c) {
         last[s] = level;
-        if (field) {
-            int32_t *f = field + (int64_t)s * g.n + row * g.nx + (int64_t)wx * 64;
-            unsigned long long m = c;
-            do {
-                f[__builtin_ctzll(m)] = level;
-                m &= m - 1;
-            } while (m);
-        }
+        if (field) geo_store_level(field + (int64_t)s * g.n + row * g.nx + (int64_t)wx * 64, c, level);
     }
     if (!T) {
         rs[(int64_t)top * g.nw + w] = 0ull;
@@ -192,16 +167,10 @@ __global__ __launch_bounds__(256) void k_wgt_walkback(const int32_t *__restrict_
         }
         cnt++;
         if (D == 0) break;
-        const int32_t x = (int32_t)(v % g.nx), y = (int32_t)((v / g.nx) % g.ny), z = (int32_t)(v / nxy);
         const int32_t want = D - (int32_t)cost[v];
         if (want < 0) break;
-        if (x > 0 && f[v - 1] == want) v -= 1;
-        else if (x < g.nx - 1 && f[v + 1] == want) v += 1;
-        else if (y > 0 && f[v - g.nx] == want) v -= g.nx;
-        else if (y < g.ny - 1 && f[v + g.nx] == want) v += g.nx;
-        else if (z > 0 && f[v - nxy] == want) v -= nxy;
-        else if (z < g.nz - 1 && f[v + nxy] == want) v += nxy;
-        else break;
+        v = geo_predecessor(f, g, nxy, v, want);
+        if (v < 0) break;
         D = want;
     }
     if (!out) len[p] = cnt;

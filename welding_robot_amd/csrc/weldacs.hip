@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <unordered_map>
@@ -171,11 +172,11 @@ struct wa_acs {
     bool ran_before = false, read_since_run = false, chained = false;
 };
 
-static int fail(wa_ctx *c, int code, const char *fmt, const char *a = "")
+static int fail(wa_ctx *c, int code, const char *fmt, const char *a = "", const char *b = "")
 {
     if (c) {
         char buf[512];
-        snprintf(buf, sizeof buf, fmt, a);
+        snprintf(buf, sizeof buf, fmt, a, b);
         c->err = buf;
     }
     return code;
@@ -400,6 +401,20 @@ static hipError_t dalloc(T **p, size_t count)
 {
     return dev_malloc((void **)p, count * sizeof(T));
 }
+// device memory that a call owns for as long as the holder lives: freed when it goes, on every way out of the call
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); return *this; }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { hipFree(p); }
+    hipError_t alloc(size_t count) { hipFree(p); p = nullptr; return dalloc(&p, count); }   // (what it held before is given back first)
+    T *detach() { T *q = p; p = nullptr; return q; }                            // the caller owns it from here
+    operator T *() const { return p; }
+};
 
 // one chunk of class k for a block under construction: from the pool; else from a kept block that nobody asked for (harvested, least
 // recently used first); else created -- pooled chunks of the other classes and cached whole blocks make room when the device is full
