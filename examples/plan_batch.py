@@ -193,6 +193,28 @@ def smooth(ctx, grid, segs, wsegs, rev, fit=None):
     return traj, ok, info
 
 
+def seam_stage(ctx, cost, seed, n_starts):
+    """Order and direction of the seams (points 2k, 2k+1 = seam k) from the endpoint costs.  Start 0 of the search is today's order
+    stage one level up: ACS-TSP on D[s][t] = the cheapest of the four end combinations, every seam left at the end nearer to its
+    successor.  Returns (what goes into the JSON, order, directions)."""
+    m = cost.shape[0] // 2
+    D = cost.reshape(m, 2, m, 2).min(axis=(1, 3))
+    np.fill_diagonal(D, 0.0)
+    tour = api.gtsp_solve(ctx, D, mode=api.RNG_DEV, seed=seed)
+    order0 = [int(e[0]) for e in tour["edges"][0]]
+    dir0 = [int(cost[2 * s:2 * s + 2, 2 * t:2 * t + 2].min(axis=1).argmin() == 0) for s, t in zip(order0, order0[1:] + order0[:1])]
+    r = api.seam_tour(ctx, cost, closed=True, or_len=3, n_starts=n_starts, seed=seed, order0=order0, dir0=dir0)
+    s = r["summary"]
+    info = dict(seams=dict(m=m, acs_tsp=dict(order=order0, dir=dir0, cost=s["start0_cost_q_in"] / api.SEAM_Q, seam_level_cost=float(tour["L"][0])),
+                           searched=dict(order=r["order"].tolist(), dir=r["dir"].tolist(), cost=r["cost"], best_start=s["best_start"],
+                                         n_starts=s["n_starts"], start0_descent_cost=s["start0_cost_q_out"] / api.SEAM_Q,
+                                         passes_total=s["passes_total"], n_capped=s["n_capped"])))
+    if m <= 16:
+        ex = api.seam_tour_exact(ctx, cost, closed=True)
+        info["seams"].update(exact=dict(order=ex["order"].tolist(), dir=ex["dir"].tolist(), cost=ex["cost"]))
+    return info, r["order"].tolist(), r["dir"].tolist()
+
+
 def wait_for_device_memory(ctx, want=0.85, timeout_s=30.0):
     """A process that has just exited may still be giving its device memory back; allocations made meanwhile can end up in
     host-visible memory (measured: the whole run 4x slower).  Wait until most of the device memory is free."""
@@ -240,9 +262,17 @@ def main():
                     help="--retime: coordinate units per s, per s^2 (up), per s^2 (down), per s^2 (lateral), per s where the distance field is <= NEAR_D2 (voxels squared)")
     ap.add_argument("--retime-tick", type=float, default=0.001, help="--retime: the controller period in seconds")
     ap.add_argument("--fit-dump", default=None, help="--fit: write the fitted polyline (n x 3 float32) to this .npy file")
+    ap.add_argument("--seams", action="store_true",
+                    help="points 2k and 2k+1 are the two ends of weld seam k: order AND direction of the seams by wa_gtsp_seam_tour, started from "
+                         "the seam-level ACS-TSP tour; the exact tour beside it up to 16 seams")
+    ap.add_argument("--seam-starts", type=int, default=1024, help="--seams: descents of the local search (start 0 is the ACS-TSP tour)")
     args = ap.parse_args()
     if args.fit is not None and not args.shortcut:
         ap.error("--fit needs the waypoints of --shortcut")
+    if args.seams and (args.points % 2 or args.points < 2):
+        ap.error("--seams needs an even number of --points (two per seam)")
+    if args.seams and (args.fit is not None or args.retime):
+        ap.error("--seams does not go together with --fit / --retime yet")
     rank, local_rank, world = wd.env_rank()
     ctx = api.Context(local_rank)
     comm = None
@@ -327,16 +357,41 @@ def main():
                                  ratio_max=float(np.max(ratios)) if ratios else None, left_at_inf=left))
     if rank == 0 and finite:
         t1 = time.perf_counter()
-        tour = api.gtsp_solve(ctx, cost, mode=api.RNG_DEV, seed=args.seed)
-        out.update(tour_cost=float(tour["L"][0]), tour_iterations=int(tour["iters"][0]),
-                   order=[int(e[0]) for e in tour["edges"][0]], t_gtsp_s=time.perf_counter() - t1,
-                   pair_generations_per_s=out["pairs"] * args.generations / t_pairs)
+        if args.seams:
+            info, order, dirs = seam_stage(ctx, cost, args.seed, args.seam_starts)
+            out.update(info, t_seams_s=time.perf_counter() - t1, pair_generations_per_s=out["pairs"] * args.generations / t_pairs)
+            # every seam is a two-node segment walked in its chosen direction; between two seams the pair path from where the torch
+            # leaves one to where it enters the next (the way back to the first seam is not stitched, as without --seams)
+            ins = [2 * s + x for s, x in zip(order, dirs)]
+            edges = [(a ^ 1, b) for a, b in zip(ins[:-1], ins[1:])]
+            rev = []
+            for k, d in enumerate(dirs):
+                rev.append(int(d))                            # a seam is stored even end first
+                if k < len(edges):
+                    rev.append(1 if edges[k][0] > edges[k][1] else 0)   # pair paths are stored i<j
+
+            def seg_list(table):
+                segs = []
+                for k, s in enumerate(order):
+                    segs.append(np.array([pts[2 * s], pts[2 * s + 1]], np.int64))
+                    if k < len(edges):
+                        a, b = edges[k]
+                        segs.append(table[(min(a, b), max(a, b))])
+                return segs
+        else:
+            tour = api.gtsp_solve(ctx, cost, mode=api.RNG_DEV, seed=args.seed)
+            out.update(tour_cost=float(tour["L"][0]), tour_iterations=int(tour["iters"][0]),
+                       order=[int(e[0]) for e in tour["edges"][0]], t_gtsp_s=time.perf_counter() - t1,
+                       pair_generations_per_s=out["pairs"] * args.generations / t_pairs)
+            edges = tour["edges"][0][:-1]
+            rev = [1 if a > b else 0 for a, b in edges]          # stored i<j; walk them in tour direction
+
+            def seg_list(table):
+                return [table[(min(a, b), max(a, b))] for a, b in edges]
         # main.cpp:283-352: stitch the tour's segments (rank 0 holds every path), then the two smoothing passes, all on the device
         t2 = time.perf_counter()
-        edges = tour["edges"][0][:-1]
-        segs = [paths[(min(a, b), max(a, b))] for a, b in edges]
-        rev = [1 if a > b else 0 for a, b in edges]          # stored i<j; walk them in tour direction
-        wsegs = [short[(min(a, b), max(a, b))] for a, b in edges] if args.shortcut else None
+        segs = seg_list(paths)
+        wsegs = seg_list(short) if args.shortcut else None
         traj, ok, info = smooth(ctx, grid, segs, wsegs, rev, fit=(metal, args.fit, args.fit_dump) if args.fit is not None else None)
         out.update(info, t_trajectory_s=time.perf_counter() - t2)
         if args.retime:
@@ -370,7 +425,7 @@ def main():
                      nodes_within_bands=within(paths[ij] for ij in reach), nodes_within_bands_hop_optimal=within(hop_paths[ij] for ij in reach),
                      nodes_next_to_metal=within((paths[ij] for ij in reach), 1), nodes_next_to_metal_hop_optimal=within((hop_paths[ij] for ij in reach), 1))
             if args.shortcut:
-                hsegs = [hop_paths[(min(a, b), max(a, b))] for a, b in edges]
+                hsegs = seg_list(hop_paths)
                 hw = api.shortcut_paths(grid, hsegs, args.max_span)[0]
                 htraj, hok, _ = smooth(ctx, grid, hsegs, hw, rev)
                 n_hit = lambda t, k: int(api.Trajectory.from_points(ctx, t[k.astype(bool)]).clearance(metal)[3]["n_hit"])

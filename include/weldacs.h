@@ -657,6 +657,50 @@ typedef struct {
 int wa_traj_retime(const wa_grid *g, const wa_traj *t, const wa_retime_limits *lim, const float *v_limit, double tick,
                    int64_t *time_q_out, int64_t *w_q_out, uint8_t *bound_out, wa_traj **ticks_out, wa_retime_summary *sum);
 
+/* ---- seam tours: order and direction of two-ended weld seams (not in the reference: ACS_GTSP orders points) ----
+ * m seams, 2m endpoints: seam s has endpoints 2s and 2s+1.  The torch enters a seam at one end, leaves it at the other and travels to the
+ * next seam; the calls choose the order of the seams and the direction of each so that the travel between seams is short.  Everything
+ * is defined in integers so that the result is the same bytes whatever computes it (DESIGN 4n holds the full text).
+ * 1. Costs.  dist is 2m x 2m doubles, row-major; only i < j is read (and mirrored), the diagonal and the entries (2s, 2s+1) are ignored
+ *    (a seam's own length is constant).  W[i][j] = (int64)rint(dist[i][j] * 2^20), ties to even; every entry read must be finite, >= 0 and
+ *    give W < 2^40.
+ * 2. Open tours.  closed == 0 appends a dummy seam m whose endpoints cost 0 to every endpoint; M = m + 1 (else M = m).  The result is the
+ *    closed tour on M seams with the dummy removed, starting with the seam behind it.  A closed result starts with seam 0.
+ * 3. State.  Positions 0 .. M-1 (taken mod M) hold seam P[k] and direction d[k]: in(k) = 2 P[k] + d[k], out(k) = 2 P[k] + 1 - d[k],
+ *    cost = sum_k W[out(k)][in(k+1)].  dir_out[k] = d[k]: 0 enters seam order_out[k] at its even endpoint.
+ * 4. Moves.  A, Reverse(i, j), 0 <= i <= j <= M-1, j - i <= M-2: positions i..j reversed, their d flipped; number i*M + j.
+ *    B, Move(i, L, g, r), 1 <= L <= min(or_len, M-2), i + L - 1 <= M-1, g outside the block and not i-1 mod M: the block i..i+L-1 leaves
+ *    the array and goes in directly behind the element that stood at g (reversed and flipped when r = 1);
+ *    number M*M + (((i*3 + L-1)*M + g)*2 + r).  A pass evaluates every move, takes the smallest cost change (the lowest number among
+ *    equals) and applies it if it is negative; otherwise the start has ended.  A start also ends after max_passes passes (n_capped).
+ * 5. Starts.  Start 0 is order0 / dir0 (NULL: the identity order / all 0; the dummy stands last).  Start r >= 1 is drawn from a
+ *    splitmix64 stream seeded with seed ^ (r * 0xD1B54A32D192ED03): Fisher-Yates from the identity for k = M-1 .. 1 with
+ *    j = ((draw >> 32) * (k+1)) >> 32, then d[k] = draw >> 63 for k = 0 .. M-1.  The start with the smallest final cost wins, the lowest
+ *    index among equals.
+ * 6. wa_gtsp_seam_tour_exact: the optimum by dynamic programming over subsets, M <= 16 (WA_ERR_CAPACITY above); of equal tours the one that
+ *    backtracking from the end with the lowest endpoint at every step finds, seam 0 first with d = 0 before the open/closed handling.
+ * WA_ERR_ARG, before anything is written: a NULL pointer (order0, dir0, start_cost_q_out, start_passes_out may be NULL), m outside
+ * 1 .. 1024, or_len outside 0 .. 3, n_starts or max_passes outside 1 .. 2^20, an order0 that is no permutation of 0 .. m-1, a dir0 entry
+ * above 1, a cost that breaks rule 1.  order_out / dir_out hold m entries, start_cost_q_out / start_passes_out n_starts entries (host).
+ * Same bytes on every call; everything runs on the context's stream.  (The calls carry the order stage's wa_gtsp_ prefix: they take
+ * a context like wa_gtsp_solve and stand where it stands in the pipeline.) */
+typedef struct {
+    int32_t closed;       /* != 0: the tour returns to its first seam */
+    int32_t or_len;       /* longest block that move B takes, 0 .. 3 (0: reversals only) */
+    int32_t n_starts;     /* 1 .. 2^20 */
+    int32_t max_passes;   /* 1 .. 2^20 per start */
+    uint64_t seed;
+} wa_seam_params;
+typedef struct {
+    int32_t m, M, n_starts, best_start, n_capped;
+    int64_t cost_q;                                /* cost of the returned tour, quanta of 2^-20 */
+    int64_t start0_cost_q_in, start0_cost_q_out;   /* start 0 as given / after its descent */
+    int64_t passes_total;
+} wa_seam_summary;
+int wa_gtsp_seam_tour(wa_ctx *ctx, const double *dist, int32_t m, const wa_seam_params *params, const int32_t *order0, const uint8_t *dir0,
+                 int32_t *order_out, uint8_t *dir_out, int64_t *start_cost_q_out, int32_t *start_passes_out, wa_seam_summary *sum);
+int wa_gtsp_seam_tour_exact(wa_ctx *ctx, const double *dist, int32_t m, int32_t closed, int32_t *order_out, uint8_t *dir_out, int64_t *cost_q);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,15 @@ class RetimeSummary(C.Structure):
                 ("peak_w_q", C.c_int64)]
 
 
+class SeamParams(C.Structure):
+    _fields_ = [("closed", C.c_int32), ("or_len", C.c_int32), ("n_starts", C.c_int32), ("max_passes", C.c_int32), ("seed", C.c_uint64)]
+
+
+class SeamSummary(C.Structure):
+    _fields_ = [("m", C.c_int32), ("M", C.c_int32), ("n_starts", C.c_int32), ("best_start", C.c_int32), ("n_capped", C.c_int32),
+                ("cost_q", C.c_int64), ("start0_cost_q_in", C.c_int64), ("start0_cost_q_out", C.c_int64), ("passes_total", C.c_int64)]
+
+
 # every symbol include/weldacs.h declares: name -> (restype, argtypes)
 _V, _I, _I64, _F, _P = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_void_p
 SYMBOLS = {
@@ -160,6 +169,8 @@ SYMBOLS = {
     "wa_grid_weighted_paths": (C.c_int, [_V, _P, _P, _P, _I, _P, _P, _P, _P]),
     "wa_grid_fit_trajectory": (C.c_int, [_V, _V, _I, _F, _I, _I64, _P, C.POINTER(_V), C.POINTER(_V), C.POINTER(FitSummary)]),
     "wa_traj_retime": (C.c_int, [_V, _V, C.POINTER(RetimeLimits), _P, C.c_double, _P, _P, _P, C.POINTER(_V), C.POINTER(RetimeSummary)]),
+    "wa_gtsp_seam_tour": (C.c_int, [_V, _P, _I, C.POINTER(SeamParams), _P, _P, _P, _P, _P, _P, C.POINTER(SeamSummary)]),
+    "wa_gtsp_seam_tour_exact": (C.c_int, [_V, _P, _I, _I, _P, _P, _P]),
 }
 
 _libs = {}

@@ -778,3 +778,37 @@ def gtsp_solve(ctx, dist, cnt=None, mode=RNG_DEV, seed=1, stream=0, max_iteratio
     ctx.check(ctx.lib.wa_gtsp_solve(ctx.h, _ptr(dist), n, cnt, inst, C.byref(p), _ptr(st), _ptr(edges), _ptr(cost),
                                     _ptr(iters), _ptr(pher)))
     return dict(edges=edges, L=cost, iters=iters, pher=pher, rand_state=st)
+
+
+SEAM_Q = 1 << 20   # quanta per unit of cost in wa_gtsp_seam_tour's integers
+
+
+def seam_tour(ctx, dist, closed=True, or_len=3, n_starts=64, max_passes=1 << 20, seed=1, order0=None, dir0=None):
+    """wa_gtsp_seam_tour: order and direction of m two-ended seams from the 2m x 2m endpoint costs (seam s: endpoints 2s, 2s+1) by a
+    multi-start local search; dir[k] = 0 enters seam order[k] at its even endpoint (Trajectory.stitch's reverse flag is dir[k] = 1)"""
+    dist = np.ascontiguousarray(dist, np.float64)
+    m = dist.shape[0] // 2
+    assert dist.shape == (2 * m, 2 * m), "dist is 2m x 2m"
+    p = L.SeamParams(1 if closed else 0, or_len, n_starts, max_passes, seed)
+    order0 = None if order0 is None else np.ascontiguousarray(order0, np.int32)
+    dir0 = None if dir0 is None else np.ascontiguousarray(dir0, np.uint8)
+    assert (order0 is None or order0.shape == (m,)) and (dir0 is None or dir0.shape == (m,)), "order0 / dir0 hold m entries"
+    order, dirs = np.zeros(m, np.int32), np.zeros(m, np.uint8)
+    n = max(int(n_starts), 0)
+    costs, passes = np.zeros(n, np.int64), np.zeros(n, np.int32)
+    s = L.SeamSummary()
+    ctx.check(ctx.lib.wa_gtsp_seam_tour(ctx.h, _ptr(dist), m, C.byref(p), _ptr(order0), _ptr(dir0), _ptr(order), _ptr(dirs), _ptr(costs),
+                                   _ptr(passes), C.byref(s)))
+    summary = {k: int(getattr(s, k)) for k, _ in L.SeamSummary._fields_}
+    return dict(order=order, dir=dirs, cost_q=summary["cost_q"], cost=summary["cost_q"] / SEAM_Q, start_cost_q=costs, start_passes=passes,
+                summary=summary)
+
+
+def seam_tour_exact(ctx, dist, closed=True):
+    """wa_gtsp_seam_tour_exact: the optimal order and directions, up to 16 seams (15 when open)"""
+    dist = np.ascontiguousarray(dist, np.float64)
+    m = dist.shape[0] // 2
+    assert dist.shape == (2 * m, 2 * m), "dist is 2m x 2m"
+    order, dirs, cost = np.zeros(m, np.int32), np.zeros(m, np.uint8), C.c_int64(0)
+    ctx.check(ctx.lib.wa_gtsp_seam_tour_exact(ctx.h, _ptr(dist), m, 1 if closed else 0, _ptr(order), _ptr(dirs), C.byref(cost)))
+    return dict(order=order, dir=dirs, cost_q=int(cost.value), cost=cost.value / SEAM_Q)

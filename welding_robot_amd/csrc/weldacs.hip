@@ -33,6 +33,7 @@
 #include "weighted_kernels.hpp"
 #include "fit_kernels.hpp"
 #include "retime_kernels.hpp"
+#include "seamtour_kernels.hpp"
 #include "stl_text.hpp"
 
 // ------------------------------------------------------------------ handles
@@ -790,5 +791,6 @@ void *wa_ctx_stream(wa_ctx *c) { return c ? (void *)c->stream : nullptr; }
 #include "host_weighted.inc"
 #include "host_fit.inc"
 #include "host_retime.inc"
+#include "host_seamtour.inc"
 
 }  // extern "C"
