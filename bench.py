@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- ACS generations/sec on the BASELINE workload (config C3 per GPU; C4 across GPUs).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,18 +13,24 @@ generations run on a throw-away search; then EXACTLY K generations of a fresh se
 between barrier + synchronize pairs, inputs already resident in HBM (the per-problem setup --
 pheromone init, heuristic field -- is outside the timed region and reported as setup_ms).
 
+A plain run does what the headline needs and no more: set-up, warm-up, the timed generations, --dump-outputs, the JSON line.  Its
+`roofline` and `kernel_ms_sampled` come from the launches stamped INSIDE the timed region and cost no run of their own.  Everything
+below that is measured or checked beside the headline -- the CPU baseline and `cost_check`, the sweep kernel alone at 128^3 and 256^3,
+the paired and continued roofline samples, the live PMC traffic passes, every extra, the sharded C5 leg -- runs with --full only
+(about half a minute more); --no-cpu, --no-extras and --no-roofline-256 then cut a --full run down again.
+
 Rank 0 prints one JSON line: metric/value (whole-job generations/s), `roofline` for the
-evaporation sweep and -- at N = 1 -- `cpu_baseline`: the reference's own loop (oracle/_ref/ref_harness,
+evaporation sweep and -- with --full at N = 1 -- `cpu_baseline`: the reference's own loop (oracle/_ref/ref_harness,
 kind "reference") or the C oracle (kind "port") timed on this host on a bounded sample.
 
-roofline: the launch of the timed loop that carries the evaporation sweep (ACSRank_3D.hpp:268-272: 48 B of
+roofline (what --full adds to it is marked so): the launch of the timed loop that carries the evaporation sweep (ACSRank_3D.hpp:268-272: 48 B of
 algorithmic traffic per voxel) is `k_evap_rank_mark` -- 4096 sweep blocks + the latency-bound rank / mark blocks of the
 same generation.  Its launches are stamped per dispatch with HIP events on the library's own stream (hipExtLaunchKernelGGL
 start/stop) over the timed region; `achieved` = 48 N^3 / that average, `frac` against the 8 TB/s HBM3E peak; `traffic` = HBM bytes per
-launch from two rocprofv3 PMC child passes of this very run (FETCH_SIZE / WRITE_SIZE; the committed passes when that is not possible).  At 128^3
-both 48 MiB buffers sit in the 256 MiB Infinity Cache, so beside it `sweep_alone` reports the sweep kernel itself
+launch from the committed PMC passes (--full: from two rocprofv3 PMC child passes of this very run, FETCH_SIZE / WRITE_SIZE, when that is possible).  At 128^3
+both 48 MiB buffers sit in the 256 MiB Infinity Cache, so beside it `sweep_alone` (--full) reports the sweep kernel itself
 (`k_evaporate`, 64 stamped launches after the timed region) at 128^3 and at 256^3 (805 MB per launch: past the cache).
-Extras after the timed region, outside `value`: `full_run` (the same search over BASELINE config 3's stated 500
+Extras (--full) after the timed region, outside `value`: `full_run` (the same search over BASELINE config 3's stated 500
 generations), `multi_start` (eight independent searches advancing together on this GPU: config 4's
 workload, with an HBM-resident sweep), `c5_full` (BASELINE config 5 at full size on this GPU), `walk_step` (time per general step of the walk
 against the issue floor of its assembled loop), `c5_pair_planning` (dense vs lazy evaporation, must agree).
@@ -54,12 +60,16 @@ def parse():
     ap.add_argument("--cpu-gens", type=int, default=100, help="generations of the CPU baseline's second sample (window_100) when the timed region is shorter")
     ap.add_argument("--cpu-gens-max", type=int, default=500, help="the CPU baseline runs the timed region's generations, at most this many")
     ap.add_argument("--cost-check-gens", type=int, default=None, help="generations the CPU port replays for cost_check (default: all K)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what is measured or checked beside the headline: the CPU baseline and cost_check, the sweep kernel alone, the paired and "
+                         "continued roofline samples, the live PMC traffic passes, the extras, the sharded C5 leg.  Off: set-up, warm-up, the timed "
+                         "generations, --dump-outputs and the JSON line only")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baseline, no cost_check")
     ap.add_argument("--profile-every", type=int, default=10, help="stamp every n-th generation's launches with HIP events")
     ap.add_argument("--no-extras", action="store_true",
-                    help="warm-up + timed region only: no continuation of the search behind the timed region (roofline samples), no walk_step, no secondary measurements "
+                    help="with --full: no continuation of the search behind the timed region (roofline samples), no walk_step, no secondary measurements "
                          "-- what a rocprofv3 kernel trace of the command should contain (tools/timed_window_stats.py)")
-    ap.add_argument("--no-roofline-256", action="store_true", help="skip the 256^3 (past the Infinity Cache) sweep measurement")
+    ap.add_argument("--no-roofline-256", action="store_true", help="with --full: skip the 256^3 (past the Infinity Cache) sweep measurement")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed region, write what its search returns to a caller (best cost and path, per-generation trace, pheromone "
                          "field) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
@@ -275,7 +285,7 @@ def live_traffic(n, ants, timeout_s=90):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(tmp, counter)
             cmd = ["rocprofv3", "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-                   "--steps", "30", "--warmup", "2", "--no-cpu", "--no-extras", "--no-roofline-256", "--grid", str(n), "--ants", str(ants)]
+                   "--steps", "30", "--warmup", "2", "--grid", str(n), "--ants", str(ants)]   # (a plain run: warm-up + timed region only)
             env = dict(os.environ, WA_BENCH_NO_LIVE_PMC="1", TMPDIR="/tmp")
             for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
                 env.pop(k, None)
@@ -637,6 +647,7 @@ def main():
     ctx = api.Context(local_rank)  # raises if libweldacs.so or the device is missing: no fallback
     mem_wait_s = wait_for_device_memory(ctx)
     n, K, W = args.grid, args.steps, args.warmup
+    extras = args.full and not args.no_extras   # (a plain run enqueues nothing behind its timed region)
     wl = wd.per_rank_workload(rank if args.workload_index is None else args.workload_index)
     free, cx, cy, cz, prec, wall = synth.synth_grid(n, seed=wl["grid_seed"], occ_prob=0.10)
     grid = api.Grid.from_occupancy(ctx, free, cx, cy, cz, prec, wall)
@@ -741,7 +752,7 @@ def main():
         # blocks + the rank / mark blocks), per-dispatch HIP events on the library's stream over the timed region
         fused = dict(prof["evaporate"])
         fused_where = "%d launches of the timed region" % fused["launches"]
-        if fused["launches"] < 32 and not args.no_extras:   # a short timed region: the same search goes on, untimed, every launch stamped, until 32 samples exist
+        if fused["launches"] < 32 and extras:   # a short timed region: the same search goes on, untimed, every launch stamped, until 32 samples exist
             solver.profile(True, 1)
             solver.run(32 - int(fused["launches"]))
             more = solver.profile_read()["evaporate"]
@@ -752,16 +763,16 @@ def main():
         # starts its workgroups 1.2 us slower and reports 1.6-2 us more than the same dispatch behind another event-carrying one -- blocks,
         # clock, L2 and TLB counters unchanged (profiles/r06/sweep_gap.txt).  `paired`: a stamped no-op dispatch in front of each timed launch
         paired_ms = None
-        if not args.no_extras:
+        if extras:
             solver.profile(True, 1, paired=True)
             solver.run(32)
             pp = solver.profile_read()["evaporate"]
             paired_ms = pp["ms"] / max(pp["launches"], 1)
             solver.profile(False, 1)
         # ---- beside it: the sweep kernel on its own, at the BASELINE size and past the Infinity Cache
-        r128 = sweep_roofline(ctx, n)
-        r256 = sweep_roofline(ctx, 256) if not args.no_roofline_256 else None
-        alg_bytes = r128["algorithmic_bytes_per_launch"]  # 6 fp32 read + written per voxel
+        r128 = sweep_roofline(ctx, n) if args.full else None
+        r256 = sweep_roofline(ctx, 256) if args.full and not args.no_roofline_256 else None
+        alg_bytes = 48.0 * n ** 3  # 6 fp32 read + written per voxel
         achieved = alg_bytes / (fused_ms * 1e-3) / 1e9 if fused_ms > 0 else 0.0
         # HBM bytes per launch from the PMC passes committed under profiles/ (bench.py cannot host rocprofv3
         # itself): only quoted for the kernel and size they were measured on
@@ -779,7 +790,7 @@ def main():
             traffic_src = "committed: " + pt["source"]
         except (OSError, KeyError, ValueError):
             pass
-        if world == 1 and not args.no_extras:   # measured in this run when rocprofv3 can wrap a child pass
+        if world == 1 and extras:   # measured in this run when rocprofv3 can wrap a child pass
             lt = live_traffic(n, args.ants)
             if lt is not None:
                 traffic, traffic_src = lt[0], lt[2] + "; sweep_alone.traffic_*: " + (traffic_src or "n/a")
@@ -810,7 +821,7 @@ def main():
                          "note": "at 128^3 both 48 MiB buffers sit in the 256 MiB Infinity Cache: frac is an on-die figure; frac_hbm (= sweep_alone.frac_256: the same sweep "
                                  "on a 256^3 field, 805 MB per launch, non-temporal loads and stores by the library's rule) is the HBM one; multi_start.in_loop_frac is the "
                                  "in-loop HBM figure (eight 128^3 fields per launch)",
-                         "sweep_alone": {"kernel": "k_evaporate, launched alone %d times after the timed region" % r128["launches"],
+                         "sweep_alone": None if r128 is None else {"kernel": "k_evaporate, launched alone %d times after the timed region" % r128["launches"],
                                          "frac_128": r128["achieved"] / HBM_PEAK_GBS, "avg_launch_ms_128": r128["avg_launch_ms"], "traffic_128": traffic_alone,
                                          "frac_256": (r256["achieved"] / HBM_PEAK_GBS) if r256 else None, "traffic_256": traffic_256, "sweep_256": r256},
                          "end_to_end_frac": alg_bytes * (K / elapsed) / 1e9 / HBM_PEAK_GBS},
@@ -825,7 +836,7 @@ def main():
         }
         if dumped is not None:
             out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
-        if world == 1 and not args.no_extras:
+        if world == 1 and extras:
             # the extras stand outside `value`: one that fails is reported under its key and must not cost the line
             def guarded(fn, *a):
                 try:
@@ -844,7 +855,7 @@ def main():
             solver.close()
             out["c5_full"] = guarded(c5_full_extra, ctx)
     c5s = None
-    if comm is not None and (not args.no_extras or os.environ.get("WA_BENCH_C5")):
+    if comm is not None and (extras or os.environ.get("WA_BENCH_C5")):   # (--full, or the leg asked for by name and size)
         # every rank takes part (rank 0 reports): BASELINE config 5 as ONE job over the ranks -- the leg where N GPUs shorten a job (strong
         # scaling); the headline above is C4, one independent search per GPU (weak)
         solver.close() if world > 1 else None
@@ -864,7 +875,7 @@ def main():
         if c5s is not None:
             out["c5_sharded"] = c5s
             out["c5_sharded_ranks"] = c5s.get("ranks") if isinstance(c5s, dict) else None
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             # the CPU leg comes last (the extras before it are host-paced: 0.52-0.84 s for the C5 extra from box to box, whatever runs in front)
             out.update(cpu_baseline(args, free, n, trace, wl, path, K, elapsed * 1e3))
         print(json.dumps(out), flush=True)

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_json_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "60", "--warmup", "4", "--cpu-gens", "100"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "60", "--warmup", "4", "--cpu-gens", "100"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -69,10 +69,33 @@ def test_bench_json_contract():
     assert abs(d["ms_per_step"] * d["value"] / 1e3 - 1.0) < 1e-6
 
 
+def test_a_plain_run_is_the_headline_alone():
+    """without --full: set-up, warm-up, the timed generations and the line.  The headline keys mean what they mean with --full, the roofline
+    figure comes from the launches stamped inside the timed region, and nothing that takes a run of its own is there"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "60", "--warmup", "4"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "acs_generations_per_sec" and d["unit"] == "generations/s" and d["value"] > 100
+    assert d["n_gpus"] == 1 and d["steps"] == 60 and d["warmup"] == 4 and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["ms_per_step"] * d["value"] / 1e3 - 1.0) < 1e-6
+    assert d["best_cost"] > 0 and d["path_nodes"] > 0 and d["stragglers"]["handed_over"] == d["stragglers"]["finished_by_resume_blocks"]
+    rf = d["roofline"]   # the six launches stamped in the timed region, nothing continued or repeated behind it
+    assert rf["kernel"].startswith("k_evap_rank_mark") and rf["sampled_launches"] == 6 and 0.3 < rf["frac"] < 1.0
+    assert rf["algorithmic_bytes_per_launch"] == 48.0 * 128 ** 3 and rf["traffic_source"].startswith("committed:")
+    assert rf["paired"] is None and rf["sweep_alone"] is None and rf["frac_hbm"] is None
+    assert d["kernel_ms_sampled"]["generations"] == [0, 10, 20, 30, 40, 50] and d["kernel_ms_sampled"]["walk"] > 0
+    for k in ("cpu_baseline", "cost_check", "walk_step", "full_run", "ref_mode", "multi_start", "multi_start_curve", "c5_pair_planning",
+              "c5_full", "c5_sharded"):
+        assert k not in d, k
+
+
 def test_a_failing_extra_does_not_cost_the_line():
     """the extras stand outside `value`: when one of them throws (device memory, say), the driver must still get its JSON line, with the
     failure reported under the extra's key"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--no-cpu", "--no-roofline-256"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "10", "--warmup", "2", "--no-cpu", "--no-roofline-256"],
                        capture_output=True, text=True, timeout=600, env=dict(os.environ, WA_BENCH_FAIL="all"))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -91,8 +114,7 @@ def test_dump_outputs_are_the_timed_search_and_repeat_exactly(tmp_path):
     got = []
     for run in ("a", "b"):
         d = tmp_path / run
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "2", "--no-cpu", "--no-extras",
-                            "--no-roofline-256", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "2", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
         assert line["steps"] == 12 and line["ms_per_step"] > 0

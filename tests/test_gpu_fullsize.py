@@ -232,6 +232,6 @@ def test_c5_sharded_leg_with_one_rank_over_real_rccl():
 def test_c4_workload_of_rank_7_on_this_gpu():
     """Rank 7's C4 problem (grid seed 2031, colony seed 12352) run here: the DEV-mode port draws the same numbers, so the
     per-generation best-cost trace must be bit-equal to the CPU's."""
-    d = _bench(["--steps", "60", "--warmup", "2", "--workload-index", "7", "--cpu-gens", "12", "--no-extras"])
+    d = _bench(["--full", "--steps", "60", "--warmup", "2", "--workload-index", "7", "--cpu-gens", "12", "--no-extras"])
     assert "seed 2024+rank" in d["config"]["workload"] and d["cost_check"]["bit_equal_trace"] is True
     assert d["cost_check"]["generations"] == 60 and d["cost_check"]["best_path_equal"] is True and d["cpu_baseline"]["value"] > 0

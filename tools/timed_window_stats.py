@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Cut a rocprofv3 --kernel-trace CSV of `bench.py --steps K --warmup W --no-extras ...` at the TIMED REGION and hold it against the
-JSON line of the same run: with --no-extras the command enqueues W warm-up generations and then K timed ones and
+"""Cut a rocprofv3 --kernel-trace CSV of a plain `bench.py --steps K --warmup W` (no --full) at the TIMED REGION and hold it against the
+JSON line of the same run: a plain run enqueues W warm-up generations and then K timed ones and
 nothing else on the solver, so the timed region is dispatches [W, W + K) of each of the loop's three kernels.  Prints, per kernel, the
 launches / total / average inside the window, the window's span from the first walk's start to the last apply's end, the sum of the
 three kernels against ms_per_step x K, and the roofline figure the window's sweep launches give.
