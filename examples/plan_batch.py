@@ -215,6 +215,40 @@ def seam_stage(ctx, cost, seed, n_starts):
     return info, r["order"].tolist(), r["dir"].tolist()
 
 
+def torch_stage(ctx, metal, xyz, stops, K):
+    """Torch axes along the trajectory's samples (wa_traj_tool_axes): one of K directions of a cone around +z per sample so that a
+    300 mm torch body (24 beads) stays clear of the metal.  Legs: the travel moves between the tour's stops, cut at the sample nearest to
+    each stop.  Wish: the torch points down the gradient of the distance field (at the nearest metal), so the body -- a direction runs
+    from the tip into the body -- is wished along the gradient itself; computed here in numpy.  Beside the plan, the check of the
+    linearly interpolated, renormalised axes half-way between consecutive samples: what a controller that interpolates would send."""
+    curve = api.Trajectory.from_points(ctx, xyz)
+    n = len(xyz)
+    cuts = [0]
+    for p in stops[1:-1]:
+        cuts.append(cuts[-1] + int(np.argmin(np.linalg.norm(xyz[cuts[-1]:] - p, axis=1))))
+    off = np.asarray(cuts + [n], np.int64)
+    ids = curve.clearance(metal)[0]
+    d2 = metal.distance_field().astype(np.float64).reshape(metal.nz, metal.ny, metal.nx)
+    gz, gy, gx = np.gradient(np.sqrt(d2))
+    want = np.stack([gx.ravel()[ids], gy.ravel()[ids], gz.ravel()[ids]], 1).astype(np.float32)
+    want[~np.isfinite(want).all(1)] = 0                          # (a grid without metal: no wish)
+    length16 = int(min(65536, round(16 * 0.3 / float(metal.precision))))
+    tool = api.torch_tool(np.rint(np.linspace(0, length16, 24)).astype(np.int64), np.full(24, 1))
+    dirs = api.torch_cone(K, 1.2)
+    r = curve.torch_axes(metal, dirs, tool, w_near=4, w_want=1, w_turn=8, near_add=8, max_turn=-1, want=want, off=off, feas=False)
+    info = dict(r["summary"], K=K, n_legs=len(off) - 1, directions_used=int(len(set(r["dir"].tolist()))), tool_length16=length16)
+    if n > 1:
+        a = dirs[r["dir"]].astype(np.float64)
+        mid = a[:-1] + a[1:]
+        norm = np.linalg.norm(mid, axis=1, keepdims=True)
+        mid = np.where(norm > 0, mid / np.where(norm > 0, norm, 1), a[:-1])
+        half = api.Trajectory.from_points(ctx, ((xyz[:-1].astype(np.float64) + xyz[1:]) / 2).astype(np.float32))
+        cs = half.torch_check(metal, mid.astype(np.float32), tool, 8)[2]
+        info.update(interpolated=dict(n=cs["n"], n_blocked=cs["n_chosen_blocked"], first_blocked=cs["first_chosen_blocked"],
+                                      n_near=cs["n_chosen_near"]))
+    return info
+
+
 def wait_for_device_memory(ctx, want=0.85, timeout_s=30.0):
     """A process that has just exited may still be giving its device memory back; allocations made meanwhile can end up in
     host-visible memory (measured: the whole run 4x slower).  Wait until most of the device memory is free."""
@@ -266,7 +300,15 @@ def main():
                     help="points 2k and 2k+1 are the two ends of weld seam k: order AND direction of the seams by wa_gtsp_seam_tour, started from "
                          "the seam-level ACS-TSP tour; the exact tour beside it up to 16 seams")
     ap.add_argument("--seam-starts", type=int, default=1024, help="--seams: descents of the local search (start 0 is the ACS-TSP tour)")
+    ap.add_argument("--torch", type=int, nargs="?", const=64, default=None, metavar="K",
+                    help="after --fit or --retime: the torch axis at every sample of the trajectory, one of K directions (1 .. 256) of a cone "
+                         "around +z, so that the torch body clears the metal (wa_traj_tool_axes); prints the summary and the check of the "
+                         "interpolated axes between samples")
     args = ap.parse_args()
+    if args.torch is not None and args.fit is None and not args.retime:
+        ap.error("--torch works on the samples of --fit or --retime")
+    if args.torch is not None and not 1 <= args.torch <= 256:
+        ap.error("--torch takes 1 .. 256 directions")
     if args.fit is not None and not args.shortcut:
         ap.error("--fit needs the waypoints of --shortcut")
     if args.seams and (args.points % 2 or args.points < 2):
@@ -408,6 +450,13 @@ def main():
                                    ticks_clearance=ticks.clearance(metal)[3] if ticks is not None else None,   # (None: more than 2^31 ticks)
                                    limits=dict(v_max=v_max, acc=acc, dec=dec, a_lat=a_lat, v_near=v_near, near_d2=int(near_d2))),
                        t_retime_s=time.perf_counter() - t3)
+        if args.torch is not None:
+            t4 = time.perf_counter()
+            cx, cy, cz = metal.coords()
+            first = np.asarray([(seg[-1] if r else seg[0]) for seg, r in zip(segs, rev)] + [segs[-1][0] if rev[-1] else segs[-1][-1]], np.int64)
+            stops = np.stack([cx[first % metal.nx], cy[(first // metal.nx) % metal.ny], cz[first // (metal.nx * metal.ny)]], 1)
+            out.update(torch=torch_stage(ctx, metal, np.ascontiguousarray(traj[ok.astype(bool)], np.float32), stops, args.torch),
+                       t_torch_s=time.perf_counter() - t4)
         if args.safe_paths:
             # what the soft margin buys and costs, against the hop-optimal paths of the same pairs in the same seam order: steps over
             # the optimum, path nodes inside the outermost band, and (--shortcut) segments of the smoothed curve that cut the metal

@@ -701,6 +701,83 @@ int wa_gtsp_seam_tour(wa_ctx *ctx, const double *dist, int32_t m, const wa_seam_
                  int32_t *order_out, uint8_t *dir_out, int64_t *start_cost_q_out, int32_t *start_passes_out, wa_seam_summary *sum);
 int wa_gtsp_seam_tour_exact(wa_ctx *ctx, const double *dist, int32_t m, int32_t closed, int32_t *order_out, uint8_t *dir_out, int64_t *cost_q);
 
+/* ---- torch axis along a trajectory: which way the torch body may point, sample by sample (not in the reference: Usr_SendToSimulation
+ *      holds alpha, beta, gamma at constants, main.cpp:393-405) ----
+ * t holds n samples, the torch TIP.  The call picks, for every sample, one of K given directions for the torch body so that the body
+ * stays clear of the metal of g and the direction changes little from sample to sample: a shortest path over (sample, direction).
+ * Everything the device sees is an integer, so the result is the same bytes whatever computes it.  "double" is IEEE float64, every
+ * operation rounded on its own (no contraction); rint rounds ties to even; integer division is floor division, >> is arithmetic.
+ * 1. Directions.  A direction points from the tip INTO the torch body.  A float triple (x, y, z) is quantised once, on the host:
+ *    len = sqrt((x*x + y*y) + z*z) in double, q_c = (int32)rint((c / len) * 16384) per component; all three components must be finite
+ *    and len > 0.  The device sees q only.  U(a, b) = ((a_x-b_x)^2 + (a_y-b_y)^2 + (a_z-b_z)^2) >> 10, at most 3 * 2^20: the turn measure.
+ * 2. Tool.  n_beads beads (1 .. WA_TORCH_MAX_BEADS); bead j sits dist16[j] sixteenths of a voxel behind the tip (0 .. 65536) and must
+ *    keep a squared clearance above r2[j] (0 .. 2^30, the voxel-index units of wa_grid_distance_field).  Its offset from the sample's
+ *    voxel is, per axis, o_c = floor((q_c * dist16[j] + 2^17) / 2^18); the sample's voxel comes from the lookup of wa_traj_clearance
+ *    (samples outside the coordinate range are clamped and counted in n_outside).  A bead whose voxel lies outside the grid passes:
+ *    space outside the grid is no obstacle.  Otherwise, with v its voxel: the bead is BLOCKED iff d2[v] <= r2[j]; it is NEAR iff it is
+ *    not blocked, near_add >= 0 and d2[v] <= r2[j] + near_add (near_add <= 2^30; negative: off).  A direction is blocked at a sample iff
+ *    any bead is; near(i, k) = the number of near beads (of all beads, whether or not another one is blocked).  On a grid without
+ *    obstacles d2 is WA_D2_NONE everywhere and nothing is blocked.
+ * 3. Node cost.  N(i, k) = BLOCK * [blocked] + w_near * near(i, k) + w_want * U(q_k, qw_i), BLOCK = 2^36; qw_i = the quantised wish
+ *    want[i]; the wish term is 0 when want is NULL or the triple is all zero.  Weights are 0 .. 1024.
+ * 4. Legs.  off[0 .. n_legs] splits the n samples into independent legs: off[0] = 0, non-decreasing, off[n_legs] = n; empty legs are
+ *    allowed, a leg holds at most 2^22 samples.  pin_first[l] / pin_last[l]: a direction index the leg must start / end with, or -1;
+ *    a NULL array means all -1; the pins of an empty leg are ignored.
+ * 5. Sequence.  Per leg with samples s .. e; every sum saturates at INF = 2^62 (finite sums stay below 2^61 by the bounds above).
+ *    alpha_s(k) = N(s, k), or INF for k != pin_first when that is given.
+ *    alpha_i(k) = N(i, k) + min over k' of (alpha_(i-1)(k') + w_turn * U(q_k', q_k) + BLOCK * [max_turn >= 0 and U(q_k', q_k) > max_turn]);
+ *    back_i(k) = the lowest k' attaining the minimum.  The last state is pin_last if given, else the lowest k minimising alpha_e; the
+ *    sequence follows back from there.  dir_out[i] = the direction index of sample i; leg_cost[l] = alpha_e(last state), 0 for an
+ *    empty leg.  Every transition is finite, so an end pin is always reached finitely from the sample before; leg_cost is INF only
+ *    for a leg of ONE sample whose two pins differ (pin_last wins).  There is always a full sequence: a sample where every direction
+ *    is blocked shows up in the summary, not as an error.
+ * 6. Summary.  n, n_outside; n_blocked_pairs = blocked (sample, direction) pairs; n_no_dir = samples where every direction is blocked;
+ *    n_chosen_blocked = samples whose chosen direction is blocked, first_chosen_blocked the lowest of them (-1: none); n_chosen_near =
+ *    samples whose chosen direction is not blocked and has near >= 1; n_over_turn = chosen transitions inside a leg with max_turn >= 0
+ *    and U > max_turn; max_turn_taken = the largest U of a chosen transition (0 without one); cost = the sum of the leg costs below
+ *    INF, itself saturating at INF.
+ * 7. wa_traj_tool_axes.  dirs: K x 3 floats, 1 <= K <= WA_TORCH_MAX_DIRS; want: n x 3 floats or NULL; dir_out (int32 n), feas_out
+ *    (uint8 n x K: feas_out[i * K + k] = 255 if direction k is blocked at sample i, else near(i, k)) and leg_cost (int64 n_legs) are on
+ *    the host and may be NULL; sum may not.
+ * 8. wa_traj_tool_check applies rule 2 to ONE given axis per sample (axes: n x 3 floats, quantised by rule 1): a caller who
+ *    interpolates between planned key poses has the interpolated poses checked by the very device function the planner uses.
+ *    blocked_out[i] = 0 / 1, near_out[i] = near of that axis (each uint8 n, host, may be NULL).  Its summary treats the given axis as the
+ *    chosen one of a single direction: n, n_outside, n_blocked_pairs = n_no_dir = n_chosen_blocked, first_chosen_blocked,
+ *    n_chosen_near are filled, the other fields are 0.
+ * 9. Errors.  WA_ERR_ARG, before anything is written: a NULL required pointer (g, t, dirs / axes, tool, weights, off, sum), g and t from
+ *    different contexts, K, n_beads, n_legs (< 0), a weight, dist16, r2 or near_add out of range, off that breaks rule 4, a pin outside
+ *    -1 .. K-1, a direction or axis that is not finite or has zero length, a want entry or a coordinate of t that is not finite.
+ *    WA_ERR_CAPACITY: a leg above 2^22 samples, n * K above 2^33 (wa_traj_tool_check: n above 2^33).
+ * Same bytes on every call; everything runs on the context's stream; g and t are not modified.  The feasibility bytes and the back
+ * pointers (n * K bytes each) live in blocks of the context's arena for the duration of the call.
+ * (The C names say "tool", the Python wrappers torch_axes / torch_check: no declaration of this header may carry the name of the
+ * tensor library, which tests/test_abi.py checks letter by letter.) */
+#define WA_TORCH_MAX_DIRS 256
+#define WA_TORCH_MAX_BEADS 64
+#define WA_TORCH_INF ((int64_t)1 << 62)
+typedef struct {
+    int32_t n_beads;                       /* 1 .. WA_TORCH_MAX_BEADS */
+    int32_t dist16[WA_TORCH_MAX_BEADS];    /* sixteenths of a voxel behind the tip, 0 .. 65536 */
+    int32_t r2[WA_TORCH_MAX_BEADS];        /* squared clearance the bead must exceed, 0 .. 2^30 */
+} wa_tool_beads;
+typedef struct {
+    int32_t w_near, w_want, w_turn;        /* 0 .. 1024 */
+    int32_t near_add;                      /* rule 2; < 0: no bead is near */
+    int32_t max_turn;                      /* rule 5; < 0: no turn limit */
+} wa_tool_weights;
+typedef struct {
+    int64_t n, n_outside;
+    int64_t n_blocked_pairs, n_no_dir;
+    int64_t n_chosen_blocked, first_chosen_blocked, n_chosen_near;
+    int64_t n_over_turn, max_turn_taken;
+    int64_t cost;
+} wa_tool_summary;
+int wa_traj_tool_axes(const wa_grid *g, const wa_traj *t, const float *dirs, int32_t K, const wa_tool_beads *tool,
+                       const wa_tool_weights *weights, const float *want, const int64_t *off, int32_t n_legs, const int32_t *pin_first,
+                       const int32_t *pin_last, int32_t *dir_out, uint8_t *feas_out, int64_t *leg_cost, wa_tool_summary *sum);
+int wa_traj_tool_check(const wa_grid *g, const wa_traj *t, const float *axes, const wa_tool_beads *tool, int32_t near_add,
+                        uint8_t *blocked_out, uint8_t *near_out, wa_tool_summary *sum);
+
 #ifdef __cplusplus
 }
 #endif

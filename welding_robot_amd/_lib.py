@@ -63,6 +63,23 @@ class SeamSummary(C.Structure):
                 ("cost_q", C.c_int64), ("start0_cost_q_in", C.c_int64), ("start0_cost_q_out", C.c_int64), ("passes_total", C.c_int64)]
 
 
+TORCH_MAX_DIRS, TORCH_MAX_BEADS, TORCH_INF = 256, 64, 1 << 62
+
+
+class ToolBeads(C.Structure):
+    _fields_ = [("n_beads", C.c_int32), ("dist16", C.c_int32 * TORCH_MAX_BEADS), ("r2", C.c_int32 * TORCH_MAX_BEADS)]
+
+
+class ToolWeights(C.Structure):
+    _fields_ = [("w_near", C.c_int32), ("w_want", C.c_int32), ("w_turn", C.c_int32), ("near_add", C.c_int32), ("max_turn", C.c_int32)]
+
+
+class ToolSummary(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_outside", C.c_int64), ("n_blocked_pairs", C.c_int64), ("n_no_dir", C.c_int64),
+                ("n_chosen_blocked", C.c_int64), ("first_chosen_blocked", C.c_int64), ("n_chosen_near", C.c_int64),
+                ("n_over_turn", C.c_int64), ("max_turn_taken", C.c_int64), ("cost", C.c_int64)]
+
+
 # every symbol include/weldacs.h declares: name -> (restype, argtypes)
 _V, _I, _I64, _F, _P = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_void_p
 SYMBOLS = {
@@ -171,6 +188,9 @@ SYMBOLS = {
     "wa_traj_retime": (C.c_int, [_V, _V, C.POINTER(RetimeLimits), _P, C.c_double, _P, _P, _P, C.POINTER(_V), C.POINTER(RetimeSummary)]),
     "wa_gtsp_seam_tour": (C.c_int, [_V, _P, _I, C.POINTER(SeamParams), _P, _P, _P, _P, _P, _P, C.POINTER(SeamSummary)]),
     "wa_gtsp_seam_tour_exact": (C.c_int, [_V, _P, _I, _I, _P, _P, _P]),
+    "wa_traj_tool_axes": (C.c_int, [_V, _V, _P, _I, C.POINTER(ToolBeads), C.POINTER(ToolWeights), _P, _P, _I, _P, _P, _P, _P, _P,
+                                    C.POINTER(ToolSummary)]),
+    "wa_traj_tool_check": (C.c_int, [_V, _V, _P, C.POINTER(ToolBeads), _I, _P, _P, C.POINTER(ToolSummary)]),
 }
 
 _libs = {}

@@ -682,6 +682,48 @@ class Trajectory:
         summary = {k: (list(getattr(s, k)) if k == "n_bound" else int(getattr(s, k))) for k, _ in L.RetimeSummary._fields_}
         return time_q, w_q, bound, Trajectory(self.ctx, th) if th.value else None, summary
 
+    def torch_axes(self, grid, dirs, tool, w_near=1, w_want=0, w_turn=1, near_add=-1, max_turn=-1, want=None, off=None, pin_first=None,
+                   pin_last=None, feas=True):
+        """wa_traj_tool_axes with these samples as the torch tip: for every sample one of the K directions `dirs` (K x 3, tip -> body) so
+        that the beads of `tool` (torch_tool(dist16, r2), or that pair) stay clear of `grid`'s metal and the direction turns little.
+        `off`: n_legs + 1 offsets of independent legs (None: one leg); want: n x 3 wished directions (zero rows: none).  Returns
+        dict(dir int32[n], feas uint8[n, K] (255 = blocked, else the near beads; None with feas=False), leg_cost int64[n_legs], summary)."""
+        n = len(self)
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        K = len(dirs)
+        tool = tool if isinstance(tool, L.ToolBeads) else torch_tool(*tool)
+        w = L.ToolWeights(w_near, w_want, w_turn, near_add, max_turn)
+        off = np.ascontiguousarray([0, n] if off is None else off, np.int64).reshape(-1)
+        n_legs = len(off) - 1
+        if want is not None:
+            want = np.ascontiguousarray(want, np.float32).reshape(-1, 3)
+            if len(want) != n:
+                raise ValueError("want needs one row per sample")
+        pins = []
+        for p in (pin_first, pin_last):
+            p = None if p is None else np.ascontiguousarray(p, np.int32).reshape(-1)
+            if p is not None and len(p) != n_legs:
+                raise ValueError("pins need one entry per leg")
+            pins.append(p)
+        dir_out, leg_cost = np.empty(n, np.int32), np.empty(max(n_legs, 0), np.int64)
+        feas_out = np.empty((n, K), np.uint8) if feas else None
+        s = L.ToolSummary()
+        self.ctx.check(self.ctx.lib.wa_traj_tool_axes(grid.h, self.h, _ptr(dirs), K, C.byref(tool), C.byref(w), _ptr(want), _ptr(off), n_legs,
+                                                      _ptr(pins[0]), _ptr(pins[1]), _ptr(dir_out), _ptr(feas_out), _ptr(leg_cost), C.byref(s)))
+        return dict(dir=dir_out, feas=feas_out, leg_cost=leg_cost, summary={k: int(getattr(s, k)) for k, _ in L.ToolSummary._fields_})
+
+    def torch_check(self, grid, axes, tool, near_add=-1):
+        """wa_traj_tool_check: one given axis per sample (n x 3) against the same bead rule; (blocked uint8[n], near uint8[n], summary)"""
+        n = len(self)
+        axes = np.ascontiguousarray(axes, np.float32).reshape(-1, 3)
+        if len(axes) != n:
+            raise ValueError("axes needs one row per sample")
+        tool = tool if isinstance(tool, L.ToolBeads) else torch_tool(*tool)
+        blocked, near = np.empty(n, np.uint8), np.empty(n, np.uint8)
+        s = L.ToolSummary()
+        self.ctx.check(self.ctx.lib.wa_traj_tool_check(grid.h, self.h, _ptr(axes), C.byref(tool), near_add, _ptr(blocked), _ptr(near), C.byref(s)))
+        return blocked, near, {k: int(getattr(s, k)) for k, _ in L.ToolSummary._fields_}
+
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.wa_traj_destroy(self.h)
@@ -812,3 +854,38 @@ def seam_tour_exact(ctx, dist, closed=True):
     order, dirs, cost = np.zeros(m, np.int32), np.zeros(m, np.uint8), C.c_int64(0)
     ctx.check(ctx.lib.wa_gtsp_seam_tour_exact(ctx.h, _ptr(dist), m, 1 if closed else 0, _ptr(order), _ptr(dirs), C.byref(cost)))
     return dict(order=order, dir=dirs, cost_q=int(cost.value), cost=cost.value / SEAM_Q)
+
+
+TORCH_INF = L.TORCH_INF   # leg cost of a one-sample leg whose two pins differ (wa_traj_tool_axes, rule 5)
+
+
+def torch_tool(dist16, r2):
+    """the beads of a torch body for Trajectory.torch_axes / torch_check: bead j sits dist16[j] sixteenths of a voxel behind the tip and
+    must keep a squared clearance (voxel-index units) above r2[j]"""
+    dist16, r2 = np.asarray(dist16, np.int64).reshape(-1), np.asarray(r2, np.int64).reshape(-1)
+    if len(dist16) != len(r2) or not 1 <= len(r2) <= L.TORCH_MAX_BEADS:
+        raise ValueError("a tool has 1 .. %d beads, one dist16 and one r2 each" % L.TORCH_MAX_BEADS)
+    if dist16.min() < -2 ** 31 or dist16.max() >= 2 ** 31 or r2.min() < -2 ** 31 or r2.max() >= 2 ** 31:
+        raise ValueError("dist16 and r2 are int32")
+    t = L.ToolBeads()
+    t.n_beads = len(r2)
+    for j in range(len(r2)):
+        t.dist16[j], t.r2[j] = int(dist16[j]), int(r2[j])
+    return t
+
+
+def torch_cone(K, half_angle, axis=(0.0, 0.0, 1.0)):
+    """K unit directions on the spherical cap of `half_angle` radians around `axis`, a Fibonacci spiral from the axis outwards
+    (direction 0 is the axis itself).  The floats are INPUTS of wa_traj_tool_axes, which quantises them: not part of the bit contract."""
+    a = np.asarray(axis, np.float64)
+    a = a / np.linalg.norm(a)
+    helper = np.array([1.0, 0.0, 0.0]) if abs(a[0]) < 0.9 else np.array([0.0, 1.0, 0.0])
+    u = np.cross(a, helper)
+    u /= np.linalg.norm(u)
+    v = np.cross(a, u)
+    k = np.arange(K, dtype=np.float64)
+    cos_t = 1.0 - (1.0 - np.cos(half_angle)) * (k / max(K - 1, 1))
+    sin_t = np.sqrt(np.maximum(0.0, 1.0 - cos_t * cos_t))
+    phi = k * (np.pi * (3.0 - np.sqrt(5.0)))
+    d = cos_t[:, None] * a + (sin_t * np.cos(phi))[:, None] * u + (sin_t * np.sin(phi))[:, None] * v
+    return np.ascontiguousarray(d, np.float32)

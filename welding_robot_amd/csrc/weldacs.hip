@@ -34,6 +34,7 @@
 #include "fit_kernels.hpp"
 #include "retime_kernels.hpp"
 #include "seamtour_kernels.hpp"
+#include "torch_kernels.hpp"
 #include "stl_text.hpp"
 
 // ------------------------------------------------------------------ handles
@@ -792,5 +793,6 @@ void *wa_ctx_stream(wa_ctx *c) { return c ? (void *)c->stream : nullptr; }
 #include "host_fit.inc"
 #include "host_retime.inc"
 #include "host_seamtour.inc"
+#include "host_torch.inc"
 
 }  // extern "C"
