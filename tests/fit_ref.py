@@ -38,16 +38,13 @@ def pieces(xyz, levels, spacing):
 def polygon(xyz, m):
     """(points float32 [sum m + 1, 3], leg of every point)"""
     xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
-    pts, leg = [], []
-    for k, mk in enumerate(m):
-        a, b = xyz[k], xyz[k + 1]
-        t = np.arange(mk, dtype=np.float32) / np.float32(mk)
-        step = (b - a).astype(np.float32)
-        pts.append((a[None, :] + (step[None, :] * t[:, None]).astype(np.float32)).astype(np.float32))
-        leg.append(np.full(mk, k, np.int64))
-    pts.append(xyz[-1:].copy())
-    leg.append(np.array([len(m) - 1], np.int64))
-    return np.concatenate(pts), np.concatenate(leg)
+    m = np.asarray(m, np.int64)
+    first = np.concatenate([[0], np.cumsum(m)])               # the first point of every leg
+    leg = np.repeat(np.arange(len(m), dtype=np.int64), m)
+    t = (np.arange(first[-1], dtype=np.int64) - first[leg]).astype(np.float32) / m[leg].astype(np.float32)
+    step = (xyz[1:] - xyz[:-1]).astype(np.float32)
+    pts = (xyz[leg] + (step[leg] * t[:, None]).astype(np.float32)).astype(np.float32)
+    return np.concatenate([pts, xyz[-1:]]), np.concatenate([leg, [len(m) - 1]])
 
 
 def owners(leg, degree):
@@ -220,3 +217,106 @@ def random_scene(seed):
 RANDOM_SPACING = 8.0
 RANDOM_SAMPLES = 2001
 RANDOM_SEEDS = [0, 2, 4, 6, 9, 14, 15, 16, 19, 21, 23, 26, 27, 30, 31, 32, 34, 35, 39, 1, 3, 5, 7, 8]
+
+
+# ------------------------------------------------------------------ polylines of many legs: the scan of the piece counts beyond one block
+def _serpentine(n):
+    """corner points of a boustrophedon through the voxels 1 .. n - 2 of an n^3 grid: rows along x one voxel apart in y, layers one voxel
+    apart in z; it never comes back to a voxel it has left"""
+    lo, hi = 1.0, float(n - 2)
+    out = []
+    fx = fy = True
+    for z in range(1, n - 1):
+        for y in (range(1, n - 1) if fy else range(n - 2, 0, -1)):
+            out.append((lo if fx else hi, y, z))
+            out.append((hi if fx else lo, y, z))
+            fx = not fx
+        fy = not fy
+    return np.array(out, np.float64)
+
+
+def many_legs_scene(n_legs, marks=(), seed=0, unit=1.0, zero_from=None, long_every=0, long_len=0.0):
+    """(free, d2, dims, axes, xyz) with exactly n_legs legs: polyline points at growing arc length along a serpentine through a 48^3 grid
+    (64^3 where 48^3 is too short for it), unit axes.  Leg k is `unit` times a length uniform in 0.05 .. 2.2 (at spacing == unit: m_k in
+    1, 2, 3, differing between neighbours); about 2 % of the legs, in runs of 1 .. 5, have zero length (both ends the same fp32 point).
+    zero_from: every leg from that index on has zero length.  long_every / long_len: every long_every-th leg (not leg 0) is long_len
+    long instead.  The grid is free except for the voxel of polyline point k (the first point of leg k) for every k in marks: the
+    control polygon keeps a point inside the metal there at every level, so the legs around k are blamed until they reach the cap."""
+    rs = np.random.RandomState(seed)
+    ln = rs.uniform(0.05, 2.2, n_legs) * unit
+    k = 0
+    while k < n_legs:                                           # runs of zero-length legs: 0.7 % starts x 3 legs on average
+        if rs.uniform() < 0.007:
+            run = int(rs.randint(1, 6))
+            ln[k:k + run] = 0.0
+            k += run
+        k += 1
+    if long_every:
+        ln[long_every::long_every] = long_len
+    if zero_from is not None:
+        ln[zero_from:] = 0.0
+    s = np.concatenate([[0.0], np.cumsum(ln)])
+    for n in (48, 64):
+        corners = _serpentine(n)
+        at = np.concatenate([[0.0], np.cumsum(np.abs(np.diff(corners, axis=0)).sum(1))])
+        if s[-1] <= at[-1]:
+            break
+    assert s[-1] <= at[-1], "the polyline does not fit into the grid"
+    xyz = np.stack([np.interp(s, at, corners[:, c]) for c in range(3)], 1).astype(np.float32)
+    assert len(xyz) == n_legs + 1
+    dims = (n, n, n)
+    axes = unit_axes(dims)
+    free = np.ones(n ** 3, np.uint8)
+    for k in marks:
+        x, y, z = (CR.axis_node(axes[c], xyz[k, c])[0] for c in range(3))
+        free[(z * n + y) * n + x] = 0
+    return scene(free, dims, xyz, axes)
+
+
+def block_marks(n_legs):
+    """the legs the block tests mark: either side of a wave's and a block's edge, and the last leg"""
+    return sorted({k for k in (0, 63, 64, 255, 256, 257, 511, 512, n_legs - 1) if k < n_legs})
+
+
+def pass_marks(n_legs):
+    """the legs the scan-pass tests mark: block_marks, either side of the 65 536th leg (256 blocks of 256: where k_fit_scan_sums starts
+    its second trip), of the block behind it and of the third trip, and the last leg"""
+    return sorted({k for k in (0, 63, 64, 255, 256, 257, 65535, 65536, 65537, 65792, 131071, 131072, n_legs - 1) if k < n_legs})
+
+
+# Leg counts around one block of 256 legs (spacing 1, max_level 2, BLOCK_SAMPLES samples) and around one trip of 256 blocks (spacing 1,
+# max_level 1, about as many samples as legs, so that a sample segment stays local and the blame does not creep).
+# CPU time of the reference, fit() alone, as tests/test_fit_rules.py prints it: 0.3 to 0.5 s for every entry of BLOCK_LEGS and degree
+# (3 rounds each), 0.6 s for "zero_tail" (3 rounds), 1.6 s for "long_legs" (10 rounds); 7.9, 7.0, 7.2, 6.7 and 14.5 s for the five
+# entries of PASS_LEGS (2 rounds each: round 1 hits at every mark, round 2 finds the same legs at the cap and raises nothing).
+BLOCK_LEGS = [63, 64, 65, 255, 256, 257, 511, 512, 513, 1025]
+BLOCK_SAMPLES = 3001
+PASS_LEGS = [65535, 65536, 65537, 65793, 131073]          # 131 073: a third trip of the block-sum scan
+_many = {}
+
+
+def many_legs_case(name, degree=3):
+    """(scene, (degree, spacing, max_level, n_samples), reference result) of a named many-legs case; computed once per process, shared
+    by tests/test_fit_rules.py and tests/test_gpu_fit.py, never modified"""
+    key = (name, degree)
+    if key not in _many:
+        if name == "zero_tail":            # every leg behind the first 300 has zero length: m_k = 1, off[k] = k, one leg per emit lane
+            n_legs = 1500
+            sc = many_legs_scene(n_legs, [0, 100, 299, 300, n_legs - 1], 5, zero_from=300)
+            par = (degree, 1.0, 2, BLOCK_SAMPLES)
+        elif name == "long_legs":          # seven legs of up to 40 voxels (m_k = 400 .. 4000 at spacing 0.01) between stretches of m_k in 1, 2, 3
+            n_legs = 700
+            sc = many_legs_scene(n_legs, [0, 96, 97, 98, 300, 388, 389, n_legs - 1], 6, unit=0.01, long_every=97, long_len=40.0)
+            par = (degree, 0.01, 2, BLOCK_SAMPLES)
+        elif name < 65535:
+            sc = many_legs_scene(name, block_marks(name), name)
+            par = (degree, 1.0, 2, BLOCK_SAMPLES)
+        else:
+            sc = many_legs_scene(name, pass_marks(name), name)
+            par = (degree, 1.0, 1, name + 4464)
+        import time
+        t0 = time.process_time()
+        r = fit(*sc, *par)
+        r["cpu_seconds"] = time.process_time() - t0
+        _many[key] = (sc, par, r)
+    return _many[key]

@@ -115,3 +115,44 @@ def test_seed_list_makes_the_loop_work():
     assert len(F.RANDOM_SEEDS) >= 20 and len(set(F.RANDOM_SEEDS)) == len(F.RANDOM_SEEDS)
     worked = sum(_scene_result(s)[1]["n_hit_first"] > 0 for s in F.RANDOM_SEEDS)
     assert 2 * worked >= len(F.RANDOM_SEEDS), worked
+
+
+# ------------------------------------------------------------------ polylines of many legs (fit_ref.many_legs_scene)
+# What tests/test_gpu_fit.py compares on the device must exercise what it is there for: hits in round 1, a second round, raised legs
+# behind the first block of 256 legs (behind the first trip of 256 blocks for the large ones) and at the very end, legs at the cap, and
+# piece counts that differ (a constant m_k would hide a shifted prefix).
+MANY = [(n, d) for n in F.BLOCK_LEGS for d in (2, 3)] + [(n, 3) for n in F.PASS_LEGS] + [("zero_tail", 3), ("long_legs", 3)]
+
+
+@pytest.mark.parametrize("case", MANY, ids=lambda c: "%s-%d" % c)
+def test_many_legs_scene_exercises_the_scan(case):
+    name, degree = case
+    (free, d2, dims, axes, xyz), (_, spacing, max_level, n_samples), r = F.many_legs_case(name, degree)
+    n_legs = len(xyz) - 1
+    print("[fit] many legs %s, degree %d: %d legs, %d samples, %d rounds, %d control points, reference %.1f s of CPU"
+          % (name, degree, n_legs, n_samples, r["rounds"], r["n_cps"], r["cpu_seconds"]))
+    assert n_legs == (name if isinstance(name, int) else n_legs) == r["n_legs"] and dims[0] in (48, 64) and int((free == 0).sum()) > 0
+    assert n_samples >= n_legs or n_legs < 65535                # large scenes: a sample segment stays local
+    raised = np.flatnonzero(r["levels"] > 0)
+    assert r["n_hit_first"] > 0 and r["rounds"] >= 2 and r["rounds"] < F.MAX_ROUNDS
+    assert len(raised) > 0 and raised.max() >= n_legs - 64      # one in the last 64 legs
+    if n_legs > 256:
+        assert (raised >= 256).any()
+    if n_legs > 65536:
+        assert (raised >= 65536).any()
+    if n_legs > 131072:
+        assert (raised >= 131072).any()
+    assert r["n_legs_at_cap"] > 0 and r["max_level_used"] == max_level
+    m = F.pieces(xyz, np.zeros(n_legs, np.int64), spacing)
+    # m_k = 1, 2, 3 with shares of about 0.46, 0.46, 0.08: neighbours differ with probability 1 - sum p^2 = 0.57 (+- 0.06 at 63 legs)
+    assert len(np.unique(m)) >= 3 and (np.diff(m[:300]) != 0).mean() > 0.3
+    zero = F.leg_lengths(xyz) == 0.0
+    if name == "zero_tail":
+        assert zero[300:].all() and (m[300:] == 1).all() and r["n_cps"] >= n_legs
+    else:
+        assert 0.01 <= zero.mean() <= 0.035 or n_legs < 1000     # about 2 % ...
+        if n_legs >= 1000:
+            assert (zero[1:] & zero[:-1]).any()                  # ... some of them in a row
+    if name == "long_legs":
+        assert (m >= 400).sum() == 7 and (m >= 1000).sum() >= 4 and np.median(m) <= 2   # (a long leg round a turn is a shorter chord)
+    assert r["cpu_seconds"] < 60.0

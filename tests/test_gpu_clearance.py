@@ -82,6 +82,30 @@ def test_edt_long_rows_and_the_int32_bound(ctx):
         g.inflate(1.0)
 
 
+def _rows_with_gaps(nx):
+    """occupied x per row (y = 0, 1) of a row of 6 chunks of 64 voxels and 5 more: where the row pass has to look ahead over chunks
+    that hold no obstacle, or finds none at all"""
+    return [("last partial chunk only", [[nx - 1, nx - 4], [nx - 5]]),
+            ("chunks 0 and 5 only", [[3, 5 * 64 + 60], [63, 5 * 64]]),
+            ("x = 63 and x = 64 only", [[63, 64], [63, 64]]),
+            ("chunk 3 only", [[3 * 64, 3 * 64 + 63], [3 * 64 + 31]]),
+            ("one row empty", [[], [10, 200, nx - 1]]),
+            ("the other row empty", [[2 * 64 + 1, 4 * 64 + 63], []])]
+
+
+@pytest.mark.parametrize("nz", [1, 2])
+@pytest.mark.parametrize("case", _rows_with_gaps(64 * 6 + 5), ids=lambda c: c[0])
+def test_edt_rows_with_empty_chunks(ctx, case, nz):
+    nx, ny = 64 * 6 + 5, 2
+    free = np.ones((nz, ny, nx), np.uint8)
+    for y, xs in enumerate(case[1]):
+        free[0, y, xs] = 0                                     # (nz = 2: layer 1 stays empty, its rows see only the layer below)
+    free = free.ravel()
+    g = grid_of(ctx, free, nx, ny, nz)
+    assert np.array_equal(g.distance_field(), R.edt_brute(free, nx, ny, nz))
+    g.close()
+
+
 @pytest.mark.parametrize("n", [128, 256])
 def test_edt_synth_grid_at_size(ctx, n):
     free, cx, cy, cz, p, wall = synth.synth_grid(n)

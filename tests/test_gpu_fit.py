@@ -229,6 +229,73 @@ def test_refusals_leave_outputs_untouched(ctx):
     other.close()
 
 
+# ------------------------------------------------------------------ leg counts beyond one block, and beyond one trip of the block-sum scan
+# The piece counts are scanned in three kernels: per block of 256 legs (k_fit_pieces), over the block sums 256 at a time with a carry
+# (k_fit_scan_sums), and added back (k_fit_scan_add, whose lane k == n_legs lies in a block of its own when 256 divides n_legs).
+# tests/test_fit_rules.py pins on the CPU that every scene here hits, refines and reaches the cap behind those boundaries.
+def _many(ctx, name, degree):
+    scene, par, r = F.many_legs_case(name, degree)
+    _same(ctx, scene, *par, ref=r)
+    return r
+
+
+@pytest.mark.parametrize("degree", [2, 3])
+@pytest.mark.parametrize("n_legs", F.BLOCK_LEGS)
+def test_leg_counts_around_the_block(ctx, n_legs, degree):
+    _many(ctx, n_legs, degree)
+
+
+@pytest.mark.parametrize("n_legs", F.PASS_LEGS)
+def test_leg_counts_around_the_second_scan_pass(ctx, n_legs):
+    r = _many(ctx, n_legs, 3)
+    assert (np.flatnonzero(r["levels"]) >= min(n_legs - 64, 65536)).any()
+
+
+def test_one_leg_per_emit_lane(ctx):
+    """every leg behind the first 300 has zero length: m_k = 1, off[k] = k, every lane of an emit wave belongs to another leg; the
+    curve rests inside the metal there, so all those legs are blamed and raised together (full ballots in k_fit_bump)"""
+    r = _many(ctx, "zero_tail", 3)
+    assert (r["levels"][300:] == 2).all()
+
+
+def test_long_legs_between_short_ones(ctx):
+    """legs of hundreds to thousands of pieces between stretches of 1 .. 3: an emit wave lies inside one leg or spans dozens"""
+    _many(ctx, "long_legs", 3)
+
+
+def test_capacity_refusal_in_a_later_round(ctx):
+    """diagonal_graze is blamed at every level.  At a spacing where level 0 takes 2^22 - 1 pieces, rounds 1 and 2 fit (2^23 + 3 control
+    points in round 2) and round 3 would need 2^24 - 4 pieces = 2^24 + 1 cubic control points: refused there, with a spline and all
+    buffers already allocated, and nothing handed out."""
+    scene = F.diagonal_graze()
+    xyz = scene[4]
+    spacing = np.float32(F.leg_lengths(xyz)[0] / 2.0 ** 22)
+    while F.pieces(xyz, [0], spacing)[0] >= 1 << 22 or F.pieces(xyz, [2], spacing)[0] + 5 <= F.MAX_CPS:
+        spacing = np.nextafter(spacing, np.float32(1.0))
+    m = [int(F.pieces(xyz, [lv], spacing)[0]) for lv in range(3)]
+    assert m[0] == (1 << 22) - 1 and m[1] + 5 <= F.MAX_CPS and m[2] <= F.MAX_CPS < m[2] + 5, m
+    g = grid_of(ctx, scene)
+    poly = api.Trajectory.from_points(ctx, xyz)
+    # capped at level 1 the same spacing is served: two rounds, both hit
+    b, samples, levels, s = poly.fit(g, 3, float(spacing), 1, 601)
+    assert (s["rounds"], s["n_cps"], s["n_legs_at_cap"], s["n_hit_first"], s["final"]["n_hit"]) == (2, m[1] + 5, 1, 1, 1) and levels.tolist() == [1]
+    samples.close()
+    b.close()
+    for max_level in (2, 6):
+        lv = np.full(8, -7, np.int32)
+        bh, th = C.c_void_p(0x1234), C.c_void_p(0x5678)
+        fs = L.FitSummary()
+        fs.rounds = -9
+        fs.n_cps = -9
+        rc = ctx.lib.wa_grid_fit_trajectory(g.h, poly.h, 3, C.c_float(spacing), max_level, 601, lv.ctypes.data, C.byref(bh), C.byref(th),
+                                            C.byref(fs))
+        assert rc == 1 and b"wa_grid_fit_trajectory: more than 2^24 control points" in ctx.lib.wa_last_error(ctx.h)
+        assert (lv == -7).all() and bh.value == 0x1234 and th.value == 0x5678 and fs.rounds == -9 and fs.n_cps == -9
+    poly.close()
+    r, _ = _same(ctx, F.l_corner(long=True), 3, 8.0, 6, 601)
+    assert r["rounds"] > 1
+
+
 # ------------------------------------------------------------------ the cubic demo's golden tour
 def _golden_tour_polyline(reverse):
     """(scene, waypoint ids) of the golden tour's segments, each shortened with span 128 on the cubic grid (shortcut_ref)"""

@@ -133,6 +133,22 @@ def test_batch_equals_single_calls(ctx):
         assert np.array_equal(p[seg[:cnt[k]]], wps[k]) and (seg[cnt[k]:] == -7).all()
 
 
+@pytest.mark.parametrize("n_paths", [255, 256, 257, 513])
+def test_more_paths_than_one_block(ctx, n_paths):
+    """k_sc_chain runs one lane per path: batches either side of one and two blocks of 256 lanes, empty paths among them"""
+    rs = np.random.RandomState(n_paths)
+    dims = (16, 12, 10)
+    free = (rs.uniform(size=int(np.prod(dims))) >= 0.15).astype(np.uint8)
+    g = grid_of(ctx, free, *dims)
+    lens = rs.randint(0, 41, n_paths)
+    lens[[0, 63, 64, n_paths - 2]] = 0                            # empty paths at a wave's edges and next to the last lane
+    lens[[255, n_paths - 1] if n_paths > 255 else [n_paths - 1]] = 40
+    paths = [_walk(rs, free, dims, int(ln), nb) for ln, nb in zip(lens, [6, 26] * n_paths)]
+    assert len(paths) == n_paths and sum(len(p) == 0 for p in paths) >= 4
+    wps, _ = _same(ctx, g, free, paths, 128, {})
+    assert any(0 < len(w) < len(p) for p, w in zip(paths[256:], wps[256:])) or n_paths <= 256   # something shortened behind block 0
+
+
 def test_refusals(ctx):
     n = 6
     g = grid_of(ctx, np.ones(n ** 3, np.uint8), n, n, n)
