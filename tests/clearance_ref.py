@@ -142,3 +142,18 @@ def clearance(free, d2, nx, ny, nz, cx, cy, cz, xyz):
     summ = {"min_d2": int(sd.min()) if n else D2_NONE, "argmin": int(np.argmin(sd)) if n else -1,
             "first_hit": int(np.flatnonzero(hits)[0]) if hits.any() else -1, "n_hit": int(hits.sum()), "n_outside": int(n_out)}
     return ids, sd.astype(np.int32), hits, summ
+
+
+def shuffled_scene():
+    """a 23 x 17 x 11 grid with 8 % metal whose tables take every path of the lookup -- x stretched, y shuffled (not monotone: the
+    scan), z with a duplicated last node, as at a seam -- and 300 samples on nodes, between them and outside.
+    Returns (free, dims, (cx, cy, cz), xyz)."""
+    rs = np.random.RandomState(9)
+    nx, ny, nz = 23, 17, 11
+    free = (rs.uniform(size=nx * ny * nz) >= 0.08).astype(np.uint8)
+    cx = (np.arange(nx) * 0.25 - 1).astype(np.float32)
+    cy = rs.permutation(np.arange(ny)).astype(np.float32) * np.float32(0.5)
+    cz = np.concatenate([np.arange(nz - 1), [nz - 2]]).astype(np.float32)
+    xyz = np.stack([rs.uniform(-1.5, 5, 300), rs.uniform(-1, 9, 300), rs.uniform(-1, 11, 300)], 1).astype(np.float32)
+    xyz[::7] = np.stack([cx[rs.randint(0, nx, len(xyz[::7]))], cy[rs.randint(0, ny, len(xyz[::7]))], cz[rs.randint(0, nz, len(xyz[::7]))]], 1)
+    return free, (nx, ny, nz), (cx, cy, cz), xyz

@@ -239,15 +239,8 @@ def test_traj_hand_cases(ctx):
 
 
 def test_traj_random_vs_restatement(ctx):
-    rs = np.random.RandomState(9)
-    nx, ny, nz = 23, 17, 11
-    free = (rs.uniform(size=nx * ny * nz) >= 0.08).astype(np.uint8)
-    cx = (np.arange(nx) * 0.25 - 1).astype(np.float32)
-    cy = rs.permutation(np.arange(ny)).astype(np.float32) * np.float32(0.5)     # not monotone: the scan path
-    cz = np.concatenate([np.arange(nz - 1), [nz - 2]]).astype(np.float32)      # a duplicated last node, as at a seam
+    free, (nx, ny, nz), (cx, cy, cz), xyz = R.shuffled_scene()
     g = grid_of(ctx, free, nx, ny, nz, cx, cy, cz)
-    xyz = np.stack([rs.uniform(-1.5, 5, 300), rs.uniform(-1, 9, 300), rs.uniform(-1, 11, 300)], 1).astype(np.float32)
-    xyz[::7] = np.stack([cx[rs.randint(0, nx, len(xyz[::7]))], cy[rs.randint(0, ny, len(xyz[::7]))], cz[rs.randint(0, nz, len(xyz[::7]))]], 1)
     s = _check(ctx, g, free, xyz)
     assert 0 < s["n_hit"] < len(xyz) - 1 and s["n_outside"] > 0
 

@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import clearance_ref as CR
 import fit_ref as F
 import retime_ref as R
 from welding_robot_amd import _lib as L
@@ -93,6 +94,14 @@ def test_slab_scene_near_the_metal(ctx):
     out[:7, 1] = -3.0
     r, _ = _same(ctx, out, R.limits(v_max=2.0, acc=4.0, dec=4.0, v_near=0.25, near_d2=9), grid=grid)
     assert r["summary"]["n_outside"] == 7
+
+
+def test_shuffled_axis_tables(ctx):
+    """every other grid here has unit axes; clearance_ref's shuffled scene has a stretched x table, a shuffled y table (the lookup's
+    scan) and a repeated last z node, and samples outside the tables' range"""
+    free, dims, axes, xyz = CR.shuffled_scene()
+    r, _ = _same(ctx, xyz, R.limits(v_max=2, acc=4, dec=4, v_near=0.25, near_d2=2), grid=R.make_grid(free, dims, axes), tick=0.01)
+    assert r["summary"]["n_outside"] > 0 and r["summary"]["n_bound"][3] > 0
 
 
 @pytest.mark.parametrize("seed", R.RANDOM_SEEDS)

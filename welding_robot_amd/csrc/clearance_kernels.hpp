@@ -165,27 +165,52 @@ __device__ inline int32_t clr_axis_node(const float *__restrict__ c, int32_t n, 
     return a;
 }
 
+// per axis: the table's smallest and largest value, and whether the table is non-decreasing
 struct WaClrAxes {
     float lo[3], hi[3];
     int32_t mono[3];
 };
 
+// The grid as something a sample is looked up in: its dims, axis tables with their ranges, and its distance field.  One kernel
+// argument, filled by the host's grid_field(); all zero when a call has no grid (k_rt_caps).
+struct WaField {
+    WaDims d;
+    const float *cx, *cy, *cz;
+    WaClrAxes A;
+    const int32_t *d2;
+};
+
+// The voxel of a point: the nearest node per axis, and its id.  *outside is set when a coordinate lies outside its table's range
+// (never cleared).  The one lookup of wa_traj_clearance, the fit, wa_traj_retime and the torch axis.
+__device__ inline int3 field_voxel(const WaField &F, float px, float py, float pz, int64_t *id, bool *outside)
+{
+    int3 v;
+    v.x = clr_axis_node(F.cx, F.d.nx, F.A.lo[0], F.A.hi[0], F.A.mono[0], px, outside);
+    v.y = clr_axis_node(F.cy, F.d.ny, F.A.lo[1], F.A.hi[1], F.A.mono[1], py, outside);
+    v.z = clr_axis_node(F.cz, F.d.nz, F.A.lo[2], F.A.hi[2], F.A.mono[2], pz, outside);
+    *id = (int64_t)v.z * F.d.nxy + (int64_t)v.y * F.d.nx + v.x;
+    return v;
+}
+
+// the start value of the summary's accumulator acc[4] (k_clr_samples, k_clr_segments): min key, first hit, n_hit, n_outside
+__host__ __device__ inline void clr_acc_init(unsigned long long acc[4])
+{
+    acc[0] = ~0ull; acc[1] = ~0ull; acc[2] = 0; acc[3] = 0;
+}
+
 // one lane per sample: its voxel, the field there, and the summary's sample terms (min d2 with its lowest index, packed as
 // d2 << 33 | index into one atomicMin; samples outside the coordinate range)
-__global__ __launch_bounds__(256) void k_clr_samples(const float *__restrict__ xyz, int64_t n, WaDims d, const float *__restrict__ cx,
-                                                     const float *__restrict__ cy, const float *__restrict__ cz, WaClrAxes A,
-                                                     const int32_t *__restrict__ d2, long long *__restrict__ ids, int32_t *__restrict__ d2s,
+__global__ __launch_bounds__(256) void k_clr_samples(const float *__restrict__ xyz, int64_t n, WaField F, long long *__restrict__ ids,
+                                                     int32_t *__restrict__ d2s,
                                                      unsigned long long *__restrict__ acc /* [0] min key, [3] n_outside */)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long key = ~0ull, outs = 0;
     if (i < n) {
         bool out = false;
-        const int32_t x = clr_axis_node(cx, d.nx, A.lo[0], A.hi[0], A.mono[0], xyz[3 * i], &out);
-        const int32_t y = clr_axis_node(cy, d.ny, A.lo[1], A.hi[1], A.mono[1], xyz[3 * i + 1], &out);
-        const int32_t z = clr_axis_node(cz, d.nz, A.lo[2], A.hi[2], A.mono[2], xyz[3 * i + 2], &out);
-        const int64_t id = (int64_t)z * d.nxy + (int64_t)y * d.nx + x;
-        const int32_t v = d2[id];
+        int64_t id;
+        field_voxel(F, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], &id, &out);
+        const int32_t v = F.d2[id];
         ids[i] = id;
         d2s[i] = v;
         key = ((unsigned long long)(uint32_t)v << 33) | (unsigned long long)i;

@@ -171,7 +171,7 @@ __global__ void k_fit_ends(const float *__restrict__ xyz, long long n_legs, WaSp
         owner[j] = 0;
         owner[S.n_cps - 1 - j] = (int32_t)(n_legs - 1);
     }
-    rec->acc[0] = ~0ull; rec->acc[1] = ~0ull; rec->acc[2] = 0; rec->acc[3] = 0;
+    clr_acc_init(rec->acc);
     rec->changed = 0;
     rec->at_cap = 0;
 }

@@ -2,19 +2,13 @@
 // (included by weldacs.hip inside extern "C").  Everything between the arguments and the results stays on the device, on the
 // context's stream; per round the host reads one WaFitRec (the next fit's size, the hit count, whether a level changed).
 struct FitBuffers {
-    int32_t *level = nullptr, *owner = nullptr, *d2 = nullptr;
-    uint8_t *mark = nullptr, *hit = nullptr;
-    long long *off = nullptr, *bsum = nullptr, *ids = nullptr;
-    WaFitRec *rec = nullptr;
-    wa_traj *samples = nullptr;
-    wa_bspline *b = nullptr;
+    DevBuf<int32_t> level, owner, d2;
+    DevBuf<uint8_t> mark, hit;
+    DevBuf<long long> off, bsum, ids;
+    DevBuf<WaFitRec> rec;
+    OwnedHandle<wa_traj> samples;
+    OwnedHandle<wa_bspline> b;
     long long cap_cps = 0;
-    ~FitBuffers()
-    {
-        hipFree(level); hipFree(owner); hipFree(d2); hipFree(mark); hipFree(hit); hipFree(off); hipFree(bsum); hipFree(ids); hipFree(rec);
-        wa_traj_destroy(samples);
-        wa_bspline_destroy(b);
-    }
 };
 
 // pieces at the current levels, scanned: off[0 .. n_legs], rec->total
@@ -32,7 +26,7 @@ static hipError_t fit_pieces(wa_ctx *ctx, const wa_traj *poly, FitBuffers &B, do
 static hipError_t fit_spline_room(wa_ctx *ctx, FitBuffers &B, int32_t degree, long long n_cps)
 {
     if (!B.b) {
-        B.b = new wa_bspline();
+        B.b.reset(new wa_bspline());
         B.b->ctx = ctx;
         B.b->S.knots = nullptr; B.b->S.cps = nullptr; B.b->S.uninit = 0.0f;
         B.b->d_ends = nullptr;
@@ -44,13 +38,13 @@ static hipError_t fit_spline_room(wa_ctx *ctx, FitBuffers &B, int32_t degree, lo
     S.n_middle = n_cps - 2 * degree;              // BSplineBasic.h:40
     S.n_knots = n_cps + degree + 1;               // :38-39
     if (n_cps <= B.cap_cps) return hipSuccess;
-    hipFree(S.knots); hipFree(S.cps); hipFree(B.owner);
-    S.knots = nullptr; S.cps = nullptr; B.owner = nullptr;
+    hipFree(S.knots); hipFree(S.cps);   // (the spline's own: it grows by half)
+    S.knots = nullptr; S.cps = nullptr;
     B.cap_cps = 0;
     const long long cap = std::min(n_cps + n_cps / 2, (long long)WA_FIT_MAX_CPS);
     hipError_t e = dalloc(&S.knots, (size_t)(cap + degree + 1));
     e = e ? e : dalloc(&S.cps, (size_t)cap * 3);
-    e = e ? e : dalloc(&B.owner, (size_t)cap);
+    e = e ? e : B.owner.alloc((size_t)cap);
     if (e == hipSuccess && !B.b->d_ends) e = dalloc(&B.b->d_ends, (size_t)(2 * degree) * 3);
     if (e == hipSuccess) B.cap_cps = cap;
     return e;
@@ -72,25 +66,25 @@ int wa_grid_fit_trajectory(const wa_grid *g, const wa_traj *poly, int32_t degree
     if (n_samples < 2 || n_samples > ((int64_t)1 << 33)) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: n_samples must be 2..2^33");
     const long long n_legs = poly->n - 1;
     if (n_legs > WA_FIT_MAX_CPS) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: more than 2^24 control points");
-    int rc = grid_build_d2(g);
-    if (rc) return rc;
-    WaClrAxes A;
-    rc = clr_axes(g, &A);
+    WaField F;
+    int rc = grid_field(g, &F);
     if (rc) return rc;
 
     FitBuffers B;
     const long long n_seg = n_samples - 1;
-    hipError_t e = dalloc(&B.level, (size_t)n_legs);
-    e = e ? e : dalloc(&B.mark, (size_t)n_legs);
-    e = e ? e : dalloc(&B.off, (size_t)n_legs + 1);
-    e = e ? e : dalloc(&B.bsum, (size_t)((n_legs + 255) / 256));
-    e = e ? e : dalloc(&B.rec, 1);
-    e = e ? e : dalloc(&B.ids, (size_t)n_samples);
-    e = e ? e : dalloc(&B.d2, (size_t)n_samples);
-    e = e ? e : dalloc(&B.hit, (size_t)n_seg);
+    hipError_t e = B.level.alloc((size_t)n_legs);
+    e = e ? e : B.mark.alloc((size_t)n_legs);
+    e = e ? e : B.off.alloc((size_t)n_legs + 1);
+    e = e ? e : B.bsum.alloc((size_t)((n_legs + 255) / 256));
+    e = e ? e : B.rec.alloc(1);
+    e = e ? e : B.ids.alloc((size_t)n_samples);
+    e = e ? e : B.d2.alloc((size_t)n_samples);
+    e = e ? e : B.hit.alloc((size_t)n_seg);
     if (e != hipSuccess) return fail(ctx, WA_ERR_ALLOC, "wa_grid_fit_trajectory: device buffers");
-    rc = traj_alloc(ctx, n_samples, &B.samples);
+    wa_traj *samples = nullptr;
+    rc = traj_alloc(ctx, n_samples, &samples);
     if (rc) return rc;
+    B.samples.reset(samples);
     e = hipMemsetAsync(B.level, 0, sizeof(int32_t) * n_legs, ctx->stream);
     e = e ? e : hipMemsetAsync(B.mark, 0, (size_t)n_legs, ctx->stream);
     e = e ? e : hipMemsetAsync(B.rec, 0, sizeof(WaFitRec), ctx->stream);
@@ -118,11 +112,10 @@ int wa_grid_fit_trajectory(const wa_grid *g, const wa_traj *poly, int32_t degree
         k_fit_knots<<<(unsigned)((S.n_knots + 255) / 256), 256, 0, ctx->stream>>>(S, fin_time);
         k_fit_ends<<<1, 64, 0, ctx->stream>>>(poly->xyz, n_legs, S, B.b->d_ends, fin_time, B.owner, B.rec);
         e = hipGetLastError();
-        e = e ? e : bspline_launch(B.b, nullptr, 0.0f, dt, n_samples, 0, B.samples->xyz, nullptr);
+        e = e ? e : bspline_launch(B.b.get(), nullptr, 0.0f, dt, n_samples, 0, B.samples->xyz, nullptr);
         if (e == hipSuccess) {
-            k_clr_samples<<<(unsigned)((n_samples + 255) / 256), 256, 0, ctx->stream>>>(B.samples->xyz, n_samples, g->d, g->cx, g->cy, g->cz, A, g->d2,
-                                                                                       B.ids, B.d2, B.rec->acc);
-            k_clr_segments<<<(unsigned)((n_seg + 255) / 256), 256, 0, ctx->stream>>>(B.ids, n_samples, g->d, g->occ, B.hit, B.rec->acc);
+            k_clr_samples<<<(unsigned)((n_samples + 255) / 256), 256, 0, ctx->stream>>>(B.samples->xyz, n_samples, F, B.ids, B.d2, B.rec.p->acc);
+            k_clr_segments<<<(unsigned)((n_seg + 255) / 256), 256, 0, ctx->stream>>>(B.ids, n_samples, g->d, g->occ, B.hit, B.rec.p->acc);
             if (degree == 2) k_fit_blame<2><<<(unsigned)((n_seg + 255) / 256), 256, 0, ctx->stream>>>(S, B.hit, n_seg, dt, B.owner, B.mark);
             else k_fit_blame<3><<<(unsigned)((n_seg + 255) / 256), 256, 0, ctx->stream>>>(S, B.hit, n_seg, dt, B.owner, B.mark);
             k_fit_bump<<<(unsigned)((n_legs + 255) / 256), 256, 0, ctx->stream>>>(B.level, B.mark, n_legs, max_level, last ? 0 : 1, B.rec);
@@ -139,11 +132,7 @@ int wa_grid_fit_trajectory(const wa_grid *g, const wa_traj *poly, int32_t degree
     }
     s.n_legs_at_cap = rec.at_cap;
     s.n_cps = B.b->S.n_cps;
-    s.final.min_d2 = (int32_t)(rec.acc[0] >> 33);
-    s.final.argmin = (int64_t)(rec.acc[0] & ((1ull << 33) - 1));
-    s.final.first_hit = rec.acc[1] == ~0ull ? -1 : (int64_t)rec.acc[1];
-    s.final.n_hit = (int64_t)rec.acc[2];
-    s.final.n_outside = (int64_t)rec.acc[3];
+    clr_summary_from(rec.acc, &s.final);
     std::vector<int32_t> lv((size_t)n_legs);
     e = hipMemcpy(lv.data(), B.level, sizeof(int32_t) * n_legs, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_grid_fit_trajectory: %s", hipGetErrorString(e));
@@ -151,9 +140,8 @@ int wa_grid_fit_trajectory(const wa_grid *g, const wa_traj *poly, int32_t degree
     if (leg_level_out) memcpy(leg_level_out, lv.data(), sizeof(int32_t) * n_legs);
     B.b->set = true;
     B.b->h_valid = false;
-    *spline_out = B.b;
-    B.b = nullptr;
-    if (samples_out) { *samples_out = B.samples; B.samples = nullptr; }
+    *spline_out = B.b.release();
+    if (samples_out) *samples_out = B.samples.release();
     *sum = s;
     return WA_OK;
 }

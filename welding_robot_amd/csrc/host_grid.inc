@@ -114,8 +114,8 @@ int wa_grid_from_mesh(wa_ctx *ctx, const float *tris, int64_t n_tris, float prec
     wa_grid *g = nullptr;
     int rc = grid_alloc(ctx, dims[0], dims[1], dims[2], ax[0].data(), ax[1].data(), ax[2].data(), precision, wall, &g);
     if (rc) return rc;
-    float *d_tris = nullptr;
-    if (dalloc(&d_tris, (size_t)n_tris * 12)) { wa_grid_destroy(g); return fail(ctx, WA_ERR_ALLOC, "triangle buffer"); }
+    DevBuf<float> d_tris;
+    if (d_tris.alloc((size_t)n_tris * 12)) { wa_grid_destroy(g); return fail(ctx, WA_ERR_ALLOC, "triangle buffer"); }
     hipError_t ve = hipMemcpyAsync(d_tris, tris, sizeof(float) * 12 * n_tris, hipMemcpyHostToDevice, ctx->stream);
     if (ve == hipSuccess) {
         if (env_int("WA_VOXELIZE_DENSE", 0)) {   // the O(T*N^3) form, kept for comparison
@@ -125,13 +125,12 @@ int wa_grid_from_mesh(wa_ctx *ctx, const float *tris, int64_t n_tris, float prec
             ve = hipMemsetAsync(g->occ, 1, (size_t)g->d.n, ctx->stream);
             for (int64_t t0 = 0; ve == hipSuccess && t0 < n_tris; t0 += 1 << 20) {
                 const int64_t cnt = n_tris - t0 < (1 << 20) ? n_tris - t0 : (1 << 20);
-                k_voxelize_clip<<<dim3((unsigned)cnt, 4), 256, 0, ctx->stream>>>(d_tris + t0 * 12, cnt, precision, g->d, g->cx, g->cy, g->cz, g->occ);
+                k_voxelize_clip<<<dim3((unsigned)cnt, 4), 256, 0, ctx->stream>>>(d_tris.p + t0 * 12, cnt, precision, g->d, g->cx, g->cy, g->cz, g->occ);
             }
         }
         ve = ve ? ve : hipGetLastError();
     }
     if (ve == hipSuccess) ve = hipStreamSynchronize(ctx->stream);
-    hipFree(d_tris);
     if (ve != hipSuccess) { wa_grid_destroy(g); return fail(ctx, WA_ERR_DEVICE, "voxelise: %s", hipGetErrorString(ve)); }
     rc = grid_count_free(g);
     if (rc) { wa_grid_destroy(g); return rc; }
@@ -254,12 +253,12 @@ int wa_grid_resolve_points(const wa_grid *g, const float *pts_xyz, int32_t n_pts
         for (int32_t i = 0; i < n_pts; i++) ids_out[i] = resolve_on_host(g, pts_xyz + 3 * (size_t)i);
         return WA_OK;
     }
-    float *d_pts = nullptr;
-    long long *d_ids = nullptr;
+    DevBuf<float> d_pts;
+    DevBuf<long long> d_ids;
     std::vector<long long> h(n_pts);
-    hipError_t e = dalloc(&d_pts, (size_t)n_pts * 3);
-    e = e ? e : dalloc(&d_ids, (size_t)n_pts);
-    if (e != hipSuccess) { hipFree(d_pts); hipFree(d_ids); return fail(ctx, WA_ERR_ALLOC, "resolve buffers"); }
+    hipError_t e = d_pts.alloc((size_t)n_pts * 3);
+    e = e ? e : d_ids.alloc((size_t)n_pts);
+    if (e != hipSuccess) return fail(ctx, WA_ERR_ALLOC, "resolve buffers");
     e = hipMemcpyAsync(d_pts, pts_xyz, sizeof(float) * 3 * n_pts, hipMemcpyHostToDevice, ctx->stream);
     e = e ? e : hipMemsetAsync(d_ids, 0xff, sizeof(long long) * n_pts, ctx->stream);  // -1
     if (e == hipSuccess) {
@@ -273,8 +272,6 @@ int wa_grid_resolve_points(const wa_grid *g, const float *pts_xyz, int32_t n_pts
     }
     e = e ? e : hipMemcpyAsync(h.data(), d_ids, sizeof(long long) * n_pts, hipMemcpyDeviceToHost, ctx->stream);
     e = e ? e : hipStreamSynchronize(ctx->stream);
-    hipFree(d_pts);
-    hipFree(d_ids);
     if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_grid_resolve_points: %s", hipGetErrorString(e));
     for (int32_t i = 0; i < n_pts; i++) ids_out[i] = h[i];
     return WA_OK;

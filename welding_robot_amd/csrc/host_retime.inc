@@ -2,18 +2,12 @@
 // inside extern "C").  Everything between the arguments and the results stays on the device, on the context's stream; the host reads
 // ONE WaRtRec (sums, counters, what was refused), sizes the tick buffer from it and launches the ticks.
 struct RetimeBuffers {
-    long long *A = nullptr, *D = nullptr, *C = nullptr, *F = nullptr, *B = nullptr, *T = nullptr, *time_q = nullptr;
-    uint8_t *kind = nullptr, *bound = nullptr;
-    float *v_limit = nullptr;
-    RtPair *scratch = nullptr;
-    WaRtRec *rec = nullptr;
-    wa_traj *ticks = nullptr;
-    ~RetimeBuffers()
-    {
-        hipFree(A); hipFree(D); hipFree(C); hipFree(F); hipFree(B); hipFree(T); hipFree(time_q); hipFree(kind); hipFree(bound);
-        hipFree(v_limit); hipFree(scratch); hipFree(rec);
-        wa_traj_destroy(ticks);
-    }
+    DevBuf<long long> A, D, C, F, B, T, time_q;
+    DevBuf<uint8_t> kind, bound;
+    DevBuf<float> v_limit;
+    DevBuf<RtPair> scratch;
+    DevBuf<WaRtRec> rec;
+    OwnedHandle<wa_traj> ticks;
 };
 
 static long long rt_scratch_pairs(long long n)
@@ -52,29 +46,20 @@ int wa_traj_retime(const wa_grid *g, const wa_traj *t, const wa_retime_limits *l
     const double tq = rint(tick * WA_RT_Q);
     if (!(tq >= 1.0 && tq <= (double)WA_RT_CAP)) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: tick must be 2^-30 .. 2^31 seconds");
     const long long tick_q = (long long)tq;
-    WaClrAxes ax = {};
-    WaDims dims = {};
+    WaField field = {};   // (no grid: all zero)
     if (g) {
-        int rc = grid_build_d2(g);
+        int rc = grid_field(g, &field);
         if (rc) return rc;
-        rc = clr_axes(g, &ax);
-        if (rc) return rc;
-        dims = g->d;
     }
 
     RetimeBuffers R;
-    hipError_t e = dalloc(&R.A, (size_t)n);
-    e = e ? e : dalloc(&R.D, (size_t)n);
-    e = e ? e : dalloc(&R.C, (size_t)n);
-    e = e ? e : dalloc(&R.F, (size_t)n);
-    e = e ? e : dalloc(&R.B, (size_t)n);
-    e = e ? e : dalloc(&R.T, (size_t)n);
-    e = e ? e : dalloc(&R.time_q, (size_t)n);
-    e = e ? e : dalloc(&R.kind, (size_t)n);
-    e = e ? e : dalloc(&R.bound, (size_t)n);
-    e = e ? e : dalloc(&R.scratch, (size_t)rt_scratch_pairs(n));
-    e = e ? e : dalloc(&R.rec, 1);
-    if (v_limit) e = e ? e : dalloc(&R.v_limit, (size_t)n);
+    hipError_t e = hipSuccess;
+    for (DevBuf<long long> *b : {&R.A, &R.D, &R.C, &R.F, &R.B, &R.T, &R.time_q}) e = e ? e : b->alloc((size_t)n);
+    e = e ? e : R.kind.alloc((size_t)n);
+    e = e ? e : R.bound.alloc((size_t)n);
+    e = e ? e : R.scratch.alloc((size_t)rt_scratch_pairs(n));
+    e = e ? e : R.rec.alloc(1);
+    if (v_limit) e = e ? e : R.v_limit.alloc((size_t)n);
     if (e != hipSuccess) return fail(ctx, WA_ERR_ALLOC, "wa_traj_retime: device buffers");
     e = hipMemsetAsync(R.rec, 0, sizeof(WaRtRec), ctx->stream);
     if (v_limit) e = e ? e : hipMemcpyAsync(R.v_limit, v_limit, sizeof(float) * n, hipMemcpyHostToDevice, ctx->stream);
@@ -85,8 +70,7 @@ int wa_traj_retime(const wa_grid *g, const wa_traj *t, const wa_retime_limits *l
     dl.curv = std::isfinite(lim->a_lat) && lim->a_lat != 0.0;
     if (e == hipSuccess) {
         k_rt_segments<<<blocks, 256, 0, ctx->stream>>>(t->xyz, n, dl.acc, dl.dec, R.A, R.D, R.rec);
-        k_rt_caps<<<blocks, 256, 0, ctx->stream>>>(t->xyz, n, dl, R.v_limit, g ? 1 : 0, dims, g ? g->cx : nullptr, g ? g->cy : nullptr,
-                                                   g ? g->cz : nullptr, ax, g ? g->d2 : nullptr, R.C, R.kind, R.rec);
+        k_rt_caps<<<blocks, 256, 0, ctx->stream>>>(t->xyz, n, dl, R.v_limit, field, R.C, R.kind, R.rec);
         e = hipGetLastError();
     }
     const RtSamples fwd = {R.A, R.C, R.F, n, 0}, bwd = {R.D, R.F, R.B, n, 1}, tim = {R.T, nullptr, R.time_q, n, 0};
@@ -120,8 +104,10 @@ int wa_traj_retime(const wa_grid *g, const wa_traj *t, const wa_retime_limits *l
     s.peak_w_q = rec.peak;
     const bool too_many = s.n_ticks > ((int64_t)1 << 31);
     if (ticks_out && !too_many) {
-        int rc = traj_alloc(ctx, s.n_ticks, &R.ticks);
+        wa_traj *ticks = nullptr;
+        int rc = traj_alloc(ctx, s.n_ticks, &ticks);
         if (rc) return rc;
+        R.ticks.reset(ticks);
         k_rt_ticks<<<(unsigned)((s.n_ticks + 255) / 256), 256, 0, ctx->stream>>>(t->xyz, n, dl.acc, dl.dec, R.B, R.time_q, tick_q, n_full,
                                                                                  s.n_ticks, R.ticks->xyz);
         e = hipGetLastError();
@@ -132,7 +118,7 @@ int wa_traj_retime(const wa_grid *g, const wa_traj *t, const wa_retime_limits *l
     if (bound_out) e = e ? e : hipMemcpyAsync(bound_out, R.bound, (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
     e = e ? e : hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_traj_retime: %s", hipGetErrorString(e));
-    if (ticks_out) { *ticks_out = R.ticks; R.ticks = nullptr; }
+    if (ticks_out) *ticks_out = R.ticks.release();
     *sum = s;
     if (too_many) return fail(ctx, WA_ERR_CAPACITY, "wa_traj_retime: more than 2^31 ticks");
     return WA_OK;

@@ -1,25 +1,6 @@
 // host_seamtour.inc -- C ABI: wa_gtsp_seam_tour / wa_gtsp_seam_tour_exact, order and direction of two-ended weld seams (DESIGN §4n; included by
 // weldacs.hip inside extern "C").  The host checks and quantises the costs (the only floating-point step), the device does the rest in
 // integers on the context's stream; device blocks come from and go back to the context's memory cache.
-extern "C++" {   // (templates: the file is included inside extern "C")
-struct StBuf {   // a device block of the call, returned to the context on every way out (the stream has been waited for by then)
-    wa_ctx *ctx;
-    void *p = nullptr;
-    explicit StBuf(wa_ctx *c) : ctx(c) {}
-    StBuf(const StBuf &) = delete;
-    StBuf &operator=(const StBuf &) = delete;
-    ~StBuf()
-    {
-        if (p) {
-            hipStreamSynchronize(ctx->stream);
-            ctx_free(ctx, p);
-        }
-    }
-    hipError_t alloc(size_t bytes) { return ctx_alloc_bytes(ctx, &p, bytes); }
-    template <class T> T *as() const { return (T *)p; }
-};
-}
-
 static const double WA_ST_Q = 1048576.0;   // 2^20 quanta per unit of cost
 
 // W (2M x 2M, symmetric, zero on the diagonal, within a seam and on the dummy's rows) from the upper triangle of dist (2m x 2m)
@@ -117,29 +98,34 @@ int wa_gtsp_seam_tour(wa_ctx *ctx, const double *dist, int32_t m, const wa_seam_
     const bool w_lds = wave || (narrow && w_narrow + state <= lds_max);
     const size_t lds = state + (w_lds ? (narrow ? w_narrow : w_wide) : 0);
 
-    StBuf dW(ctx), dE0(ctx), dCost(ctx), dPass(ctx), dCap(ctx), dTours(ctx);
+    CtxBuf<unsigned char> dW(ctx);   // uint32_t or long long entries
+    CtxBuf<uint16_t> dE0(ctx);
+    CtxBuf<long long> dCost(ctx);
+    CtxBuf<int32_t> dPass(ctx);
+    CtxBuf<uint8_t> dCap(ctx);
+    CtxBuf<uint16_t> dTours(ctx);
     hipError_t e = dW.alloc((size_t)N2 * N2 * (narrow ? 4 : 8));
-    e = e ? e : dE0.alloc(sizeof(uint16_t) * M);
-    e = e ? e : dCost.alloc(sizeof(long long) * n_starts);
-    e = e ? e : dPass.alloc(sizeof(int32_t) * n_starts);
+    e = e ? e : dE0.alloc((size_t)M);
+    e = e ? e : dCost.alloc((size_t)n_starts);
+    e = e ? e : dPass.alloc((size_t)n_starts);
     e = e ? e : dCap.alloc((size_t)n_starts);
-    e = e ? e : dTours.alloc(sizeof(uint16_t) * (size_t)n_starts * M);
+    e = e ? e : dTours.alloc((size_t)n_starts * M);
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, WA_ERR_ALLOC, "wa_gtsp_seam_tour: device buffers"); }
     std::vector<uint32_t> W32;
     if (narrow) {
         W32.resize(W.size());
         for (size_t k = 0; k < W.size(); k++) W32[k] = (uint32_t)W[k];
-        e = hipMemcpyAsync(dW.p, W32.data(), W32.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+        e = hipMemcpyAsync(dW, W32.data(), W32.size() * 4, hipMemcpyHostToDevice, ctx->stream);
     } else {
-        e = hipMemcpyAsync(dW.p, W.data(), W.size() * 8, hipMemcpyHostToDevice, ctx->stream);
+        e = hipMemcpyAsync(dW, W.data(), W.size() * 8, hipMemcpyHostToDevice, ctx->stream);
     }
-    e = e ? e : hipMemcpyAsync(dE0.p, e0.data(), sizeof(uint16_t) * M, hipMemcpyHostToDevice, ctx->stream);
+    e = e ? e : hipMemcpyAsync(dE0, e0.data(), sizeof(uint16_t) * M, hipMemcpyHostToDevice, ctx->stream);
     WaStArgs a;
-    a.W = dW.p;
-    a.e0 = dE0.as<uint16_t>();
+    a.W = dW;
+    a.e0 = dE0;
     a.M = M; a.or_len = prm->or_len; a.n_starts = n_starts; a.max_passes = prm->max_passes;
     a.seed = prm->seed;
-    a.cost = dCost.as<long long>(); a.passes = dPass.as<int32_t>(); a.capped = dCap.as<uint8_t>(); a.tours = dTours.as<uint16_t>();
+    a.cost = dCost; a.passes = dPass; a.capped = dCap; a.tours = dTours;
     if (e == hipSuccess) {
         if (wave) e = narrow ? st_launch<uint32_t, true, 64>(ctx, a, lds) : st_launch<long long, true, 64>(ctx, a, lds);
         else if (w_lds) e = st_launch<uint32_t, true, 256>(ctx, a, lds);
@@ -148,9 +134,9 @@ int wa_gtsp_seam_tour(wa_ctx *ctx, const double *dist, int32_t m, const wa_seam_
     std::vector<int64_t> cost((size_t)n_starts);
     std::vector<int32_t> passes((size_t)n_starts);
     std::vector<uint8_t> capped((size_t)n_starts);
-    e = e ? e : hipMemcpyAsync(cost.data(), dCost.p, sizeof(int64_t) * n_starts, hipMemcpyDeviceToHost, ctx->stream);
-    e = e ? e : hipMemcpyAsync(passes.data(), dPass.p, sizeof(int32_t) * n_starts, hipMemcpyDeviceToHost, ctx->stream);
-    e = e ? e : hipMemcpyAsync(capped.data(), dCap.p, (size_t)n_starts, hipMemcpyDeviceToHost, ctx->stream);
+    e = e ? e : hipMemcpyAsync(cost.data(), dCost, sizeof(int64_t) * n_starts, hipMemcpyDeviceToHost, ctx->stream);
+    e = e ? e : hipMemcpyAsync(passes.data(), dPass, sizeof(int32_t) * n_starts, hipMemcpyDeviceToHost, ctx->stream);
+    e = e ? e : hipMemcpyAsync(capped.data(), dCap, (size_t)n_starts, hipMemcpyDeviceToHost, ctx->stream);
     e = e ? e : hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_gtsp_seam_tour: %s", hipGetErrorString(e));
     wa_seam_summary s;
@@ -165,7 +151,7 @@ int wa_gtsp_seam_tour(wa_ctx *ctx, const double *dist, int32_t m, const wa_seam_
     s.start0_cost_q_in = st_cost(W, e0.data(), M);
     s.start0_cost_q_out = cost[0];
     std::vector<uint16_t> best((size_t)M);
-    e = hipMemcpyAsync(best.data(), dTours.as<uint16_t>() + (size_t)s.best_start * M, sizeof(uint16_t) * M, hipMemcpyDeviceToHost, ctx->stream);
+    e = hipMemcpyAsync(best.data(), dTours.p + (size_t)s.best_start * M, sizeof(uint16_t) * M, hipMemcpyDeviceToHost, ctx->stream);
     e = e ? e : hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_gtsp_seam_tour: %s", hipGetErrorString(e));
     st_emit(best.data(), m, M, order_out, dir_out);
@@ -193,17 +179,17 @@ int wa_gtsp_seam_tour_exact(wa_ctx *ctx, const double *dist, int32_t m, int32_t 
     int64_t opt = 0;
     if (n > 0) {
         const size_t cells = ((size_t)1 << n) * ne;
-        StBuf dW(ctx), dF(ctx);
-        hipError_t e = dW.alloc(sizeof(int64_t) * W.size());
-        e = e ? e : dF.alloc(sizeof(int64_t) * cells);
+        CtxBuf<long long> dW(ctx), dF(ctx);
+        hipError_t e = dW.alloc(W.size());
+        e = e ? e : dF.alloc(cells);
         if (e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, WA_ERR_ALLOC, "wa_gtsp_seam_tour_exact: device buffers"); }
-        e = hipMemcpyAsync(dW.p, W.data(), sizeof(int64_t) * W.size(), hipMemcpyHostToDevice, ctx->stream);
+        e = hipMemcpyAsync(dW, W.data(), sizeof(int64_t) * W.size(), hipMemcpyHostToDevice, ctx->stream);
         for (int level = 1; level <= n && e == hipSuccess; level++) {
-            k_seam_dp_level<<<(unsigned)((cells + 255) / 256), 256, 0, ctx->stream>>>(dW.as<long long>(), M, level, dF.as<long long>());
+            k_seam_dp_level<<<(unsigned)((cells + 255) / 256), 256, 0, ctx->stream>>>(dW, M, level, dF);
             e = hipGetLastError();
         }
         std::vector<int64_t> f(cells);
-        e = e ? e : hipMemcpyAsync(f.data(), dF.p, sizeof(int64_t) * cells, hipMemcpyDeviceToHost, ctx->stream);
+        e = e ? e : hipMemcpyAsync(f.data(), dF, sizeof(int64_t) * cells, hipMemcpyDeviceToHost, ctx->stream);
         e = e ? e : hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_gtsp_seam_tour_exact: %s", hipGetErrorString(e));
         // backtracking from the end: the lowest endpoint among equal values at every step

@@ -24,16 +24,16 @@ int wa_grid_path_shortcut(const wa_grid *g, const int64_t *ids, const int64_t *o
         }
         return WA_OK;
     }
-    long long *d_ids = nullptr, *d_off = nullptr, *d_wp = nullptr;
-    int32_t *d_step = nullptr, *d_cnt = nullptr;
-    double *d_len = nullptr;
+    DevBuf<long long> d_ids, d_off, d_wp;
+    DevBuf<int32_t> d_step, d_cnt;
+    DevBuf<double> d_len;
     std::vector<long long> wp((size_t)N);
-    hipError_t e = dalloc(&d_ids, (size_t)N);
-    e = e ? e : dalloc(&d_off, (size_t)n_paths + 1);
-    e = e ? e : dalloc(&d_wp, (size_t)N);
-    e = e ? e : dalloc(&d_step, (size_t)N);
-    e = e ? e : dalloc(&d_cnt, (size_t)n_paths);
-    e = e ? e : dalloc(&d_len, (size_t)n_paths);
+    hipError_t e = d_ids.alloc((size_t)N);
+    e = e ? e : d_off.alloc((size_t)n_paths + 1);
+    e = e ? e : d_wp.alloc((size_t)N);
+    e = e ? e : d_step.alloc((size_t)N);
+    e = e ? e : d_cnt.alloc((size_t)n_paths);
+    e = e ? e : d_len.alloc((size_t)n_paths);
     e = e ? e : hipMemcpyAsync(d_ids, ids, sizeof(long long) * N, hipMemcpyHostToDevice, ctx->stream);
     e = e ? e : hipMemcpyAsync(d_off, off, sizeof(long long) * ((size_t)n_paths + 1), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
@@ -49,7 +49,6 @@ int wa_grid_path_shortcut(const wa_grid *g, const int64_t *ids, const int64_t *o
     e = e ? e : hipMemcpyAsync(wp_count, d_cnt, sizeof(int32_t) * n_paths, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && length_out) e = hipMemcpyAsync(length_out, d_len, sizeof(double) * n_paths, hipMemcpyDeviceToHost, ctx->stream);
     e = e ? e : hipStreamSynchronize(ctx->stream);
-    hipFree(d_ids); hipFree(d_off); hipFree(d_wp); hipFree(d_step); hipFree(d_cnt); hipFree(d_len);
     if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_grid_path_shortcut: %s", hipGetErrorString(e));
     // only each path's waypoints: the rest of its range in the caller's buffer stays as it was
     for (int32_t p = 0; p < n_paths; p++)

@@ -34,21 +34,14 @@ static bool torch_tool_dev(const wa_tool_beads *tool, int32_t near_add, WaTorchT
 static const WaTorchRec TORCH_REC0 = {0, 0, 0, 0, ~0ull, 0, 0, 0, 0};
 
 struct TorchBuffers {
-    wa_ctx *ctx;
-    short4 *q = nullptr, *wish = nullptr;
-    WaTorchTool *tool = nullptr;
-    WaTorchRec *rec = nullptr;
-    long long *off = nullptr, *leg_cost = nullptr;
-    int32_t *pin_first = nullptr, *pin_last = nullptr, *dir = nullptr;
-    uint8_t *feas = nullptr, *back = nullptr;   // n * K bytes each, from the context's arena
-    uint8_t *blocked = nullptr, *near_ = nullptr;
-    explicit TorchBuffers(wa_ctx *c) : ctx(c) {}
-    ~TorchBuffers()
-    {
-        hipFree(q); hipFree(wish); hipFree(tool); hipFree(rec); hipFree(off); hipFree(leg_cost); hipFree(pin_first); hipFree(pin_last);
-        hipFree(dir); hipFree(blocked); hipFree(near_);
-        ctx_free(ctx, feas); ctx_free(ctx, back);
-    }
+    DevBuf<short4> q, wish;
+    DevBuf<WaTorchTool> tool;
+    DevBuf<WaTorchRec> rec;
+    DevBuf<long long> off, leg_cost;
+    DevBuf<int32_t> pin_first, pin_last, dir;
+    CtxBuf<uint8_t> feas, back;   // n * K bytes each, from the context's arena
+    DevBuf<uint8_t> blocked, near_;
+    explicit TorchBuffers(wa_ctx *c) : feas(c), back(c) {}
 };
 
 static void torch_summary_from(const WaTorchRec &rec, int64_t n, wa_tool_summary *s)
@@ -105,15 +98,13 @@ int wa_traj_tool_axes(const wa_grid *g, const wa_traj *t, const float *dirs, int
     }
     if (long_leg) return fail(ctx, WA_ERR_CAPACITY, "wa_traj_tool_axes: a leg holds more than 2^22 samples");
     if (n > (((int64_t)1 << 33) / K)) return fail(ctx, WA_ERR_CAPACITY, "wa_traj_tool_axes: n * K exceeds 2^33");
-    int rc = grid_build_d2(g);
+    WaField F;
+    int rc = grid_field(g, &F);
     if (rc) return rc;
     WaTorchRec rec = TORCH_REC0;
     std::vector<int64_t> costs((size_t)n_legs, 0);
     TorchBuffers B(ctx);
     if (n > 0) {
-        WaClrAxes A;
-        rc = clr_axes(g, &A);
-        if (rc) return rc;
         const size_t lds = (size_t)K * (size_t)dt.n_beads * sizeof(short4);
         if (lds > ((size_t)48 << 10)) {   // (the limit belongs to the function, per device: raised to the most a call can ask for)
             const hipError_t a = hipFuncSetAttribute((const void *)k_torch_nodes, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -121,17 +112,17 @@ int wa_traj_tool_axes(const wa_grid *g, const wa_traj *t, const float *dirs, int
             if (a != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_traj_tool_axes: dynamic LDS limit: %s", hipGetErrorString(a));
         }
         const size_t nk = (size_t)n * (size_t)K;
-        hipError_t e = dalloc(&B.q, (size_t)K);
-        e = e ? e : dalloc(&B.tool, 1);
-        e = e ? e : dalloc(&B.rec, 1);
-        e = e ? e : dalloc(&B.off, (size_t)n_legs + 1);
-        e = e ? e : dalloc(&B.leg_cost, (size_t)n_legs);
-        e = e ? e : dalloc(&B.dir, (size_t)n);
-        if (want) e = e ? e : dalloc(&B.wish, (size_t)n);
-        if (pin_first) e = e ? e : dalloc(&B.pin_first, (size_t)n_legs);
-        if (pin_last) e = e ? e : dalloc(&B.pin_last, (size_t)n_legs);
-        e = e ? e : ctx_alloc(ctx, &B.feas, nk);
-        e = e ? e : ctx_alloc(ctx, &B.back, nk);
+        hipError_t e = B.q.alloc((size_t)K);
+        e = e ? e : B.tool.alloc(1);
+        e = e ? e : B.rec.alloc(1);
+        e = e ? e : B.off.alloc((size_t)n_legs + 1);
+        e = e ? e : B.leg_cost.alloc((size_t)n_legs);
+        e = e ? e : B.dir.alloc((size_t)n);
+        if (want) e = e ? e : B.wish.alloc((size_t)n);
+        if (pin_first) e = e ? e : B.pin_first.alloc((size_t)n_legs);
+        if (pin_last) e = e ? e : B.pin_last.alloc((size_t)n_legs);
+        e = e ? e : B.feas.alloc(nk);
+        e = e ? e : B.back.alloc(nk);
         if (e != hipSuccess) return fail(ctx, WA_ERR_ALLOC, "wa_traj_tool_axes: device buffers");
         hipStream_t st = ctx->stream;
         e = hipMemcpyAsync(B.q, hq.data(), sizeof(short4) * (size_t)K, hipMemcpyHostToDevice, st);
@@ -143,7 +134,7 @@ int wa_traj_tool_axes(const wa_grid *g, const wa_traj *t, const float *dirs, int
         if (pin_last) e = e ? e : hipMemcpyAsync(B.pin_last, pin_last, sizeof(int32_t) * (size_t)n_legs, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) {
             const unsigned tiles = (unsigned)((n + WA_TORCH_TILE - 1) / WA_TORCH_TILE);
-            k_torch_nodes<<<tiles, 256, lds, st>>>(t->xyz, n, g->d, g->cx, g->cy, g->cz, A, g->d2, B.q, K, B.tool, B.feas, B.rec);
+            k_torch_nodes<<<tiles, 256, lds, st>>>(t->xyz, n, F, B.q, K, B.tool, B.feas, B.rec);
             e = hipGetLastError();
         }
         if (e == hipSuccess) {
@@ -191,27 +182,24 @@ int wa_traj_tool_check(const wa_grid *g, const wa_traj *t, const float *axes, co
     for (int64_t i = 0; i < n; i++)
         if (!torch_quantise(axes + 3 * (size_t)i, &hq[(size_t)i]))
             return fail(ctx, WA_ERR_ARG, "wa_traj_tool_check: an axis is not finite or has zero length");
-    int rc = grid_build_d2(g);
+    WaField F;
+    int rc = grid_field(g, &F);
     if (rc) return rc;
     WaTorchRec rec = TORCH_REC0;
     if (n > 0) {
-        WaClrAxes A;
-        rc = clr_axes(g, &A);
-        if (rc) return rc;
         TorchBuffers B(ctx);
-        hipError_t e = dalloc(&B.q, (size_t)n);
-        e = e ? e : dalloc(&B.tool, 1);
-        e = e ? e : dalloc(&B.rec, 1);
-        e = e ? e : dalloc(&B.blocked, (size_t)n);
-        e = e ? e : dalloc(&B.near_, (size_t)n);
+        hipError_t e = B.q.alloc((size_t)n);
+        e = e ? e : B.tool.alloc(1);
+        e = e ? e : B.rec.alloc(1);
+        e = e ? e : B.blocked.alloc((size_t)n);
+        e = e ? e : B.near_.alloc((size_t)n);
         if (e != hipSuccess) return fail(ctx, WA_ERR_ALLOC, "wa_traj_tool_check: device buffers");
         hipStream_t st = ctx->stream;
         e = hipMemcpyAsync(B.q, hq.data(), sizeof(short4) * (size_t)n, hipMemcpyHostToDevice, st);
         e = e ? e : hipMemcpyAsync(B.tool, &dt, sizeof dt, hipMemcpyHostToDevice, st);
         e = e ? e : hipMemcpyAsync(B.rec, &rec, sizeof rec, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) {
-            k_torch_check<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(t->xyz, n, g->d, g->cx, g->cy, g->cz, A, g->d2, B.q, B.tool, B.blocked,
-                                                                       B.near_, B.rec);
+            k_torch_check<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(t->xyz, n, F, B.q, B.tool, B.blocked, B.near_, B.rec);
             e = hipGetLastError();
         }
         e = e ? e : hipMemcpyAsync(&rec, B.rec, sizeof rec, hipMemcpyDeviceToHost, st);

@@ -50,11 +50,11 @@ int wa_traj_stitch(const wa_grid *g, const int64_t *seg_ids, const int64_t *seg_
     int rc = traj_alloc(ctx, n, &t);
     if (rc) return rc;
     if (n) {
-        long long *d_ids = nullptr, *d_off = nullptr;
-        uint8_t *d_rev = nullptr;
-        hipError_t h = dalloc(&d_ids, (size_t)n);
-        h = h ? h : dalloc(&d_off, (size_t)n_seg + 1);
-        if (reverse) h = h ? h : dalloc(&d_rev, (size_t)n_seg);
+        DevBuf<long long> d_ids, d_off;
+        DevBuf<uint8_t> d_rev;
+        hipError_t h = d_ids.alloc((size_t)n);
+        h = h ? h : d_off.alloc((size_t)n_seg + 1);
+        if (reverse) h = h ? h : d_rev.alloc((size_t)n_seg);
         h = h ? h : hipMemcpyAsync(d_ids, seg_ids, sizeof(long long) * n, hipMemcpyHostToDevice, ctx->stream);
         h = h ? h : hipMemcpyAsync(d_off, seg_off, sizeof(long long) * (n_seg + 1), hipMemcpyHostToDevice, ctx->stream);
         if (reverse) h = h ? h : hipMemcpyAsync(d_rev, reverse, (size_t)n_seg, hipMemcpyHostToDevice, ctx->stream);
@@ -63,7 +63,6 @@ int wa_traj_stitch(const wa_grid *g, const int64_t *seg_ids, const int64_t *seg_
             h = hipGetLastError();
         }
         h = h ? h : hipStreamSynchronize(ctx->stream);
-        hipFree(d_ids); hipFree(d_off); hipFree(d_rev);
         if (h != hipSuccess) { wa_traj_destroy(t); return fail(ctx, WA_ERR_DEVICE, "wa_traj_stitch: %s", hipGetErrorString(h)); }
     }
     *out = t;
@@ -167,15 +166,13 @@ int wa_bspline_set_param(wa_bspline *b, const float *init, const float *fin, con
     if (!init || !fin || (b->S.n_middle > 0 && !middle)) return fail(ctx, WA_ERR_ARG, "wa_bspline_set_param: null argument");
     if (stride < b->S.dim) return fail(ctx, WA_ERR_ARG, "wa_bspline_set_param: stride < dim");
     if (!(fin_time > 0.0f) || !isfinite(fin_time)) return fail(ctx, WA_ERR_ARG, "wa_bspline_set_param: fin_time must be finite and > 0");
-    float *d_mid = nullptr;
+    DevBuf<float> d_mid;
     if (b->S.n_middle) {
-        if (dalloc(&d_mid, (size_t)b->S.n_middle * stride)) return fail(ctx, WA_ERR_ALLOC, "wa_bspline_set_param: staging");
+        if (d_mid.alloc((size_t)b->S.n_middle * stride)) return fail(ctx, WA_ERR_ALLOC, "wa_bspline_set_param: staging");
         hipError_t h = hipMemcpyAsync(d_mid, middle, sizeof(float) * b->S.n_middle * stride, hipMemcpyHostToDevice, ctx->stream);
-        if (h != hipSuccess) { hipFree(d_mid); return fail(ctx, WA_ERR_DEVICE, "wa_bspline_set_param: %s", hipGetErrorString(h)); }
+        if (h != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_bspline_set_param: %s", hipGetErrorString(h));
     }
-    int rc = bspline_setup(b, init, fin, d_mid, stride, fin_time);
-    hipFree(d_mid);
-    return rc;
+    return bspline_setup(b, init, fin, d_mid, stride, fin_time);
 }
 
 int wa_bspline_set_param_traj(wa_bspline *b, const float *init, const float *fin, const wa_traj *middle, float fin_time)
@@ -232,8 +229,9 @@ static int bspline_run(wa_bspline *b, const float *u, float t0, float dt, int64_
     if (out_traj) *out_traj = nullptr;
     if (count == 0) return out_traj ? traj_alloc(ctx, 0, out_traj) : WA_OK;
     const int dim = b->S.dim;
-    float *d_u = nullptr, *d_out = nullptr;
-    uint8_t *d_ok = nullptr;
+    DevBuf<float> d_u, d_tmp;   // d_tmp: the values, unless they go into a trajectory
+    DevBuf<uint8_t> d_ok;
+    float *d_out = nullptr;
     wa_traj *t = nullptr;
     hipError_t h = hipSuccess;
     if (out_traj) {
@@ -241,19 +239,18 @@ static int bspline_run(wa_bspline *b, const float *u, float t0, float dt, int64_
         if (rc) return rc;
         d_out = t->xyz;
     } else {
-        h = dalloc(&d_out, (size_t)count * dim);
+        h = d_tmp.alloc((size_t)count * dim);
+        d_out = d_tmp;
     }
     if (u) {
-        h = h ? h : dalloc(&d_u, (size_t)count);
+        h = h ? h : d_u.alloc((size_t)count);
         h = h ? h : hipMemcpyAsync(d_u, u, sizeof(float) * count, hipMemcpyHostToDevice, ctx->stream);
     }
-    if (ok) h = h ? h : dalloc(&d_ok, (size_t)count);
+    if (ok) h = h ? h : d_ok.alloc((size_t)count);
     h = h ? h : bspline_launch(b, d_u, t0, dt, count, der, d_out, d_ok);
     if (out) h = h ? h : hipMemcpyAsync(out, d_out, sizeof(float) * count * dim, hipMemcpyDeviceToHost, ctx->stream);
     if (ok) h = h ? h : hipMemcpyAsync(ok, d_ok, (size_t)count, hipMemcpyDeviceToHost, ctx->stream);
     h = h ? h : hipStreamSynchronize(ctx->stream);
-    hipFree(d_u); hipFree(d_ok);
-    if (!out_traj) hipFree(d_out);
     if (h != hipSuccess) {
         wa_traj_destroy(t);
         return fail(ctx, WA_ERR_DEVICE, "B-spline evaluation: %s", hipGetErrorString(h));

@@ -120,11 +120,10 @@ struct WaRtLimits {
     int32_t curv;         // a_lat is finite and not 0
 };
 
-// Rule 2.  The voxel of a sample is found per axis by clr_axis_node, the lookup k_clr_samples runs.
+// Rule 2.  The voxel of a sample is found by field_voxel, the lookup k_clr_samples runs; a call without a grid passes a zeroed view.
 __global__ __launch_bounds__(256) void k_rt_caps(const float *__restrict__ xyz, long long n, WaRtLimits lim, const float *__restrict__ v_limit,
-                                                 int32_t have_grid, WaDims d, const float *__restrict__ cx, const float *__restrict__ cy,
-                                                 const float *__restrict__ cz, WaClrAxes ax, const int32_t *__restrict__ d2,
-                                                 long long *__restrict__ C, uint8_t *__restrict__ kind, WaRtRec *__restrict__ rec)
+                                                 WaField F, long long *__restrict__ C, uint8_t *__restrict__ kind,
+                                                 WaRtRec *__restrict__ rec)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long outs = 0;
@@ -149,13 +148,12 @@ __global__ __launch_bounds__(256) void k_rt_caps(const float *__restrict__ xyz, 
                 if (k2 < cap) { cap = k2; k = 2; }
             }
         }
-        if (have_grid) {
+        if (F.d2) {
             bool out = false;
-            const int32_t x = clr_axis_node(cx, d.nx, ax.lo[0], ax.hi[0], ax.mono[0], p[0], &out);
-            const int32_t y = clr_axis_node(cy, d.ny, ax.lo[1], ax.hi[1], ax.mono[1], p[1], &out);
-            const int32_t z = clr_axis_node(cz, d.nz, ax.lo[2], ax.hi[2], ax.mono[2], p[2], &out);
+            int64_t id;
+            field_voxel(F, p[0], p[1], p[2], &id, &out);
             outs = out ? 1 : 0;
-            if (lim.near_d2 >= 0 && d2[(int64_t)z * d.nxy + (int64_t)y * d.nx + x] <= lim.near_d2) {
+            if (lim.near_d2 >= 0 && F.d2[id] <= lim.near_d2) {
                 const double k3 = lim.v_near * lim.v_near;
                 if (k3 < cap) { cap = k3; k = 3; }
             }

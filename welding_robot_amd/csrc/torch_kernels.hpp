@@ -58,17 +58,12 @@ __device__ __forceinline__ int32_t torch_turn(short4 a, short4 b)
 }
 
 // The voxel of sample i by the lookup of wa_traj_clearance; *outside as there; *bad when a coordinate is not finite.
-__device__ __forceinline__ int3 torch_sample_voxel(const float *__restrict__ xyz, long long i, WaDims d, const float *__restrict__ cx,
-                                                   const float *__restrict__ cy, const float *__restrict__ cz, const WaClrAxes &A,
-                                                   bool *outside, bool *bad)
+__device__ __forceinline__ int3 torch_sample_voxel(const float *__restrict__ xyz, long long i, const WaField &F, bool *outside, bool *bad)
 {
     const float px = xyz[3 * i], py = xyz[3 * i + 1], pz = xyz[3 * i + 2];
     *bad = !(isfinite(px) && isfinite(py) && isfinite(pz));
-    int3 v;
-    v.x = clr_axis_node(cx, d.nx, A.lo[0], A.hi[0], A.mono[0], px, outside);
-    v.y = clr_axis_node(cy, d.ny, A.lo[1], A.hi[1], A.mono[1], py, outside);
-    v.z = clr_axis_node(cz, d.nz, A.lo[2], A.hi[2], A.mono[2], pz, outside);
-    return v;
+    int64_t id;
+    return field_voxel(F, px, py, pz, &id, outside);
 }
 
 // One workgroup per tile of WA_TORCH_TILE consecutive samples: neighbouring samples of a trajectory touch the same lines of d2, so
@@ -76,10 +71,9 @@ __device__ __forceinline__ int3 torch_sample_voxel(const float *__restrict__ xyz
 // the lanes of a wavefront -- consecutive directions -- read consecutive 8-byte words.  The (sample, direction) pairs of the tile are
 // laid out sample-major over the threads, which is also the layout of feas: every store is coalesced.
 // Dynamic LDS: K * n_beads * 8 bytes (at most 128 KiB).
-__global__ __launch_bounds__(256) void k_torch_nodes(const float *__restrict__ xyz, long long n, WaDims d, const float *__restrict__ cx,
-                                                     const float *__restrict__ cy, const float *__restrict__ cz, WaClrAxes A,
-                                                     const int32_t *__restrict__ d2, const short4 *__restrict__ q, int32_t K,
-                                                     const WaTorchTool *__restrict__ tool, uint8_t *__restrict__ feas, WaTorchRec *__restrict__ rec)
+__global__ __launch_bounds__(256) void k_torch_nodes(const float *__restrict__ xyz, long long n, WaField F, const short4 *__restrict__ q,
+                                                     int32_t K, const WaTorchTool *__restrict__ tool, uint8_t *__restrict__ feas,
+                                                     WaTorchRec *__restrict__ rec)
 {
     extern __shared__ __align__(16) unsigned char torch_lds[];
     short4 *offs = (short4 *)torch_lds;
@@ -97,7 +91,7 @@ __global__ __launch_bounds__(256) void k_torch_nodes(const float *__restrict__ x
     if (threadIdx.x < 64) {   // (wavefront 0 as a whole: WA_TORCH_TILE <= 64)
         bool outside = false, bad = false;
         if ((int32_t)threadIdx.x < ts) {
-            vox[threadIdx.x] = torch_sample_voxel(xyz, i0 + threadIdx.x, d, cx, cy, cz, A, &outside, &bad);
+            vox[threadIdx.x] = torch_sample_voxel(xyz, i0 + threadIdx.x, F, &outside, &bad);
             n_blk[threadIdx.x] = 0;
         }
         const unsigned long long mo = __ballot(outside), mb = __ballot(bad);
@@ -115,7 +109,7 @@ __global__ __launch_bounds__(256) void k_torch_nodes(const float *__restrict__ x
         int n_near = 0;
         bool blocked = false;
         for (int32_t j = 0; j < nb; j++) {
-            const int r = torch_bead(d2, d, v.x, v.y, v.z, offs[j * K + k], thr[0][j], thr[1][j]);
+            const int r = torch_bead(F.d2, F.d, v.x, v.y, v.z, offs[j * K + k], thr[0][j], thr[1][j]);
             n_near += r == 1;
             blocked |= r == 2;
         }
@@ -135,20 +129,18 @@ __global__ __launch_bounds__(256) void k_torch_nodes(const float *__restrict__ x
 }
 
 // Rule 2 for one given axis per sample: one lane per sample, the same offset and bead functions as above.
-__global__ __launch_bounds__(256) void k_torch_check(const float *__restrict__ xyz, long long n, WaDims d, const float *__restrict__ cx,
-                                                     const float *__restrict__ cy, const float *__restrict__ cz, WaClrAxes A,
-                                                     const int32_t *__restrict__ d2, const short4 *__restrict__ q, const WaTorchTool *__restrict__ tool,
-                                                     uint8_t *__restrict__ blocked_out, uint8_t *__restrict__ near_out,
-                                                     WaTorchRec *__restrict__ rec)
+__global__ __launch_bounds__(256) void k_torch_check(const float *__restrict__ xyz, long long n, WaField F, const short4 *__restrict__ q,
+                                                     const WaTorchTool *__restrict__ tool, uint8_t *__restrict__ blocked_out,
+                                                     uint8_t *__restrict__ near_out, WaTorchRec *__restrict__ rec)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     bool outside = false, bad = false, blocked = false;
     int n_near = 0;
     if (i < n) {
-        const int3 v = torch_sample_voxel(xyz, i, d, cx, cy, cz, A, &outside, &bad);
+        const int3 v = torch_sample_voxel(xyz, i, F, &outside, &bad);
         const short4 qi = q[i];
         for (int32_t j = 0; j < tool->n_beads; j++) {
-            const int r = torch_bead(d2, d, v.x, v.y, v.z, torch_offset(qi, tool->dist16[j]), tool->r2[j], tool->rn[j]);
+            const int r = torch_bead(F.d2, F.d, v.x, v.y, v.z, torch_offset(qi, tool->dist16[j]), tool->r2[j], tool->rn[j]);
             n_near += r == 1;
             blocked |= r == 2;
         }

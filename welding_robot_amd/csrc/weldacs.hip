@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <chrono>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <unordered_map>
@@ -83,6 +84,9 @@ struct wa_grid {
     mutable std::mutex h_mu;   // guards the mirror's first fill (concurrent wa_grid_resolve_points calls on one grid)
     // exact squared distance field of the occupancy (wa_grid_distance_field): built on the first call that needs it, freed with the grid
     mutable int32_t *d2 = nullptr;   // device, n
+    // ... and what a lookup in it needs of the axis tables (grid_field): computed once, under the same lock
+    mutable WaClrAxes axes;
+    mutable bool axes_valid = false;
     mutable std::mutex d2_mu;
     // bit-packed copy of the occupancy (1 = free, 64 voxels of a row in x per word, rows padded to whole words) for the geodesic
     // searches: built on the first wa_grid_geodesic_* call, freed with the grid
@@ -418,6 +422,14 @@ struct DevBuf {
     operator T *() const { return p; }
 };
 
+// a trajectory or spline that a call builds and hands over when it succeeds (release()): destroyed on every other way out
+struct WaHandleDel {
+    void operator()(wa_traj *t) const { wa_traj_destroy(t); }
+    void operator()(wa_bspline *b) const { wa_bspline_destroy(b); }
+};
+template <class H>
+using OwnedHandle = std::unique_ptr<H, WaHandleDel>;
+
 // one chunk of class k for a block under construction: from the pool; else from a kept block that nobody asked for (harvested, least
 // recently used first); else created -- pooled chunks of the other classes and cached whole blocks make room when the device is full
 static hipError_t arena_chunk(wa_ctx *c, int k, hipMemGenericAllocationHandle_t *h, bool *kept)
@@ -659,6 +671,19 @@ static void ctx_free(wa_ctx *c, const void *cp)
     }
     hipFree(p);
 }
+// DevBuf's sibling for a block from ctx_alloc.  Such a block goes back to the context's cache, where the next caller may be handed it
+// at once: the context's stream is waited for first, so that nothing launched by this call still writes it.
+template <class T>
+struct CtxBuf {
+    wa_ctx *ctx;
+    T *p = nullptr;
+    explicit CtxBuf(wa_ctx *c) : ctx(c) {}
+    CtxBuf(const CtxBuf &) = delete;
+    CtxBuf &operator=(const CtxBuf &) = delete;
+    ~CtxBuf() { if (p) { hipStreamSynchronize(ctx->stream); ctx_free(ctx, p); } }
+    hipError_t alloc(size_t count) { return ctx_alloc(ctx, &p, count); }
+    operator T *() const { return p; }
+};
 
 extern "C" {
 
