@@ -170,14 +170,20 @@ void wa_acs_destroy(wa_acs *s);
  * batch, at least min(n_slots, 4) -- from 32 slots on n_slots / 8, between 8 and 24) and once per solver; the per-generation trace (20 B per slot and generation) comes on top.
  * Nothing is allocated.  The drop-in ACS_Rank sizes the concurrent pair searches of a device from this and
  * wa_ctx_memory_info (ACSRank_3D.hpp:472-499 runs them one after another).  The straggler pools of small dense solvers come on top:
- * wa_acs_straggler_pool_bytes. */
+ * wa_acs_straggler_pool_bytes.  Both are sums over the list of blocks the solver itself is created from (csrc/acs_plan.hpp), so every
+ * block is counted at its size: bytes_fixed holds the guard bands (a lazy solver's stamp guard included), the L table, the pads of the
+ * replay table (1 024 B) and of the byte masks (4 B), the REF stream, the debug counters, the per-ant REF verdicts and the REF
+ * speculation buffers; a dense solver created under WA_REPLAY=0 has no replay table and none is counted.  (Until the plan existed the
+ * small blocks were a guessed 4 096 B and the stamp guard and the pads were left out: bytes_per_slot and bytes_per_heuristic_field
+ * are what they were, bytes_fixed moved by less than a megabyte.) */
 int wa_acs_memory_estimate(const wa_grid *grid, int32_t max_colony, int64_t path_capacity, int32_t neighbourhood, int32_t lazy,
                            int64_t *bytes_per_slot, int64_t *bytes_per_heuristic_field, int64_t *bytes_fixed);
 /* A dense solver (6 or 26 neighbours) of at most 256 ants and at most 16 slots (WA_STRAGGLER_SLOTS) additionally holds, PER SLOT, the
  * arrival list and what the straggler hand-over needs (see wa_acs_debug_counters): a second array of ants' paths (max_colony x
  * path_capacity words: stragglers walk on in place while the next generation writes the other array) + 256 spill-bitmap rows
- * (0.33 GB per slot at 128^3 with 256 ants and the default path capacity).  *bytes = what a solver of this shape holds in total, 0 when it
- * gets none (lazy, larger colonies, more slots, WA_STRAGGLERS=0). */
+ * (0.33 GB per slot at 128^3 with 256 ants and the default path capacity) + the small lists and counters.  *bytes = what a solver of this
+ * shape holds in total -- its plan with the group minus its plan without -- 0 when it gets none (lazy, larger colonies, more slots,
+ * WA_STRAGGLERS=0). */
 int wa_acs_straggler_pool_bytes(const wa_grid *grid, int32_t n_slots, int32_t max_colony, int64_t path_capacity, int32_t neighbourhood,
                                 int32_t lazy, int64_t *bytes);
 /* initFromGridMap :343-408: in-bounds edges pheromone_0, out-of-bounds edges 0. slot<0: all */

@@ -17,7 +17,8 @@ def ctx():
     c.close()
 
 
-@pytest.mark.parametrize("lazy,colony,nb", [(True, 24, 6), (False, 24, 6), (False, 256, 6), (False, 64, 26), (False, 2048, 6), (True, 2048, 6)])
+@pytest.mark.parametrize("lazy,colony,nb", [(True, 24, 6), (False, 24, 6), (False, 256, 6), (False, 64, 26), (False, 2048, 6), (True, 2048, 6),
+                                            (True, 24, 26), (False, 35, 6), (False, 36, 6)])
 def test_memory_estimate_matches_the_allocator(ctx, lazy, colony, nb):
     if os.environ.get("PYTEST_XDIST_WORKER"):
         pytest.skip("compares the estimate with the DEVICE's free memory, which other xdist workers change meanwhile: run without -n")

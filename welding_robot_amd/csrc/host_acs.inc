@@ -16,23 +16,43 @@ void wa_acs_default_params(wa_acs_params *p)
 }
 
 
+static_assert(WA_PLAN_REF_SPEC_LEN == WA_REF_SPEC_LEN && WA_PLAN_REF_SUPER == WA_REF_SUPER && WA_PLAN_RESUME_MAX == WA_RESUME_MAX &&
+              WA_PLAN_POOL_REC == WA_POOL_REC && WA_PLAN_ROW26 == WA_ROW26, "acs_plan.hpp and the kernels' headers disagree");
+// what the solver's memory plan (acs_plan.hpp) is made from: the shape and the switches of the environment
+static WaPlanIn acs_plan_in(const wa_grid *grid, int32_t n_slots, int32_t max_colony, int64_t path_capacity, int32_t nb, bool lazy)
+{
+    // four fields (a few searches share theirs); solvers sized for pair planning get one per eight slots, between 8 and 24: the pair
+    // loop runs its searches in end-point order, a batch of 224 of C5's searches spans 5-8 of the large end-point groups but up to ~20 of
+    // the small ones (group j has j pairs), and growing the pool inside a run is an allocation of the whole pool + a copy -- on fresh
+    // device memory possibly the driver's wipe of it: measured 0.18 s in one batch of C5's first run.  More on demand (wa_acs_begin), at
+    // most one per slot.
+    int32_t fields0 = n_slots < 4 ? n_slots : 4;
+    if (n_slots >= 32) fields0 = n_slots / 8 < 8 ? 8 : (n_slots / 8 > 24 ? 24 : n_slots / 8);
+    return WaPlanIn{grid->d.n, grid->d.nxy, n_slots, max_colony, fields0, path_capacity, nb, lazy ? 1 : 0,
+                    env_int("WA_MASK_U64", 0), env_int("WA_REPLAY", 1), env_int("WA_REF_SPEC", 1), env_int("WA_STRAGGLERS", 1), env_int("WA_STRAGGLER_SLOTS", 16),
+                    (int64_t)sizeof(WaSlotCtl), (int64_t)sizeof(WaGlibcRand)};
+}
+
 // The pool of heuristic fields ((1 + beta*cos) of ACSRank_3D.hpp:151-154, one per END point in use): `want` fields in one
 // allocation with the walk loop's guard bands at both ends; growing keeps the fields that are there.
 static int heur_pool_grow(wa_acs *s, WaAcsDev *D, int32_t want)
 {
     if (want <= s->heur_fields) return 0;
-    const size_t guard = s->heur_guard, stride = (size_t)D->pher_stride;
+    const WaPlanRow &row = s->plan.rows[s->plan.heur_row];
+    const size_t guard = (size_t)s->plan.guard, stride = (size_t)D->pher_stride;
+    WaBlock *cur = nullptr;
+    for (WaBlock &b : s->blocks) if (b.row == &row) cur = &b;
     float *fresh = nullptr;
-    if (ctx_alloc(s->ctx, &fresh, (size_t)want * stride + 2 * guard) != hipSuccess) return (int)hipErrorOutOfMemory;
+    if (ctx_alloc_bytes(s->ctx, (void **)&fresh, (size_t)s->plan.bytes(row, want)) != hipSuccess) return (int)hipErrorOutOfMemory;
     hipStream_t st = s->ctx->stream;
     hipError_t e = hipMemsetAsync(fresh, 0, sizeof(float) * guard, st);
     e = e ? e : hipMemsetAsync(fresh + guard + (size_t)want * stride, 0, sizeof(float) * guard, st);
-    if (!e && s->heur_alloc)
-        e = hipMemcpyAsync(fresh + guard, s->heur_alloc + guard, sizeof(float) * (size_t)s->heur_fields * stride, hipMemcpyDeviceToDevice, st);
+    if (!e && cur)
+        e = hipMemcpyAsync(fresh + guard, (float *)cur->p + guard, sizeof(float) * (size_t)s->heur_fields * stride, hipMemcpyDeviceToDevice, st);
     e = e ? e : hipStreamSynchronize(st);
     if (e != hipSuccess) { ctx_free(s->ctx, fresh); return (int)e; }   // the pool that is there stays as it is
-    if (s->heur_alloc) ctx_free(s->ctx, s->heur_alloc);
-    s->heur_alloc = fresh;
+    if (cur) { ctx_free(s->ctx, cur->p); cur->p = fresh; }
+    else s->blocks.push_back(WaBlock{&row, fresh});
     D->heur = fresh + guard;
     s->heur_end.resize((size_t)want, -1);
     s->heur_beta.resize((size_t)want, 0.f);
@@ -42,49 +62,15 @@ static int heur_pool_grow(wa_acs *s, WaAcsDev *D, int32_t want)
 }
 
 static int acs_create_once(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, int32_t max_colony,
-                           int64_t path_capacity, int32_t nb, bool lazy, wa_acs **out);
-// (a solver whose arrays were served from kept blocks somewhat larger than asked for -- the arena's way of not re-mapping everything for
-//  every slightly different shape -- can fail to fit where exact blocks would: one more attempt with exact sizes only)
-static int acs_create(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, int32_t max_colony,
-                      int64_t path_capacity, int32_t nb, bool lazy, wa_acs **out)
-{
-    int rc = acs_create_once(ctx, grid, n_slots, max_colony, path_capacity, nb, lazy, out);
-    if (rc == WA_ERR_ALLOC && ctx && ctx->arena_on && !ctx->arena_strict) {
-        ctx->arena_strict = true;
-        rc = acs_create_once(ctx, grid, n_slots, max_colony, path_capacity, nb, lazy, out);
-        ctx->arena_strict = false;
-    }
-    return rc;
-}
-static int acs_create_once(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, int32_t max_colony,
                            int64_t path_capacity, int32_t nb, bool lazy, wa_acs **out)
 {
     if (!ctx || !grid || !out || n_slots < 1 || max_colony < 1) return fail(ctx, WA_ERR_ARG, "wa_acs_create: bad argument");
     *out = nullptr;
     wa_acs *s = new wa_acs();
-    memset(&s->D, 0, sizeof s->D);
     s->ctx = ctx;
     s->grid = grid;
     s->n_slots = n_slots;
-    s->heur_fields = 0;
-    s->heur_batch = 0;
     s->max_colony = max_colony;
-    s->n_active = 0;
-    s->begun = false;
-    s->gens_enqueued = 0;
-    s->prof = false;
-    s->prof_sweep_all = false;
-    s->prof_paired = false;
-    s->last_walk[0] = s->last_walk[1] = s->last_walk[2] = s->last_walk[3] = 0;
-    s->prof_every = 1;
-    s->d_starts = s->d_ends = nullptr;
-    s->d_streams = nullptr;
-    s->d_hslot = s->d_hlist = s->d_hends = nullptr;
-    s->pher_buf[0] = s->pher_buf[1] = nullptr;
-    s->pher_alloc[0] = s->pher_alloc[1] = s->heur_alloc = nullptr;
-    s->stamp_alloc = nullptr;
-    s->cur_buf = 0;
-    for (int i = 0; i < WA_K_COUNT; i++) { s->prof_ms[i] = 0; s->prof_n[i] = 0; }
     const int64_t n = grid->d.n;
     if (nb != 6 && nb != 26) { delete s; return fail(ctx, WA_ERR_ARG, "wa_acs_create: neighbourhood must be 6 or 26"); }
     s->nb = nb;
@@ -100,19 +86,16 @@ static int acs_create_once(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, in
         delete s;
         return fail(ctx, WA_ERR_ARG, "wa_acs_create: 26-neighbour grids above 2^27 voxels (512^3) are not supported");
     }
-    if (path_capacity <= 0) path_capacity = n < (1 << 18) ? n : (1 << 18);
-    if (path_capacity > n) path_capacity = n;
-    if (path_capacity < 2) path_capacity = 2;
-    s->path_cap = path_capacity;
+    const WaAcsPlan &P = s->plan = wa_acs_plan(acs_plan_in(grid, n_slots, max_colony, path_capacity, nb, lazy));
+    path_capacity = s->path_cap = P.cap;
+    s->ref_spec = P.ref_spec;
     WaAcsDev &D = s->D;
     D.d = grid->d;
     D.cx = grid->cx; D.cy = grid->cy; D.cz = grid->cz; D.occ = grid->occ;
     D.nb = nb;
-    D.pher_stride = (((int64_t)nb * n + 63) / 64) * 64;
-    D.path_cap = path_capacity;
-    D.vbits_words = (n + 31) / 32;
     D.max_colony = max_colony;
-    D.trace_cap = 0;
+    D.pher_stride = P.pher_stride; D.path_cap = P.cap; D.vbits_words = P.vbits_words; D.vbits_rows = (int32_t)P.vbits_rows;
+    D.guard_bytes = (int32_t)(P.guard * sizeof(float)); D.stamp_guard_bytes = (int32_t)(P.sguard * sizeof(uint32_t));
     // tabu hash: a probe that lands on another key costs the walk a taken branch and an LDS round trip, so the table is
     // sized for a few percent load on a typical walk (64 x the grid's L1 diameter) while one walk block per CU suffices
     int lg = 11;
@@ -190,7 +173,6 @@ static int acs_create_once(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, in
     s->pipe_groups_env = env_int("WA_PIPE_GROUPS", 0);
     s->hw_queues = env_int("GPU_MAX_HW_QUEUES", 4);
     s->drain_ok = env_int("WA_STRAGGLER_DRAIN", 1) != 0;
-    s->ref_spec = env_int("WA_REF_SPEC", 1) != 0 && nb == 6;
     s->sweep_nt_env = env_int("WA_SWEEP_NT", -1);
     s->straggler_gens = env_int("WA_STRAGGLER_GENS", 64);
     {   // sweep grid: measured on MI355X -- 100 MB fields (128^3 x 6) peak at 4096 blocks (6.0 TB/s; 2048: 5.5, 8192: 5.8),
@@ -200,82 +182,57 @@ static int acs_create_once(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, in
         if (blocks > 65536) blocks = 65536;
         s->evap_blocks = env_int("WA_EVAP_BLOCKS", (int)blocks);
     }
-    const size_t S = (size_t)n_slots, C = (size_t)max_colony;
     hipError_t e = hipSuccess;
     // WA_TRACE_CREATE=1: seconds spent allocating / clearing / initialising, on stderr (tools/create_time.py)
     const bool trace_create = env_int("WA_TRACE_CREATE", 0) != 0;
     const auto t_create0 = std::chrono::steady_clock::now();
     auto since0 = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_create0).count(); };
-    // The walk's inner loop reads records up to two lattice hops away from the current voxel without clamping the
-    // address (an out-of-bounds neighbour is never walked to, its record is only fetched): every pheromone /
-    // heuristic allocation therefore carries a guard band of 2*nx*ny records (+ slack) in front and behind.
-    const size_t guard = nb == 6 ? (((size_t)2 * grid->d.nxy * 6 + 64 + 63) / 64) * 64 : 0;   // floats
-    D.guard_bytes = (int32_t)(guard * sizeof(float));
-    e = e ? e : ctx_alloc(ctx, &s->pher_alloc[0], S * D.pher_stride + 2 * guard);
-    if (!lazy) e = e ? e : ctx_alloc(ctx, &s->pher_alloc[1], S * D.pher_stride + 2 * guard);   // the lazy sweep is in place: one field
-    if (!e) { s->pher_buf[0] = s->pher_alloc[0] + guard; if (s->pher_alloc[1]) s->pher_buf[1] = s->pher_alloc[1] + guard; }
-    if (lazy) {
-        const size_t sguard = (((size_t)grid->d.nxy + 64 + 63) / 64) * 64;   // entries: the walk fetches its six neighbours' stamps unclamped
-        D.stamp_guard_bytes = (int32_t)(sguard * sizeof(uint32_t));
-        e = e ? e : ctx_alloc(ctx, &s->stamp_alloc, S * n + 2 * sguard);
-        if (!e) D.stamp = s->stamp_alloc + sguard;
-        e = e ? e : ctx_alloc(ctx, &D.dirty_list, S * n);
-        e = e ? e : ctx_alloc(ctx, &D.dcount, S * 2);
+    // the plan's blocks, in its order.  The straggler group is an optimisation: a device that has no room for all of it gets the group's
+    // blocks back and runs the solver without the hand-over instead of failing (the resume blocks' bitmap rows are then simply never used)
+    bool pools = P.pools;
+    for (const WaPlanRow &r : P.rows) {
+        if (e || (r.pool && !pools)) continue;
+        if (&r == &P.rows[P.heur_row]) { e = (hipError_t)heur_pool_grow(s, &D, (int32_t)P.fields0); continue; }
+        void *p = nullptr;
+        const hipError_t re = ctx_alloc_bytes(ctx, &p, (size_t)P.bytes(r));
+        if (re == hipSuccess) { s->blocks.push_back(WaBlock{&r, p}); continue; }
+        if (!r.pool) { e = re; continue; }
+        (void)hipGetLastError();
+        pools = false;
+        for (; s->blocks.back().row->pool; s->blocks.pop_back()) ctx_free(ctx, s->blocks.back().p);
     }
-    s->heur_guard = guard;
-    // four fields (a few searches share theirs); solvers sized for pair planning get one per eight slots, between 8 and 24: the pair
-    // loop runs its searches in end-point order, a batch of 224 of C5's searches spans 5-8 of the large end-point groups but up to ~20 of
-    // the small ones (group j has j pairs), and growing the pool inside a run is an allocation of the whole pool + a copy -- on fresh
-    // device memory possibly the driver's wipe of it: measured 0.18 s in one batch of C5's first run.  More on demand (wa_acs_begin), at
-    // most one per slot.
-    {
-        int32_t fields0 = n_slots < 4 ? n_slots : 4;
-        if (n_slots >= 32) fields0 = n_slots / 8 < 8 ? 8 : (n_slots / 8 > 24 ? 24 : n_slots / 8);
-        e = e ? e : (hipError_t)heur_pool_grow(s, &D, fields0);
+    // every block to the pointer that names it (+ the guard band in front of a field); a solver without the block keeps the null pointer
+    size_t wired = 0;
+    auto wire = [&](auto *&dst, const char *name, int64_t skip = 0) {
+        using T = typename std::remove_reference<decltype(dst)>::type;
+        for (const WaBlock &b : s->blocks)
+            if (!strcmp(b.row->name, name)) { dst = static_cast<T>(b.p) + skip; wired++; }
+    };
+    uint32_t *ref_jump = nullptr;
+    wire(s->pher_buf[0], "pher0", P.guard); wire(s->pher_buf[1], "pher1", P.guard); wire(D.heur, "heur", P.guard); wire(D.ltab, "ltab");
+    wire(D.stamp, "stamp", P.sguard); wire(D.dirty_list, "dirty_list"); wire(D.dcount, "dcount");
+    wire(D.mask8, "mask8"); wire(D.mask, "mask"); wire(D.bestmark, "bestmark"); wire(D.bestpath, "bestpath"); wire(D.bestpos, "bestpos"); wire(D.besttabu, "besttabu"); wire(D.rtab, "rtab");
+    wire(D.paths, "paths"); wire(D.antL, "antL"); wire(D.antLen, "antLen"); wire(D.perm, "perm"); wire(D.depA, "depA"); wire(D.sortk, "sortk");
+    wire(D.vbits, "vbits"); wire(D.ctl, "ctl"); wire(D.rng, "rng"); wire(D.dbg, "dbg");
+    wire(D.ref_draws, "ref_draws"); wire(D.ref_state, "ref_state"); wire(D.ref_ok, "ref_ok"); wire(ref_jump, "ref_jump");
+    s->paths_arr[0] = s->paths_arr[1] = D.paths;   // (one array, unless the straggler group brought the second)
+    wire(s->paths_arr[1], "paths2"); wire(D.arr_len, "arr_len"); wire(D.arr_n, "arr_n"); wire(D.pool_rec, "pool_rec"); wire(D.pool_n, "pool_n"); wire(D.strag_cnt, "strag_cnt");
+    wire(s->d_starts, "d_starts"); wire(s->d_ends, "d_ends"); wire(s->d_streams, "d_streams"); wire(s->d_hslot, "d_hslot"); wire(s->d_hlist, "d_hlist"); wire(s->d_hends, "d_hends");
+    if (D.antLen) D.antRep = D.antLen + (size_t)n_slots * max_colony;   // (the replay flags: the upper half of the lengths' block)
+    D.ref_jump = ref_jump;
+    D.pher = s->pher_buf[0];
+    if (!e && wired != s->blocks.size()) e = hipErrorInvalidValue;   // (a row of the plan that nothing above takes)
+    if (e != hipSuccess) {
+        wa_acs_destroy(s);
+        return fail(ctx, WA_ERR_ALLOC, "wa_acs_create: device allocation failed: %s", hipGetErrorString(e));
     }
-    e = e ? e : ctx_alloc(ctx, &D.ltab, (size_t)path_capacity + 1);
-    // rank masks: a bit per depositing rank and edge.  At most 0.2 * colony + 1 ranks deposit (:200), so a solver for colonies
-    // of up to 35 ants (pair planning: 24) gets by with one BYTE per edge instead of a u64 (805 -> 101 MB per slot at 256^3);
-    // the byte array is padded to a multiple of 4 (the marks are 32-bit atomic ORs on the containing word)
-    const bool narrow_masks = (int32_t)(0.2 * max_colony) + 1 <= 8 && env_int("WA_MASK_U64", 0) == 0;
-    D.mask = nullptr; D.mask8 = nullptr;
-    if (narrow_masks) e = e ? e : ctx_alloc(ctx, &D.mask8, S * D.pher_stride + 4);
-    else e = e ? e : ctx_alloc(ctx, &D.mask, S * D.pher_stride);
-    e = e ? e : ctx_alloc(ctx, &D.bestmark, S * n);
-    e = e ? e : ctx_alloc(ctx, &D.bestpath, S * path_capacity);
-    e = e ? e : ctx_alloc(ctx, &D.bestpos, S * n);
-    e = e ? e : ctx_alloc(ctx, &D.besttabu, S * path_capacity);
-    if (lazy || env_int("WA_REPLAY", 1) != 0)   // replay table: 8 floats per best-path node (6 neighbours) / 32 (26 neighbours)
-        e = e ? e : ctx_alloc(ctx, &D.rtab, S * path_capacity * (nb == 6 ? 8 : WA_ROW26) + 256);
-    // ants' paths; solvers that hand stragglers over (see below) keep two such arrays and alternate by generation: a straggler's walk so far
-    // stays where it is and its resume block walks on in place while the next generation's ants write the other array
-    const bool strag_alloc = n_slots <= env_int("WA_STRAGGLER_SLOTS", 16) && !lazy && max_colony <= 256 && env_int("WA_STRAGGLERS", 1);
-    e = e ? e : ctx_alloc(ctx, &D.paths, S * C * path_capacity);
-    s->paths_arr[0] = s->paths_arr[1] = D.paths;   // (the second array comes with the straggler pools below, if there is room for it)
-    e = e ? e : ctx_alloc(ctx, &D.antL, S * C);
-    e = e ? e : ctx_alloc(ctx, &D.antLen, 2 * S * C);   // (+ the replay flags behind the lengths: one block, the allocator rounds every block up to its granule)
-    if (!e) D.antRep = D.antLen + S * C;
-    e = e ? e : ctx_alloc(ctx, &D.perm, S * C);
-    e = e ? e : ctx_alloc(ctx, &D.depA, S * C);
-    e = e ? e : ctx_alloc(ctx, &D.sortk, S * C * 2);
-    // stragglers (see WaAcsDev): dense searches (6 or 26 neighbours) of at most 256 ants, lists and pools PER SLOT (0.5 GB per slot at
-    // path_capacity 2^18), for solvers of up to WA_STRAGGLER_SLOTS (16) slots; WA_STRAGGLERS=0 switches the mechanism off
-    D.vbits_rows = max_colony + (strag_alloc ? WA_RESUME_MAX : 0);          // (+ the rows of the resume blocks)
-    const size_t vbits_rows = S * (size_t)D.vbits_rows;
-    e = e ? e : ctx_alloc(ctx, &D.vbits, vbits_rows * D.vbits_words);
-    e = e ? e : ctx_alloc(ctx, &D.ctl, S);
-    e = e ? e : ctx_alloc(ctx, &D.rng, 1);
-    e = e ? e : ctx_alloc(ctx, &D.dbg, 16);
-    // REF mode, converged colonies: the stream generated ahead for a generation, the kept states, the per-ant verdicts (see k_ref_draws).
-    // Only solvers that can run REF speculation carry them (6 neighbours, dense, WA_REF_SPEC != 0): ~24 KB per ant otherwise unused
-    if (s->ref_spec && !lazy) {
-        e = e ? e : ctx_alloc(ctx, &D.ref_draws, C * WA_REF_SPEC_LEN);
-        e = e ? e : ctx_alloc(ctx, &D.ref_state, (C * WA_REF_SPEC_LEN / 64 + 2 * (WA_REF_SUPER / 64) + 2) * 32);
-    } else {
-        s->ref_spec = false;
+    const double t_alloc = since0();
+    for (const WaBlock &b : s->blocks) {
+        if (b.row->fill == WA_FILL_NONE) continue;
+        const size_t bytes = (size_t)P.bytes(*b.row), skip = b.row->upper_half ? bytes / 2 : 0;
+        e = e ? e : hipMemsetAsync((char *)b.p + skip, b.row->fill == WA_FILL_ONES ? 0xff : 0, bytes - skip, ctx->stream);
     }
-    e = e ? e : ctx_alloc(ctx, &D.ref_ok, C + 2);
-    if (s->ref_spec) {   // the libc stream's jump matrix: state(n + WA_REF_SUPER) = J * state(n) over Z/2^32, state = (x[n-31] .. x[n-1]), x[n] = x[n-31] + x[n-3]
+    if (P.ref_spec) {   // the libc stream's jump matrix: state(n + WA_REF_SUPER) = J * state(n) over Z/2^32, state = (x[n-31] .. x[n-1]), x[n] = x[n-31] + x[n-3]
         // (glibc random_r.c TYPE_3): companion matrix to the power WA_REF_SUPER by repeated squaring
         static std::vector<uint32_t> J;
         if (J.empty()) {
@@ -288,61 +245,15 @@ static int acs_create_once(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, in
                     }
                 return Cm;
             };
-            std::vector<uint32_t> P(31 * 31, 0u), Rm(31 * 31, 0u);
-            for (int j = 0; j < 30; j++) P[j * 31 + j + 1] = 1u;      // s'[j] = s[j + 1]
-            P[30 * 31 + 0] = 1u; P[30 * 31 + 28] = 1u;                // s'[30] = s[0] + s[28]
+            std::vector<uint32_t> Pm(31 * 31, 0u), Rm(31 * 31, 0u);
+            for (int j = 0; j < 30; j++) Pm[j * 31 + j + 1] = 1u;     // s'[j] = s[j + 1]
+            Pm[30 * 31 + 0] = 1u; Pm[30 * 31 + 28] = 1u;              // s'[30] = s[0] + s[28]
             for (int i = 0; i < 31; i++) Rm[i * 31 + i] = 1u;
-            for (int k = WA_REF_SUPER; k; k >>= 1) { if (k & 1) Rm = mul(Rm, P); P = mul(P, P); }
+            for (int k = WA_REF_SUPER; k; k >>= 1) { if (k & 1) Rm = mul(Rm, Pm); Pm = mul(Pm, Pm); }
             J = Rm;
         }
-        uint32_t *dj = nullptr;
-        e = e ? e : ctx_alloc(ctx, &dj, (size_t)31 * 31);
-        if (!e) e = hipMemcpyAsync(dj, J.data(), sizeof(uint32_t) * 31 * 31, hipMemcpyHostToDevice, ctx->stream);   // (in stream order: see ltab below)
-        D.ref_jump = dj;
+        e = e ? e : hipMemcpyAsync(ref_jump, J.data(), sizeof(uint32_t) * 31 * 31, hipMemcpyHostToDevice, ctx->stream);   // (in stream order: see ltab below)
     }
-    if (!e) e = hipMemsetAsync(D.ref_ok, 0, sizeof(int32_t) * (C + 2), ctx->stream);
-    D.arr_len = nullptr; D.arr_n = nullptr; D.pool_n = nullptr; D.pool_rec = nullptr; D.prev_paths = nullptr; D.prev_pher = nullptr; D.strag_cnt = nullptr;
-    if (strag_alloc && !e) {
-        // (the pools are an optimisation: a device that has no room for them runs the solver without the hand-over instead of failing)
-        hipError_t pe = hipSuccess;
-        int32_t *paths2 = nullptr;
-        pe = pe ? pe : ctx_alloc(ctx, &paths2, S * C * path_capacity);   // the second paths array: a straggler's walk so far stays where it is
-        pe = pe ? pe : ctx_alloc(ctx, &D.arr_len, S * 256);
-        pe = pe ? pe : ctx_alloc(ctx, &D.arr_n, S);
-        pe = pe ? pe : ctx_alloc(ctx, &D.pool_rec, S * 2 * WA_RESUME_MAX * WA_POOL_REC);
-        pe = pe ? pe : ctx_alloc(ctx, &D.pool_n, S * 2);
-        pe = pe ? pe : ctx_alloc(ctx, &D.strag_cnt, S * 2);
-        pe = pe ? pe : hipMemsetAsync(D.strag_cnt, 0, sizeof(unsigned long long) * S * 2, ctx->stream);
-        pe = pe ? pe : hipMemsetAsync(D.arr_len, 0xff, sizeof(uint32_t) * S * 256, ctx->stream);
-        pe = pe ? pe : hipMemsetAsync(D.arr_n, 0, sizeof(uint32_t) * S, ctx->stream);
-        pe = pe ? pe : hipMemsetAsync(D.pool_n, 0, sizeof(int32_t) * S * 2, ctx->stream);
-        if (pe != hipSuccess) {
-            // (without pools the resume blocks' bitmap rows are simply never used)
-            (void)hipGetLastError();
-            ctx_free(ctx, paths2); ctx_free(ctx, D.arr_len); ctx_free(ctx, D.arr_n); ctx_free(ctx, D.pool_rec); ctx_free(ctx, D.pool_n); ctx_free(ctx, D.strag_cnt);
-            D.arr_len = nullptr; D.arr_n = nullptr; D.pool_n = nullptr; D.pool_rec = nullptr; D.strag_cnt = nullptr;
-            // (nothing is ever handed over: one paths array is in use)
-        } else {
-            s->paths_arr[1] = paths2;
-        }
-    }
-    e = e ? e : ctx_alloc(ctx, &s->d_starts, S);
-    e = e ? e : ctx_alloc(ctx, &s->d_ends, S);
-    e = e ? e : ctx_alloc(ctx, &s->d_streams, S);
-    e = e ? e : ctx_alloc(ctx, &s->d_hslot, S);
-    e = e ? e : ctx_alloc(ctx, &s->d_hlist, S);
-    e = e ? e : ctx_alloc(ctx, &s->d_hends, S);
-    if (e != hipSuccess) {
-        wa_acs_destroy(s);
-        return fail(ctx, WA_ERR_ALLOC, "wa_acs_create: device allocation failed: %s", hipGetErrorString(e));
-    }
-    const double t_alloc = since0();
-    if (D.mask) e = e ? e : (hipMemsetAsync(D.mask, 0, sizeof(unsigned long long) * S * D.pher_stride, ctx->stream));
-    if (D.mask8) e = e ? e : (hipMemsetAsync(D.mask8, 0, S * D.pher_stride + 4, ctx->stream));
-    D.pher = s->pher_buf[0];
-    s->cur_buf = 0;
-    e = e ? e : (hipMemsetAsync(s->pher_alloc[0], 0, sizeof(float) * (S * D.pher_stride + 2 * guard), ctx->stream));
-    if (s->pher_alloc[1]) e = e ? e : (hipMemsetAsync(s->pher_alloc[1], 0, sizeof(float) * (S * D.pher_stride + 2 * guard), ctx->stream));
     {   // L as a function of the step count: `distance` (== precision, :378) added once per step in fp32 (:78) -- a
         // sequential chain, so it is run once here on the host (this TU is built with -ffp-contract=off) and uploaded
         std::vector<float> &lt = s->ltab_host;            // (lives as long as the solver: the asynchronous copy below may still read it after this function)
@@ -354,15 +265,6 @@ static int acs_create_once(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, in
         // the fill landed on top of the table, every arrival's L read NaN, the search never found a best (round 5, profiles/HISTORY.md).
         e = e ? e : hipMemcpyAsync(D.ltab, lt.data(), sizeof(float) * lt.size(), hipMemcpyHostToDevice, ctx->stream);
     }
-    if (lazy) {
-        e = e ? e : (hipMemsetAsync(s->stamp_alloc, 0, sizeof(uint32_t) * S * n + 2 * (size_t)D.stamp_guard_bytes, ctx->stream));
-        e = e ? e : (hipMemsetAsync(D.dcount, 0, sizeof(int32_t) * S * 2, ctx->stream));
-    }
-    e = e ? e : (hipMemsetAsync(D.bestmark, 0, sizeof(uint32_t) * S * n, ctx->stream));
-    e = e ? e : (hipMemsetAsync(D.antRep, 0, sizeof(int32_t) * S * C, ctx->stream));
-    e = e ? e : (hipMemsetAsync(D.vbits, 0, sizeof(uint32_t) * vbits_rows * D.vbits_words, ctx->stream));
-    e = e ? e : (hipMemsetAsync(D.ctl, 0, sizeof(WaSlotCtl) * S, ctx->stream));
-    e = e ? e : (hipMemsetAsync(D.dbg, 0, sizeof(unsigned long long) * 16, ctx->stream));
     WaGlibcRand r0;
     wa_glibc_seed(&r0, 1);  // a process that never calls srand() behaves as srand(1)
     e = e ? e : (hipMemcpyAsync(D.rng, &r0, sizeof r0, hipMemcpyHostToDevice, ctx->stream));
@@ -383,81 +285,59 @@ static int acs_create_once(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, in
     return WA_OK;
 }
 
-// What acs_create allocates, per slot / per heuristic field / once, without allocating anything: the drop-in's pair loop sizes
-// its slot count from this and wa_ctx_memory_info (tests/test_gpu_shard_sizing.py holds it against the allocator's own numbers).
+// (a solver whose arrays were served from kept blocks somewhat larger than asked for -- the arena's way of not re-mapping everything for
+//  every slightly different shape -- can fail to fit where exact blocks would: one more attempt with exact sizes only)
+static int acs_create(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, int32_t max_colony, int64_t path_capacity, int32_t nb, bool lazy, wa_acs **out)
+{
+    WaDevGuard dev_guard_(ctx);
+    if (!dev_guard_.ok) return WA_ERR_DEVICE;   // the context's device could not be made current
+    int rc = acs_create_once(ctx, grid, n_slots, max_colony, path_capacity, nb, lazy, out);
+    if (rc == WA_ERR_ALLOC && ctx && ctx->arena_on && !ctx->arena_strict) {
+        ctx->arena_strict = true;
+        rc = acs_create_once(ctx, grid, n_slots, max_colony, path_capacity, nb, lazy, out);
+        ctx->arena_strict = false;
+    }
+    return rc;
+}
+
+// What acs_create allocates, per slot / per heuristic field / once, without allocating anything: sums over the solver's plan (acs_plan.hpp;
+// a dense solver under WA_REPLAY=0 has no replay table, here as there).  The drop-in's pair loop sizes its slot count from this and
+// wa_ctx_memory_info (tests/test_gpu_shard_sizing.py holds it against the allocator's own numbers).
 int wa_acs_memory_estimate(const wa_grid *grid, int32_t max_colony, int64_t path_capacity, int32_t neighbourhood, int32_t lazy,
                            int64_t *bytes_per_slot, int64_t *bytes_per_heuristic_field, int64_t *bytes_fixed)
 {
     if (!grid || max_colony < 1 || (neighbourhood != 6 && neighbourhood != 26)) return WA_ERR_ARG;
-    const int64_t n = grid->d.n, C = max_colony, nb = neighbourhood;
-    if (path_capacity <= 0) path_capacity = n < (1 << 18) ? n : (1 << 18);
-    if (path_capacity > n) path_capacity = n;
-    if (path_capacity < 2) path_capacity = 2;
-    const int64_t stride = ((nb * n + 63) / 64) * 64, cap = path_capacity;
-    const int64_t guard = nb == 6 ? (((int64_t)2 * grid->d.nxy * 6 + 64 + 63) / 64) * 64 : 0;
-    const bool narrow = (int32_t)(0.2 * max_colony) + 1 <= 8 && env_int("WA_MASK_U64", 0) == 0;
-    int64_t slot = 4 * stride * (lazy ? 1 : 2);                      // pheromone (the dense sweep is out of place: two fields)
-    if (lazy) slot += 4 * n + 4 * n + 8;                             // stamps, dirty list, counters
-    slot += narrow ? stride : 8 * stride;                            // deposit rank masks
-    slot += 4 * n + 4 * n;                                           // best-path stamps and positions
-    slot += 4 * cap + cap + 4 * cap * (nb == 6 ? 8 : WA_ROW26);      // best path, its prefix-tabu bits, replay table
-    slot += C * (4 * cap + 4 * ((n + 31) / 32) + 4 + 4 + 4 + 4 + 4 + 8); // per ant: path, spill bitmap, L, length, replay flag, rank, deposit, sort scratch
-    slot += (int64_t)sizeof(WaSlotCtl) + 8 + 8 + 4 + 4 + 4 + 4;
-    if (bytes_per_slot) *bytes_per_slot = slot;
-    if (bytes_per_heuristic_field) *bytes_per_heuristic_field = 4 * stride;   // (the pool starts with min(n_slots, 4) fields; from 32 slots on with n_slots / 8, between 8 and 24)
-    int64_t fixed = 4 * 2 * guard * (lazy ? 2 : 3) + 4 * (cap + 1) + 4096;   // guard bands, L table, small blocks
-    // REF mode's speculation buffers (per solver: the stream generated ahead for a generation and the kept states, ~24 KB per ant): dense
-    // 6-neighbour solvers only (acs_create: ref_spec)
-    if (nb == 6 && !lazy && env_int("WA_REF_SPEC", 1) != 0)
-        fixed += 4 * C * WA_REF_SPEC_LEN + 4 * 32 * (C * WA_REF_SPEC_LEN / 64 + 2 * (WA_REF_SUPER / 64) + 2) + 4 * 31 * 31;
-    if (bytes_fixed) *bytes_fixed = fixed;
+    const WaPlanSums sums = wa_plan_estimate(acs_plan_in(grid, 1, max_colony, path_capacity, neighbourhood, lazy != 0));
+    if (bytes_per_slot) *bytes_per_slot = sums.per_slot;
+    if (bytes_per_heuristic_field) *bytes_per_heuristic_field = sums.per_field;   // (the pool starts with WaAcsPlan::fields0 of them)
+    if (bytes_fixed) *bytes_fixed = sums.fixed;
     return WA_OK;
 }
 
-// The straggler lists and pools acs_create adds for a dense solver of at most 256 ants and at most WA_STRAGGLER_SLOTS (16) slots:
-// per slot a second paths array (max_colony paths) + WA_RESUME_MAX spill-bitmap rows + the small lists (same conditions as strag_alloc there)
+// What the straggler group adds to a solver of this shape (the plan with the group minus the plan without it: the group's own blocks
+// and the resume blocks' spill-bitmap rows), 0 for a solver that gets none
 int wa_acs_straggler_pool_bytes(const wa_grid *grid, int32_t n_slots, int32_t max_colony, int64_t path_capacity, int32_t neighbourhood,
                                 int32_t lazy, int64_t *bytes)
 {
     if (!grid || !bytes || n_slots < 1 || max_colony < 1 || (neighbourhood != 6 && neighbourhood != 26)) return WA_ERR_ARG;
-    const int64_t n = grid->d.n;
-    if (path_capacity <= 0) path_capacity = n < (1 << 18) ? n : (1 << 18);
-    if (path_capacity > n) path_capacity = n;
-    if (path_capacity < 2) path_capacity = 2;
-    *bytes = 0;
-    if (lazy || max_colony > 256 || n_slots > env_int("WA_STRAGGLER_SLOTS", 16) || !env_int("WA_STRAGGLERS", 1)) return WA_OK;
-    const int64_t per_slot = (int64_t)max_colony * path_capacity * 4 + (int64_t)WA_RESUME_MAX * ((n + 31) / 32) * 4 +
-                             (int64_t)2 * WA_RESUME_MAX * WA_POOL_REC * 4 + 256 * 4 + 4 + 8;
-    *bytes = per_slot * n_slots;
+    *bytes = wa_plan_pool_bytes(acs_plan_in(grid, n_slots, max_colony, path_capacity, neighbourhood, lazy != 0));
     return WA_OK;
 }
 
-int wa_acs_create(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, int32_t max_colony, int64_t path_capacity,
-                  wa_acs **out)
+int wa_acs_create(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, int32_t max_colony, int64_t path_capacity, wa_acs **out)
 {
-    WaDevGuard dev_guard_(ctx);
-    if (!dev_guard_.ok) return WA_ERR_DEVICE;   // the context's device could not be made current
     return acs_create(ctx, grid, n_slots, max_colony, path_capacity, 6, false, out);
 }
-int wa_acs_create_nb(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, int32_t max_colony, int64_t path_capacity,
-                     int32_t neighbourhood, wa_acs **out)
+int wa_acs_create_nb(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, int32_t max_colony, int64_t path_capacity, int32_t neighbourhood, wa_acs **out)
 {
-    WaDevGuard dev_guard_(ctx);
-    if (!dev_guard_.ok) return WA_ERR_DEVICE;   // the context's device could not be made current
     return acs_create(ctx, grid, n_slots, max_colony, path_capacity, neighbourhood, false, out);
 }
-int wa_acs_create_lazy(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, int32_t max_colony, int64_t path_capacity,
-                       wa_acs **out)
+int wa_acs_create_lazy(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, int32_t max_colony, int64_t path_capacity, wa_acs **out)
 {
-    WaDevGuard dev_guard_(ctx);
-    if (!dev_guard_.ok) return WA_ERR_DEVICE;   // the context's device could not be made current
     return acs_create(ctx, grid, n_slots, max_colony, path_capacity, 6, true, out);
 }
-int wa_acs_create_lazy_nb(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, int32_t max_colony, int64_t path_capacity,
-                          int32_t neighbourhood, wa_acs **out)
+int wa_acs_create_lazy_nb(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, int32_t max_colony, int64_t path_capacity, int32_t neighbourhood, wa_acs **out)
 {
-    WaDevGuard dev_guard_(ctx);
-    if (!dev_guard_.ok) return WA_ERR_DEVICE;   // the context's device could not be made current
     return acs_create(ctx, grid, n_slots, max_colony, path_capacity, neighbourhood, true, out);
 }
 
@@ -483,13 +363,7 @@ void wa_acs_destroy(wa_acs *s)
     for (auto st : s->gstream) { hipStreamSynchronize(st); hipStreamDestroy(st); }
     for (auto ev : s->gjoin) hipEventDestroy(ev);
     if (s->gfork) hipEventDestroy(s->gfork);
-    WaAcsDev &D = s->D;
-    ctx_free(s->ctx, s->pher_alloc[0]); ctx_free(s->ctx, s->pher_alloc[1]); ctx_free(s->ctx, s->heur_alloc); ctx_free(s->ctx, D.ltab); ctx_free(s->ctx, D.mask); ctx_free(s->ctx, D.mask8); ctx_free(s->ctx, D.bestmark); ctx_free(s->ctx, D.bestpath); ctx_free(s->ctx, D.bestpos); ctx_free(s->ctx, D.besttabu); ctx_free(s->ctx, D.rtab);
-    if (s->paths_arr[1] != s->paths_arr[0]) ctx_free(s->ctx, s->paths_arr[1]);
-    ctx_free(s->ctx, s->paths_arr[0]); ctx_free(s->ctx, D.antL); ctx_free(s->ctx, D.antLen); ctx_free(s->ctx, D.perm); ctx_free(s->ctx, D.depA);
-    ctx_free(s->ctx, D.sortk); ctx_free(s->ctx, D.vbits); ctx_free(s->ctx, D.ctl); ctx_free(s->ctx, D.rng); ctx_free(s->ctx, D.dbg); ctx_free(s->ctx, D.ref_draws); ctx_free(s->ctx, D.ref_state); ctx_free(s->ctx, D.ref_ok); ctx_free(s->ctx, const_cast<uint32_t *>(D.ref_jump)); ctx_free(s->ctx, D.arr_len); ctx_free(s->ctx, D.arr_n); ctx_free(s->ctx, D.pool_n); ctx_free(s->ctx, D.pool_rec); ctx_free(s->ctx, D.strag_cnt);
-    ctx_free(s->ctx, s->stamp_alloc); ctx_free(s->ctx, D.dirty_list); ctx_free(s->ctx, D.dcount);
-    ctx_free(s->ctx, s->d_starts); ctx_free(s->ctx, s->d_ends); ctx_free(s->ctx, s->d_streams); ctx_free(s->ctx, s->d_hslot); ctx_free(s->ctx, s->d_hlist); ctx_free(s->ctx, s->d_hends);
+    for (const WaBlock &b : s->blocks) ctx_free(s->ctx, b.p);
     free_trace(s);
     delete s;
 }

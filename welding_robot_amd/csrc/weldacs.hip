@@ -37,6 +37,7 @@
 #include "seamtour_kernels.hpp"
 #include "torch_kernels.hpp"
 #include "stl_text.hpp"
+#include "acs_plan.hpp"
 
 // ------------------------------------------------------------------ handles
 struct WaDevBlock { void *p; size_t bytes; unsigned long long stamp; };
@@ -108,12 +109,15 @@ struct wa_bspline {
     bool h_valid = false;
 };
 struct EvPair { hipEvent_t a, b; int cls; };
+struct WaBlock { const WaPlanRow *row; void *p; };   // a block the solver was given for a row of its plan
 struct wa_acs {
-    wa_ctx *ctx;
-    const wa_grid *grid;
-    int32_t n_slots, max_colony, n_active, nb;
-    int64_t path_cap;
-    WaAcsDev D;            // D.pher always points at the CURRENT pheromone buffer
+    wa_ctx *ctx = nullptr;
+    const wa_grid *grid = nullptr;
+    int32_t n_slots = 0, max_colony = 0, n_active = 0, nb = 6;
+    int64_t path_cap = 0;
+    WaAcsDev D = {};       // D.pher always points at the CURRENT pheromone buffer
+    WaAcsPlan plan;                  // the solver's device blocks (acs_plan.hpp) ...
+    std::vector<WaBlock> blocks;     // ... and what it was given for them, in the plan's order: wa_acs_destroy gives exactly these back
     int32_t *d_stage = nullptr;      // staging block of acs_fetch_results (the best paths of all slots, packed), grows on demand
     size_t stage_words = 0;
     // host copy of every slot's control block and best path behind the last run (acs_fetch_results): wa_acs_result / _batch read it
@@ -123,43 +127,40 @@ struct wa_acs {
     int64_t res_longest = 0;
     bool res_valid = false;
     int32_t *paths_arr[2] = {nullptr, nullptr};   // the ants' paths: one array ([1] == [0]), or two alternating by generation when stragglers are handed over
-    float *pher_buf[2];    // double buffer: evaporation writes the other one (dst = src * rho)
-    float *pher_alloc[2], *heur_alloc;   // the allocations behind pher_buf[] / D.heur (fields + guard bands)
-    uint32_t *stamp_alloc;               // ... and D.stamp (lazy solvers)
-    int cur_buf;
+    float *pher_buf[2] = {nullptr, nullptr};      // double buffer: evaporation writes the other one (dst = src * rho); the fields behind the blocks' guard bands
+    int cur_buf = 0;
     std::vector<int> slot_buf;           // which of the two buffers holds slot q's current field (inactive slots do not follow the flips)
-    bool walk_asm;         // hand-scheduled walk loop (default); WA_WALK_ASM=0 keeps the compiler-scheduled one
-    int walk_warm;         // touch loads in the hand-scheduled loop: -1 by launch size (wa_acs_run), 0 / 1 forced (WA_WALK_WARM)
-    int32_t last_walk[4];  // wa_acs_walk_info
+    bool walk_asm = true;  // hand-scheduled walk loop (default); WA_WALK_ASM=0 keeps the compiler-scheduled one
+    int walk_warm = -1;    // touch loads in the hand-scheduled loop: -1 by launch size (wa_acs_run), 0 / 1 forced (WA_WALK_WARM)
+    int32_t last_walk[4] = {0, 0, 0, 0};   // wa_acs_walk_info
 #ifdef WA_STATE_HASH
     unsigned long long *d_hashlog = nullptr;   // [WA_HASH_GENS][3][n_slots][8], diagnostic build only (k_state_hash)
 #endif
-    int tab16_env, id_bits; // WA_TAB16 (-1 by rule, 0 never, 1 wherever possible); bits of the grid's voxel ids
-    int lds_pad;           // WA_WALK_LDS_PAD: experiment knob, extra dynamic LDS per walk block (occupancy at a constant table)
-    int walk_direct;       // the loop WITHOUT look-ahead for saturated launches: -1 by rule (walk_direct_rule), 0 / 1 forced (WA_WALK_DIRECT)
-    int walk_flags;        // k_walk_dev's switches: hand-scheduled loop, re-entry onto the replay track (WA_REENTRY=0: off), see acs_create
-    WaRun R;
-    bool begun;
-    bool lazy;                          // lazy evaporation (wa_acs_create_lazy): never-deposited voxels are not swept
+    int tab16_env = -1, id_bits = 0; // WA_TAB16 (-1 by rule, 0 never, 1 wherever possible); bits of the grid's voxel ids
+    int lds_pad = 0;       // WA_WALK_LDS_PAD: experiment knob, extra dynamic LDS per walk block (occupancy at a constant table)
+    int walk_direct = -1;  // the loop WITHOUT look-ahead for saturated launches: -1 by rule (walk_direct_rule), 0 / 1 forced (WA_WALK_DIRECT)
+    int walk_flags = 0;    // k_walk_dev's switches: hand-scheduled loop, re-entry onto the replay track (WA_REENTRY=0: off), see acs_create
+    WaRun R = {};
+    bool begun = false;
+    bool lazy = false;                  // lazy evaporation (wa_acs_create_lazy): never-deposited voxels are not swept
     std::vector<int> lazy_mode;         // per slot: init mode of the stored records (-1 unknown)
     std::vector<float> lazy_p0;
-    int32_t gens_enqueued, colony_bound, hash_log2, evap_blocks, lazy_blocks_env, straggler_gens = 64;
-    long long *d_starts, *d_ends;
-    uint32_t *d_streams;
-    int32_t *d_hslot, *d_hlist, *d_hends;   // per search: the heuristic field it reads / the fields wa_acs_begin computes and their end points
-    int32_t heur_fields;                // fields in the pool (heur_alloc): grows on demand, at most one per slot
-    size_t heur_guard;                  // floats of guard band around the pool
+    int32_t gens_enqueued = 0, colony_bound = 0, hash_log2 = 0, evap_blocks = 0, lazy_blocks_env = 0, straggler_gens = 64;
+    long long *d_starts = nullptr, *d_ends = nullptr;
+    uint32_t *d_streams = nullptr;
+    int32_t *d_hslot = nullptr, *d_hlist = nullptr, *d_hends = nullptr;   // per search: the heuristic field it reads / the fields wa_acs_begin computes and their end points
+    int32_t heur_fields = 0;            // fields in the pool (the plan's "heur" block): grows on demand, at most one per slot
     std::vector<long long> heur_end;    // per field: the end point it holds (-1: none), the beta it was computed with,
     std::vector<float> heur_beta;       // ... and the last wa_acs_begin that used it (oldest goes first)
     std::vector<long long> heur_used;
-    long long heur_batch;
+    long long heur_batch = 0;
     // profiling
-    bool prof, prof_sweep_all;   // prof_sweep_all: the sweep-carrying launch of EVERY generation carries its own start/stop events
-    bool prof_paired;            // a stamped no-op dispatch in front of every timed sweep-carrying launch (prof_pair_marker)
-    int32_t prof_every;
+    bool prof = false, prof_sweep_all = false;   // prof_sweep_all: the sweep-carrying launch of EVERY generation carries its own start/stop events
+    bool prof_paired = false;    // a stamped no-op dispatch in front of every timed sweep-carrying launch (prof_pair_marker)
+    int32_t prof_every = 1;
     std::vector<EvPair> ev;
-    double prof_ms[WA_K_COUNT];
-    int64_t prof_n[WA_K_COUNT];
+    double prof_ms[WA_K_COUNT] = {};
+    int64_t prof_n[WA_K_COUNT] = {};
     // pipelined groups (wa_acs_run): the active slots split into groups, each with a stream of its own, so that one group's HBM-bound
     // sweep runs under another group's latency-bound walk.  Forked from / joined into the context's stream inside every wa_acs_run call.
     int32_t pipe_groups_env = 0;         // WA_PIPE_GROUPS, read at creation (0: by rule)
