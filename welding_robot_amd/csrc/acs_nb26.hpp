@@ -44,8 +44,9 @@ __device__ __forceinline__ void wa_table26_lengths(const WaAcsDev &D, const WaRu
 // One wavefront per best-path node (wave w of n_waves takes nodes w, w + n_waves, ...): the walk's own step evaluation with
 // visited set = best[0..i].  apply_here: the row first applies the pending ranked deposits (mask != 0) of its 26 edges -- same
 // adds, same ascending rank order as wa_apply_body, which skips edges leaving a best-path node when it shares the launch.
+// dep_lane, n_dep: the deposit coefficients, rank bit l in lane l, and how many ranks deposit (wa_add_ranked).
 __device__ __forceinline__ void wa_table26_rows(const WaAcsDev &D, const WaRun &R, int32_t slot, int32_t w, int32_t n_waves, bool apply_here,
-                                                const float *s_dep)
+                                                float dep_lane, int32_t n_dep)
 {
     const int lane = threadIdx.x & 63;
     const WaSlotCtl *ctl = &D.ctl[slot];
@@ -70,35 +71,38 @@ __device__ __forceinline__ void wa_table26_rows(const WaAcsDev &D, const WaRun &
     const uint32_t *stamp = D.stamp ? D.stamp + (int64_t)slot * D.d.n : nullptr;
     const float clean_now = ctl->clean[ctl->gen & 1];
     const uint32_t evap_tab = ctl->evap_base + (uint32_t)ctl->gen;   // the fused launch already counted this generation
+    // second term of :211, `(float)onbest * lambda * Q / bestL`: one of two values, each evaluated once and exactly as that expression groups
+    const float bonus_on = wa_uniform(1.f * lambda * Q / bestL), bonus_off = wa_uniform(0.f * lambda * Q / bestL);
     for (int32_t i = w; i < blen - 1; i += n_waves) {   // decisions exist at nodes 0 .. blen-2
         const int32_t v = bpath[i] & WaNbT<26>::IDM;
         float p = -0.f, h = 0.f;
         bool adm = false;
+        const int64_t e = (int64_t)v * 26 + k;
+        int32_t nb = 0;
+        uint32_t mk = 0u;
+        unsigned long long m = 0ULL;
         if (lane < 26) {
-            const int64_t e = (int64_t)v * 26 + lane;
             p = pher[e];
             h = heur[e];
             if (stamp) {
                 const uint32_t stv = stamp[v];
                 p = stv == 0 ? copysignf(clean_now, p) : copysignf(wa_catch_up(fabsf(p), evap_tab + 1u - stv, R.rho), p);
             }
-            int32_t nb = v + dk;
+            nb = v + dk;
             nb = nb < 0 ? 0 : nb > last_id ? last_id : nb;    // (an out-of-bounds edge is inadmissible by its sign bit whatever is found here)
-            const uint32_t mk = mark[nb];
-            unsigned long long m = apply_here ? wa_mask_get(mask, e) : 0ULL;
-            if (m) {  // somebody walked (v, lane): the ranked deposits in ascending rank order (:210-211); v is on the best path (:209)
-                const float bonus = (float)(mk == ver) * lambda * Q / bestL;
-                while (m) {
-                    const int bq = __ffsll((long long)m) - 1;
-                    m &= m - 1;
-                    p += s_dep[bq] + bonus;
-                }
+            mk = mark[nb];
+            m = apply_here ? wa_mask_get(mask, e) : 0ULL;
+        }
+        if (apply_here) {  // the whole wavefront: lanes 26.. have no edge (m == 0)
+            // somebody walked (v, lane): the ranked deposits in ascending rank order (:210-211); v is on the best path (:209)
+            p = wa_add_ranked(p, m, dep_lane, mk == ver ? bonus_on : bonus_off, n_dep);
+            if (m) {
                 pher[e] = p;
                 wa_mask_clear(mask, e);
             }
-            if ((__float_as_uint(p) >> 31) == 0)              // in bounds and free (:148)
-                adm = !(mk == ver && pos[nb] <= i);           // not on the prefix best[0..i] (:145-146)
         }
+        if (lane < 26 && (__float_as_uint(p) >> 31) == 0)     // in bounds and free (:148)
+            adm = !(mk == ver && pos[nb] <= i);               // not on the prefix best[0..i] (:145-146)
         const float info = wa_powi(fabsf(p), R.alpha) * h;    // :154
         const float a = adm ? info : 0.f;
         float t = 0.f + a, c = 0.f + a;
@@ -117,7 +121,7 @@ __global__ __launch_bounds__(64) void k_replay_table26(WaAcsDev D, WaRun R)
 {
     __shared__ float s_d[1024];
     if (blockIdx.x == 0) wa_table26_lengths(D, R, blockIdx.y, s_d);
-    else wa_table26_rows(D, R, blockIdx.y, (int32_t)blockIdx.x - 1, (int32_t)gridDim.x - 1, false, nullptr);
+    else wa_table26_rows(D, R, blockIdx.y, (int32_t)blockIdx.x - 1, (int32_t)gridDim.x - 1, false, 0.f, 0);
 }
 // Deposit apply + replay table of the 26-neighbour search in ONE launch, like k_apply_table: block 0 = arrival lengths,
 // blocks [1, 1 + WA_TABLE26_BLOCKS) = table rows (four wavefronts each) that also apply the deposits on edges leaving a
@@ -126,7 +130,6 @@ __global__ __launch_bounds__(64) void k_replay_table26(WaAcsDev D, WaRun R)
 __global__ __launch_bounds__(256) void k_apply_table26(WaAcsDev D, WaRun R)
 {
     __shared__ float s_d[1024];
-    __shared__ float s_dep[64];
     const int32_t slot = blockIdx.y, tid = threadIdx.x;
     // lazy evaporation: voxels that became dirty in this generation join the swept set from the next sweep on (see k_apply_table)
     if (D.dcount && blockIdx.x == 0 && tid == 0) D.dcount[slot * 2] = D.dcount[slot * 2 + 1];
@@ -137,15 +140,13 @@ __global__ __launch_bounds__(256) void k_apply_table26(WaAcsDev D, WaRun R)
     }
     if (blockIdx.x == 0) { wa_table26_lengths(D, R, slot, s_d); return; }
     if ((int32_t)blockIdx.x <= WA_TABLE26_BLOCKS) {
-        const float dep_mine = (tid < 64 && tid < D.max_colony) ? D.depA[(int64_t)slot * D.max_colony + tid] : 0.f;
+        const float dep_lane = (tid & 63) < D.max_colony ? D.depA[(int64_t)slot * D.max_colony + (tid & 63)] : 0.f;   // rank bit l in lane l of every wavefront
         const int32_t n_dep = D.ctl[slot].n_dep;
-        if (tid < 64) s_dep[tid] = tid < n_dep ? dep_mine : 0.f;
-        __syncthreads();
-        wa_table26_rows(D, R, slot, ((int32_t)blockIdx.x - 1) * 4 + (tid >> 6), WA_TABLE26_BLOCKS * 4, true, s_dep);
+        wa_table26_rows(D, R, slot, ((int32_t)blockIdx.x - 1) * 4 + (tid >> 6), WA_TABLE26_BLOCKS * 4, true, dep_lane, n_dep < 64 ? n_dep : 64);
         return;
     }
     const int32_t ab = (int32_t)blockIdx.x - 1 - WA_TABLE26_BLOCKS;  // (bx = ab & 7, rank bit = ab >> 3)
-    wa_apply_body<26>(D, slot, 0, ab >> 3, ab & 7, 8, true, s_dep);
+    wa_apply_body<26>(D, slot, 0, ab >> 3, ab & 7, 8, true);
 }
 
 // one lane per node, 64 nodes per ballot.  Returns 1 dead end at node i, 2 arrived, 3 deviates at node i (i in `node`).

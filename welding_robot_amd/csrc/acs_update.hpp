@@ -580,20 +580,44 @@ __global__ __launch_bounds__(256) void k_deposit_mark(WaAcsDev D, int32_t base)
         wa_mask_or(mask, e, bit);
     }
 }
+// The deposits of the ranks present on one edge: p += dep[b] + bonus for every set bit b of m, lowest rank first -- the adds of
+// :210-211 one by one, in the reference's order (no add is merged, reordered or contracted).  The whole wavefront calls this together,
+// each lane with its own edge (m == 0: nothing to add there).  dep_lane: lane l holds the coefficient of rank bit l of the chunk;
+// n: depositing ranks of the chunk (<= 64; no mask has a bit at or above it).  The loop is uniform over the rank bits and takes a
+// coefficient out of dep_lane as a scalar, so a trip is a handful of register instructions: nothing in it reads memory or LDS, waits
+// for either, or branches by lane (the loop this replaces went through LDS once per set bit, each trip behind the one before).
+// Groups of eight rank bits that no lane of the wavefront carries are stepped over, and the loop ends behind the last one any lane carries.
+__device__ __forceinline__ float wa_add_ranked(float p, unsigned long long m, float dep_lane, float bonus, int32_t n)
+{
+    n = __builtin_amdgcn_readfirstlane(n);
+    asm volatile("" : "+v"(p));   // the edge's record has arrived here: no trip of the loop waits for a load
+    for (int32_t b0 = 0; b0 < n; b0 += 8) {
+        const unsigned long long rest = m >> b0;
+        if (__ballot(rest != 0) == 0) break;
+        const uint32_t r8 = (uint32_t)rest & 0xffu;
+        if (__ballot(r8 != 0) == 0) continue;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const float t = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dep_lane), b0 + j)) + bonus;
+            p = ((r8 >> j) & 1u) ? p + t : p;
+        }
+    }
+    return p;
+}
 // Body of the apply pass for rank bit `bit` of chunk `base`, x-block `bx` of `nbx`.  skip_best_src: edges that
 // leave a best-path node belong to the replay-table rows of the same launch (k_apply_table).
 template <int NB>
 __device__ __forceinline__ void wa_apply_body(const WaAcsDev &D, int32_t slot, int32_t base, int32_t bit, int32_t bx, int32_t nbx,
-                                              bool skip_best_src, float *s_dep)
+                                              bool skip_best_src)
 {
     // The kernel is a chain of dependent global loads (control block -> rank -> ant -> path word -> edge record),
     // so loads are issued as early as their addresses are known, speculatively where a bound is not yet known
     // (always inside the allocation): three dependent levels instead of eight.
     const int32_t o = base + bit + 1;
-    const int32_t tid = threadIdx.x, C = D.max_colony;
+    const int32_t tid = threadIdx.x, lane = tid & 63, C = D.max_colony;
     const WaSlotCtl *c = &D.ctl[slot];
-    // level 1: addresses that depend only on the launch geometry
-    const float dep_mine = (tid < 64 && base + tid < C) ? D.depA[(int64_t)slot * C + base + tid] : 0.f;
+    // level 1: addresses that depend only on the launch geometry (every wavefront keeps the chunk's coefficients, one per lane)
+    const float dep_lane = base + lane < C ? D.depA[(int64_t)slot * C + base + lane] : 0.f;
     const int32_t a = o - 1 < C ? D.perm[(int64_t)slot * C + o - 1] : 0;
     const int32_t n_dep = c->n_dep;
     const uint32_t ver = c->best_ver;
@@ -602,44 +626,44 @@ __device__ __forceinline__ void wa_apply_body(const WaAcsDev &D, int32_t slot, i
     if (o > n_dep) return;
     // a rank whose ant replayed the best path, but not the lowest such rank: every edge of its path carries that lower rank's bit too, so it owns none
     if (o <= 64 && ((rep >> (o - 1)) & 1ULL) && (o - 1) != __ffsll((long long)rep) - 1) return;
-    if (tid < 64) s_dep[tid] = base + tid < n_dep ? dep_mine : 0.f;
     // level 2: the ranked ant's length and this thread's first path words
     const int32_t *path = D.paths + ((int64_t)slot * C + a) * D.path_cap;
     const int32_t i0 = 1 + bx * (int32_t)blockDim.x + tid;
     const int32_t len = D.antLen[(int64_t)slot * C + a];
     int32_t w = i0 < D.path_cap ? path[i0] : 0, pv = i0 < D.path_cap ? path[i0 - 1] : 0;
-    __syncthreads();
+    // second term of :211, `(float)onbest * lambda * Q / bestL`, the same for every rank: it takes one of two values in a launch, both
+    // evaluated here once, each exactly as that expression groups -- ((onbest * lambda) * Q) / bestL --, and an edge picks its own
+    const float bonus_on = wa_uniform(1.f * lambda * Q / bestL), bonus_off = wa_uniform(0.f * lambda * Q / bestL);
+    const int32_t n = n_dep - base < 64 ? n_dep - base : 64;
     const WaMaskRef mask = wa_mask_of(D, slot);
     float *pher = D.pher + (int64_t)slot * D.pher_stride;
     const uint32_t *mark = D.bestmark + (int64_t)slot * D.d.n;
-    for (int32_t i = i0; i < len; i += nbx * (int32_t)blockDim.x) {
-        if (i != i0) { w = path[i]; pv = path[i - 1]; }
+    // (the trips are the wavefront's: a lane past its path's end goes along on edge 0 of voxel 0 and owns nothing, so that wa_add_ranked finds every lane there)
+    for (int32_t i = i0; __any(i < len); i += nbx * (int32_t)blockDim.x) {
+        const bool live = i < len;
+        if (!live) { w = 0; pv = 0; }
+        else if (i != i0) { w = path[i]; pv = path[i - 1]; }
         const int32_t v = pv & WaNbT<NB>::IDM;
         const int64_t e = (int64_t)v * NB + ((uint32_t)w >> WaNbT<NB>::SHIFT);
         // level 3: four independent loads
         const uint32_t mv = mark[v], mw = mark[w & WaNbT<NB>::IDM];
-        unsigned long long m = wa_mask_get(mask, e);
+        const unsigned long long m = wa_mask_get(mask, e);
         float p = pher[e];
         const bool v_best = mv == ver;
-        if (skip_best_src && v_best) continue;
-        if (m == 0 || (__ffsll((long long)m) - 1) != bit) continue;  // not the owner
+        const bool own = live && !(skip_best_src && v_best) && m != 0 && (__ffsll((long long)m) - 1) == bit;  // the lowest rank present owns the edge
         const bool onbest = v_best && mw == ver;                      // :209
-        const float bonus = (float)onbest * lambda * Q / bestL;       // second term of :211, the same for every rank
-        while (m) {
-            int b = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            p += s_dep[b] + bonus;  // :210-211
+        p = wa_add_ranked(p, own ? m : 0ULL, dep_lane, onbest ? bonus_on : bonus_off, n);  // :210-211
+        if (own) {
+            pher[e] = p;
+            wa_mask_clear(mask, e);
         }
-        pher[e] = p;
-        wa_mask_clear(mask, e);
     }
 }
 
 template <int NB>
 __global__ __launch_bounds__(256) void k_deposit_apply(WaAcsDev D, int32_t base)
 {
-    __shared__ float s_dep_[64];
-    wa_apply_body<NB>(D, blockIdx.z, base, blockIdx.y, blockIdx.x, gridDim.x, false, s_dep_);
+    wa_apply_body<NB>(D, blockIdx.z, base, blockIdx.y, blockIdx.x, gridDim.x, false);
 }
 
 // ------------------------------------------------------------------ lazy evaporation: reset / read-back helpers

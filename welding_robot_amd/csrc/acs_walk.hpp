@@ -922,12 +922,17 @@ __device__ __forceinline__ void wa_walk_one(const WaAcsDev &D, const WaRun &R, i
 // Output per node: thr[k] = admissible ? prob_sum_k : -inf (k = 0..5), total, edge taken to best[i+1].
 template <int NB>
 __device__ __forceinline__ void wa_apply_body(const WaAcsDev &D, int32_t slot, int32_t base, int32_t bit, int32_t bx, int32_t nbx,
-                                              bool skip_best_src, float *s_dep);
+                                              bool skip_best_src);
+__device__ __forceinline__ float wa_add_ranked(float p, unsigned long long m, float dep_lane, float bonus, int32_t n);   // (acs_update.hpp)
+// a value every lane holds alike, kept as the scalar it is: computed where this stands and not again per edge (the compiler otherwise moves
+// a division whose operands are launch constants down to its use inside the row loop)
+__device__ __forceinline__ float wa_uniform(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
 
 // apply_here: the row also APPLIES the pending ranked deposits (mask != 0) of its six edges -- same adds, same
 // ascending rank order as wa_apply_body -- writes them back, clears the masks, and evaluates on the new values.
+// dep_lane, n_dep: the deposit coefficients, rank bit l in lane l of every wavefront, and how many ranks deposit (wa_add_ranked).
 __device__ __forceinline__ void wa_table_rows(const WaAcsDev &D, const WaRun &R, int32_t slot, int32_t row0, int32_t rows, bool apply_here,
-                                              const float *s_dep, int32_t w_first, int32_t w_first_next)
+                                              float dep_lane, int32_t n_dep, int32_t w_first, int32_t w_first_next)
 {
     // w_first / w_first_next = bestpath[row0], bestpath[row0 + 1], loaded by the caller before the best length was
     // known (speculatively, inside the allocation) so that the row's record loads start one round trip earlier
@@ -958,8 +963,12 @@ __device__ __forceinline__ void wa_table_rows(const WaAcsDev &D, const WaRun &R,
     const uint32_t *stamp = D.stamp ? D.stamp + (int64_t)slot * D.d.n : nullptr;
     const float clean_now = ctl->clean[ctl->gen & 1];
     const uint32_t evap_tab = ctl->evap_base + (uint32_t)ctl->gen;   // the fused launch already counted this generation
-    for (int32_t i = row0; i < blen; i += rows) {
-        const int32_t wv = i == row0 ? w_first : bpath[i];
+    // second term of :211, `(float)onbest * lambda * Q / bestL`: one of two values, each evaluated once and exactly as that expression groups
+    const float bonus_on = wa_uniform(1.f * lambda * Q / bestL), bonus_off = wa_uniform(0.f * lambda * Q / bestL);
+    // (the trips are the wavefront's: a row past the path's end goes along on voxel 0 and writes nothing, so that wa_add_ranked finds every lane there)
+    for (int32_t i = row0; __any(i < blen); i += rows) {
+        const bool live = i < blen;
+        const int32_t wv = !live ? 0 : i == row0 ? w_first : bpath[i];
         const int32_t wn = i + 1 < blen ? (i == row0 ? w_first_next : bpath[i + 1]) : 0;
         const int32_t v = wv & (int32_t)WA_ID_MASK;
         // all record loads of the row are independent of each other
@@ -970,7 +979,7 @@ __device__ __forceinline__ void wa_table_rows(const WaAcsDev &D, const WaRun &R,
             const uint32_t stv = stamp[v];
             p = stv == 0 ? copysignf(clean_now, p) : copysignf(wa_catch_up(fabsf(p), evap_tab + 1u - stv, R.rho), p);
         }
-        unsigned long long m = apply_here ? wa_mask_get(mask, e) : 0ULL;
+        const unsigned long long m = apply_here && live && k2 < 6 ? wa_mask_get(mask, e) : 0ULL;
         int32_t nbid = v + dk;
         nbid = nbid < 0 ? 0 : nbid > last_id ? last_id : nbid;       // (an out-of-bounds edge is inadmissible by its sign bit whatever is found here)
         const uint32_t mk = (apply_here || rebuild) ? mark[nbid] : 0u;
@@ -979,23 +988,20 @@ __device__ __forceinline__ void wa_table_rows(const WaAcsDev &D, const WaRun &R,
             // (only for a neighbour id inside the field: wa_replay_from looks such a neighbour up by its id)
             const bool on = k2 < 6 && nbid == v + dk && mk == ver && pos[nbid] <= i;
             bt = (uint32_t)(__ballot(on) >> (threadIdx.x & 48)) & 0x3fu;   // the six lanes of this 16-lane row
-            if (k2 == 0) btabu[i] = (uint8_t)bt;
+            if (k2 == 0 && live) btabu[i] = (uint8_t)bt;
         } else {
-            bt = btabu[i];
+            bt = live ? btabu[i] : 0u;
         }
-        bool adm = false;
-        if (k2 < 6) {
-            if (m) {  // somebody walked (v, k2): apply the ranked deposits in ascending rank order (:210-211)
-                const bool onbest = mk == ver;  // v itself is on the best path (:209)
-                const float bonus = (float)onbest * lambda * Q / bestL;
-                while (m) {
-                    int b = __ffsll((long long)m) - 1;
-                    m &= m - 1;
-                    p += s_dep[b] + bonus;
-                }
+        if (apply_here) {
+            // somebody walked (v, k2): apply the ranked deposits in ascending rank order (:210-211); v itself is on the best path, so mk == ver is :209
+            p = wa_add_ranked(p, m, dep_lane, mk == ver ? bonus_on : bonus_off, n_dep);
+            if (m) {
                 pher[e] = p;
                 wa_mask_clear(mask, e);
             }
+        }
+        bool adm = false;
+        if (k2 < 6) {
             // in bounds and free (:148), and not on the prefix best[0..i] (:145-146)
             adm = (__float_as_uint(p) >> 31) == 0 && !((bt >> k2) & 1u);
         } else {
@@ -1005,6 +1011,7 @@ __device__ __forceinline__ void wa_table_rows(const WaAcsDev &D, const WaRun &R,
         const float a = adm ? info : 0.f;
         float t, c;
         wa_ordered_sums(a, t, c);
+        if (!live) continue;
         if (k2 < 6) T[(int64_t)i * 8 + k2] = adm ? c : -INFINITY;
         if (k2 == 5) T[(int64_t)i * 8 + 6] = t;
         if (k2 == 0) T[(int64_t)i * 8 + 7] = __int_as_float(i + 1 < blen ? (int32_t)((uint32_t)wn >> WA_K_SHIFT) : -1);
@@ -1016,7 +1023,7 @@ __global__ __launch_bounds__(256) void k_replay_table(WaAcsDev D, WaRun R)
     const int32_t row0 = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const int32_t *bpath = D.bestpath + (int64_t)blockIdx.y * D.path_cap;
     const int32_t w0 = row0 < D.path_cap ? bpath[row0] : 0, w1 = row0 + 1 < D.path_cap ? bpath[row0 + 1] : 0;
-    wa_table_rows(D, R, blockIdx.y, row0, (gridDim.x * blockDim.x) >> 4, false, nullptr, w0, w1);
+    wa_table_rows(D, R, blockIdx.y, row0, (gridDim.x * blockDim.x) >> 4, false, 0.f, 0, w0, w1);
 }
 
 // Deposit apply + replay table in ONE launch (DEV fast path, <= 64 depositing ranks): blocks [0, TB) are
@@ -1031,7 +1038,6 @@ __global__ __launch_bounds__(256) void k_replay_table(WaAcsDev D, WaRun R)
 // faster --, 1 for launches that carry 32 searches or more)
 __global__ __launch_bounds__(256) void k_apply_table(WaAcsDev D, WaRun R, int32_t split_log2, int32_t table_blocks)
 {
-    __shared__ float s_dep[64];
     const int32_t slot = blockIdx.y;
     // lazy evaporation: voxels that became dirty in this generation join the swept set from the next sweep on
     if (D.dcount && blockIdx.x == 0 && threadIdx.x == 0) D.dcount[slot * 2] = D.dcount[slot * 2 + 1];
@@ -1041,19 +1047,17 @@ __global__ __launch_bounds__(256) void k_apply_table(WaAcsDev D, WaRun R, int32_
         if (threadIdx.x == 0) { *sg.arr_n = 0; sg.pool_n[D.ctl[slot].gen & 1] = 0; }   // (ctl.gen is already the next generation's number)
     }
     if ((int32_t)blockIdx.x < table_blocks) {
-        // independent loads first: deposit coefficients, control block, this row's path words
-        const int32_t tid = threadIdx.x, row0 = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
-        const float dep_mine = (tid < 64 && tid < D.max_colony) ? D.depA[(int64_t)slot * D.max_colony + tid] : 0.f;
+        // independent loads first: deposit coefficients (rank bit l in lane l of every wavefront), control block, this row's path words
+        const int32_t lane = threadIdx.x & 63, row0 = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+        const float dep_lane = lane < D.max_colony ? D.depA[(int64_t)slot * D.max_colony + lane] : 0.f;
         const int32_t *bpath = D.bestpath + (int64_t)slot * D.path_cap;
         const int32_t w0 = row0 < D.path_cap ? bpath[row0] : 0, w1 = row0 + 1 < D.path_cap ? bpath[row0 + 1] : 0;
         const int32_t n_dep = D.ctl[slot].n_dep;
-        if (tid < 64) s_dep[tid] = tid < n_dep ? dep_mine : 0.f;
-        __syncthreads();
-        wa_table_rows(D, R, slot, row0, (table_blocks * blockDim.x) >> 4, true, s_dep, w0, w1);
+        wa_table_rows(D, R, slot, row0, (table_blocks * blockDim.x) >> 4, true, dep_lane, n_dep < 64 ? n_dep : 64, w0, w1);
         return;
     }
     const int32_t ab = (int32_t)blockIdx.x - table_blocks;  // 0..(ranks << split_log2)-1: (bx, rank bit)
-    wa_apply_body<6>(D, slot, 0, ab >> split_log2, ab & ((1 << split_log2) - 1), 1 << split_log2, true, s_dep);
+    wa_apply_body<6>(D, slot, 0, ab >> split_log2, ab & ((1 << split_log2) - 1), 1 << split_log2, true);
 }
 
 // DEV: grid = (max_colony, n_problems), block = one wavefront
