@@ -285,6 +285,11 @@ int wa_acs_debug_counters(wa_acs *s, uint64_t out16[16], int32_t reset);
 int wa_acs_straggler_counters(wa_acs *s, int32_t slot, uint64_t *handed_over, uint64_t *resumed, int32_t reset);
 /* generations of a search during which its ants may be handed over (default 64, WA_STRAGGLER_GENS; 0: off; < 0: back to the default) */
 int wa_acs_set_stragglers(wa_acs *s, int32_t generations);
+/* Converged generations in one launch (dense 6-neighbour solvers on the fused DEV loop; WA_CONVERGED_RUN=0, read at wa_acs_create, switches it off;
+ * WA_CONVERGED_WINDOW: generations a window covers at most).  out: [0] windows enqueued for `slot` since the solver was created, [1] windows
+ * committed whole, [2] windows cut short by an ant that left the best path, [3] generations committed.  Results are bit-identical with the
+ * mechanism on or off.  Waits for the work enqueued so far. */
+int wa_acs_converged_info(wa_acs *s, int32_t slot, uint64_t out[4]);
 /* evaporation sweep alone (ACSRank_3D.hpp:268-272) over `slot` -- for roofline measurements */
 int wa_acs_evaporate(wa_acs *s, int32_t slot, float rho, int32_t repeats);
 

@@ -366,6 +366,13 @@ class AcsSolver:
         self.ctx.check(self.ctx.lib.wa_acs_straggler_counters(self.h, slot, C.byref(a), C.byref(b), 1 if reset else 0))
         return a.value, b.value
 
+    def converged_info(self, slot=0):
+        """converged generations in one launch, for one slot since the solver was created: windows enqueued, committed whole, cut short by an
+        ant that left the best path, and generations committed"""
+        out = (C.c_uint64 * 4)()
+        self.ctx.check(self.ctx.lib.wa_acs_converged_info(self.h, slot, out))
+        return dict(enqueued=int(out[0]), whole=int(out[1]), cut=int(out[2]), generations=int(out[3]))
+
     def set_stragglers(self, generations):
         """generations of a search during which ants may be handed over (0: off, < 0: default)"""
         self.ctx.check(self.ctx.lib.wa_acs_set_stragglers(self.h, generations))

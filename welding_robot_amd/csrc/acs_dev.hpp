@@ -63,6 +63,11 @@ struct WaAcsDev {
     uint32_t tab16_kmul;           // 16-bit tabu entries (WaTabu): K_B << (32 - B) for this grid's B-bit voxel ids, 0 where an entry cannot name them (6 neighbours only)
     int32_t guard_bytes;           // guard band in front of / behind the pheromone and heuristic allocations (6-neighbour solvers)
     int32_t stamp_guard_bytes;     // ... and the stamp allocation of a lazily evaporating solver
+    // converged generations in one launch (acs_converged.hpp): per-slot scratch block = header + the snapshots of the path state, one per generation of a window.
+    // Null where the mechanism is off (WA_CONVERGED_RUN=0, lazy fields, 26 neighbours, REF mode, colonies past the fused path)
+    char *conv;                    // [slot][conv_stride] bytes
+    int64_t conv_stride;
+    int32_t conv_nodes;            // longest best path a window covers (the window kernel keeps 96 bytes of LDS per node)
     int32_t vbits_rows;            // bitmap rows per slot: max_colony (+ WA_RESUME_MAX rows of the resume blocks when the solver has straggler pools)
 };
 
@@ -256,6 +261,7 @@ __global__ void k_begin(WaAcsDev D, WaRun R, int32_t n_problems, const long long
     c.evap_base += (uint32_t)c.gen;    // ... and so does the count of evaporations applied so far
     c.gen = 0;
     c.tabu_gen = -2;
+    c.spec_until = 0;
     c.bestL = INFINITY;  // :232; the best PATH is kept (Q9) but unreachable while bestL is inf
     c.best_len = 0;
     c.n_dep = 0;

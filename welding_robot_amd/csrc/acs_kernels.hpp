@@ -18,3 +18,4 @@
 #include "acs_walk.hpp"     // tabu, the walk loops, replay, k_walk_dev / k_walk_ref, k_replay_table / k_apply_table
 #include "acs_update.hpp"   // k_rank, the sweep, k_evap_rank_mark, k_deposit_*, lazy helpers
 #include "acs_nb26.hpp"     // 26-neighbour walk, table and apply kernels
+#include "acs_converged.hpp"  // k_converged_run: the generations of a converged colony in one launch, the flush helpers of the regular launches

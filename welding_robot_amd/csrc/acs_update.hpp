@@ -260,6 +260,7 @@ __global__ __launch_bounds__(256) void k_rank(WaAcsDev D, WaRun R, int32_t gen)
 // :268-272 -- dst = src * rho over n_floats values; float4 per lane, 4 independent float4 in flight per
 // thread, grid-stride over E blocks.  One definition for k_evaporate and the fused k_evap_rank_mark.
 typedef float wa_v4f __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ int32_t wa_conv_pending(const WaAcsDev &D, int32_t slot);   // (acs_converged.hpp)
 // NT bit 0 / bit 1: non-temporal loads / stores (the `nt` bit of global_load / global_store: the lines stream through the caches instead of
 // displacing what is there).  Wrong for a lone search at 128^3 -- the next walk finds the swept field in the Infinity Cache -- and
 // right when several searches share the GPU (their fields are past every cache anyway and the walking groups' records stay in L2)
@@ -271,8 +272,9 @@ __device__ __forceinline__ void wa_sweep_st(wa_v4f *p, wa_v4f v)
     if (NT & 2) __builtin_nontemporal_store(v, p);
     else *p = v;
 }
+// reps: multiplications per value, one rounding each (1: the sweep of a generation; j: the flush behind j committed generations, uniform over the launch)
 template <int NT>
-__device__ __forceinline__ void wa_sweep_body_nt(const float *src, float *dst, int64_t n_floats, float rho, int32_t ebx, int32_t E)
+__device__ __forceinline__ void wa_sweep_body_nt(const float *src, float *dst, int64_t n_floats, float rho, int32_t ebx, int32_t E, int32_t reps)
 {
     const wa_v4f *s4 = reinterpret_cast<const wa_v4f *>(src);
     wa_v4f *d4 = reinterpret_cast<wa_v4f *>(dst);
@@ -281,25 +283,29 @@ __device__ __forceinline__ void wa_sweep_body_nt(const float *src, float *dst, i
     int64_t i = (int64_t)ebx * blockDim.x + threadIdx.x;
     for (; i + 3 * gsz < n4; i += 4 * gsz) {
         wa_v4f a = wa_sweep_ld<NT>(s4 + i), b = wa_sweep_ld<NT>(s4 + i + gsz), c = wa_sweep_ld<NT>(s4 + i + 2 * gsz), d = wa_sweep_ld<NT>(s4 + i + 3 * gsz);
-        a *= rho; b *= rho; c *= rho; d *= rho;
+        for (int32_t r = 0; r < reps; r++) { a *= rho; b *= rho; c *= rho; d *= rho; }
         wa_sweep_st<NT>(d4 + i, a); wa_sweep_st<NT>(d4 + i + gsz, b); wa_sweep_st<NT>(d4 + i + 2 * gsz, c); wa_sweep_st<NT>(d4 + i + 3 * gsz, d);
     }
     for (; i < n4; i += gsz) {
         wa_v4f a = wa_sweep_ld<NT>(s4 + i);
-        a *= rho;
+        for (int32_t r = 0; r < reps; r++) a *= rho;
         wa_sweep_st<NT>(d4 + i, a);
     }
     // tail (n_floats is even; at most 2 floats)
     const int64_t t = (n4 << 2) + (int64_t)ebx * blockDim.x + threadIdx.x;
-    if (t < n_floats) dst[t] = src[t] * rho;
+    if (t < n_floats) {
+        float v = src[t];
+        for (int32_t r = 0; r < reps; r++) v *= rho;
+        dst[t] = v;
+    }
 }
-__device__ __forceinline__ void wa_sweep_body(const float *src, float *dst, int64_t n_floats, float rho, int32_t ebx, int32_t E, int32_t nt = 0)
+__device__ __forceinline__ void wa_sweep_body(const float *src, float *dst, int64_t n_floats, float rho, int32_t ebx, int32_t E, int32_t nt = 0, int32_t reps = 1)
 {
     switch (nt & 3) {   // (uniform over the launch)
-    case 0: wa_sweep_body_nt<0>(src, dst, n_floats, rho, ebx, E); break;
-    case 1: wa_sweep_body_nt<1>(src, dst, n_floats, rho, ebx, E); break;
-    case 2: wa_sweep_body_nt<2>(src, dst, n_floats, rho, ebx, E); break;
-    default: wa_sweep_body_nt<3>(src, dst, n_floats, rho, ebx, E); break;
+    case 0: wa_sweep_body_nt<0>(src, dst, n_floats, rho, ebx, E, reps); break;
+    case 1: wa_sweep_body_nt<1>(src, dst, n_floats, rho, ebx, E, reps); break;
+    case 2: wa_sweep_body_nt<2>(src, dst, n_floats, rho, ebx, E, reps); break;
+    default: wa_sweep_body_nt<3>(src, dst, n_floats, rho, ebx, E, reps); break;
     }
 }
 
@@ -325,6 +331,18 @@ __global__ __launch_bounds__(256) void k_evap_rank_mark(WaAcsDev D, WaRun R, con
     // colony kept four blocks per CU resident, a 4-KB one keeps eight (32 lazy 256-ant searches: 253 -> 283 k problem-generations/s, round 6)
     extern __shared__ unsigned long long wa_rank_lds[];
     const int32_t slot = blockIdx.y, tid = threadIdx.x;
+    // A generation below ctl.spec_until was committed by k_converged_run (acs_converged.hpp): nothing to rank, mark or sweep.  The launch of the LAST
+    // committed generation is the flush: its sweep blocks apply the j evaporations the committed generations owe the field, one rounding each.  The field
+    // sits where the window found it -- the host flipped src / dst j - 1 times since: this launch's src for odd j (out of place), its dst for even j
+    // (in place) -- and ends up in dst, the buffer the host takes for current, either way
+    if (gen < D.ctl[slot].spec_until) {
+        if (!SPARSE && NB == 6 && gen + 1 == D.ctl[slot].spec_until && (int32_t)blockIdx.x >= MB) {
+            const int32_t j = wa_conv_pending(D, slot);
+            float *to = dst_base + (int64_t)slot * D.pher_stride;
+            wa_sweep_body((j & 1) ? src_base + (int64_t)slot * D.pher_stride : to, to, (int64_t)NB * D.d.n, R.rho, (int32_t)blockIdx.x - MB, E, sweep_nt, j);
+        }
+        return;
+    }
     // the MB rank/mark blocks come FIRST in the grid so that they are dispatched immediately and
     // their latency-bound work hides under the sweep blocks that follow
     if ((int32_t)blockIdx.x >= MB) {  // ---- sweep: dst = src * rho (same body as k_evaporate)

@@ -489,6 +489,16 @@ __device__ __forceinline__ void wa_walk_slow(const WaAcsDev &D, const WaRun &R, 
 // Returns 1 dead end at node i, 2 arrived, 3 deviates at node i (i in `node`).
 // draws != nullptr (REF mode, k_walk_ref_spec): the draw of step i is draws[i] -- the libc stream's output the ant would be dealt if every
 // ant in front of it followed the whole best path -- instead of the counter hash
+// One node's test: the row (a = thr[0..3]; b = thr[4], thr[5], total, edge taken) against the 31-bit draw.  Bit k of the result: thr[k] >= rnd;
+// the roulette, scanning i = 5..0, takes the highest set bit (none: dead end).  One definition for the walk's replay and the converged run.
+__device__ __forceinline__ uint32_t wa_replay_hits(const float4 &ca, const float4 &cb, int32_t draw)
+{
+    float rnd = (float)draw / 2147483648.0f;  // (float)rand()/(float)RAND_MAX (:169)
+    rnd *= cb.z;                              // :170, total
+    // thr = admissible ? prob_sum : -inf   (:178)
+    return (ca.x >= rnd ? 1u : 0u) | (ca.y >= rnd ? 2u : 0u) | (ca.z >= rnd ? 4u : 0u) | (ca.w >= rnd ? 8u : 0u) |
+           (cb.x >= rnd ? 16u : 0u) | (cb.y >= rnd ? 32u : 0u);
+}
 __device__ __forceinline__ int wa_walk_replay(const float *__restrict__ T, int32_t rlen, uint64_t antkey, int32_t &node, const int32_t *__restrict__ draws = nullptr)
 {
     // Replay steps do not depend on each other while the ant stays on the path, so 64 consecutive nodes
@@ -512,12 +522,9 @@ __device__ __forceinline__ int wa_walk_replay(const float *__restrict__ T, int32
             a = T4[2 * nv];
             b = T4[2 * nv + 1];
         }
-        float rnd = (float)(draws ? (valid ? __hip_atomic_load(&draws[nodev], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0) : (int32_t)wa_ctr_draw(antkey, (uint32_t)nodev)) / 2147483648.0f;  // (float)rand()/(float)RAND_MAX (:169)
-        rnd *= cb.z;                                                               // :170, total
+        const int32_t draw = draws ? (valid ? __hip_atomic_load(&draws[nodev], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0) : (int32_t)wa_ctr_draw(antkey, (uint32_t)nodev);
         const int nk = __float_as_int(cb.w);
-        // thr = admissible ? prob_sum : -inf   (:178)
-        const uint32_t h = (ca.x >= rnd ? 1u : 0u) | (ca.y >= rnd ? 2u : 0u) | (ca.z >= rnd ? 4u : 0u) | (ca.w >= rnd ? 8u : 0u) |
-                           (cb.x >= rnd ? 16u : 0u) | (cb.y >= rnd ? 32u : 0u);
+        const uint32_t h = wa_replay_hits(ca, cb, draw);
         const int pick = h ? 31 - __clz((int)h) : -1;
         const unsigned long long fm = __ballot(valid && pick != nk);
         if (__builtin_expect(fm != 0, 0)) {
@@ -928,6 +935,24 @@ __device__ __forceinline__ float wa_add_ranked(float p, unsigned long long m, fl
 // a division whose operands are launch constants down to its use inside the row loop)
 __device__ __forceinline__ float wa_uniform(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
 
+// The row arithmetic of one edge (role k2 of a 16-lane row; roles 6..15 pad the sums with zeros): admissible = in bounds and free (:148) and not
+// on the prefix best[0..i] (:145-146, bit k2 of bt); info (:154); the two ordered sums.  thr = what the table keeps for the edge (roles 0..5),
+// t = total in role 5.  One definition for the table rows and the converged run, so the bits agree.
+__device__ __forceinline__ void wa_row_values(const WaRun &R, float p, float h, int32_t k2, uint32_t bt, float &thr, float &t)
+{
+    bool adm = false;
+    if (k2 < 6) {
+        adm = (__float_as_uint(p) >> 31) == 0 && !((bt >> k2) & 1u);
+    } else {
+        p = -0.f;
+    }
+    const float info = (R.alpha == 1 ? fabsf(p) : wa_powi(fabsf(p), R.alpha)) * (k2 < 6 ? h : 0.f);  // :154
+    const float a = adm ? info : 0.f;
+    float c;
+    wa_ordered_sums(a, t, c);
+    thr = adm ? c : -INFINITY;
+}
+
 // apply_here: the row also APPLIES the pending ranked deposits (mask != 0) of its six edges -- same adds, same
 // ascending rank order as wa_apply_body -- writes them back, clears the masks, and evaluates on the new values.
 // dep_lane, n_dep: the deposit coefficients, rank bit l in lane l of every wavefront, and how many ranks deposit (wa_add_ranked).
@@ -1000,19 +1025,10 @@ __device__ __forceinline__ void wa_table_rows(const WaAcsDev &D, const WaRun &R,
                 wa_mask_clear(mask, e);
             }
         }
-        bool adm = false;
-        if (k2 < 6) {
-            // in bounds and free (:148), and not on the prefix best[0..i] (:145-146)
-            adm = (__float_as_uint(p) >> 31) == 0 && !((bt >> k2) & 1u);
-        } else {
-            p = -0.f;
-        }
-        const float info = (R.alpha == 1 ? fabsf(p) : wa_powi(fabsf(p), R.alpha)) * (k2 < 6 ? h : 0.f);  // :154
-        const float a = adm ? info : 0.f;
-        float t, c;
-        wa_ordered_sums(a, t, c);
+        float thr, t;
+        wa_row_values(R, p, h, k2, bt, thr, t);
         if (!live) continue;
-        if (k2 < 6) T[(int64_t)i * 8 + k2] = adm ? c : -INFINITY;
+        if (k2 < 6) T[(int64_t)i * 8 + k2] = thr;
         if (k2 == 5) T[(int64_t)i * 8 + 6] = t;
         if (k2 == 0) T[(int64_t)i * 8 + 7] = __int_as_float(i + 1 < blen ? (int32_t)((uint32_t)wn >> WA_K_SHIFT) : -1);
     }
@@ -1036,15 +1052,24 @@ __global__ __launch_bounds__(256) void k_replay_table(WaAcsDev D, WaRun R)
 #define WA_TABLE_BLOCKS_MAX 64
 // split_log2: apply blocks per depositing rank = 1 << this (the host passes 2 for one or a few searches -- 8 blocks per rank are no
 // faster --, 1 for launches that carry 32 searches or more)
-__global__ __launch_bounds__(256) void k_apply_table(WaAcsDev D, WaRun R, int32_t split_log2, int32_t table_blocks)
+__device__ __forceinline__ void wa_conv_flush_rows(const WaAcsDev &D, int32_t slot, int32_t first, int32_t step);   // (acs_converged.hpp)
+// gen: the generation this launch belongs to.  Below ctl.spec_until the generation was committed by k_converged_run and the launch returns at once --
+// except the launch of the LAST committed generation, whose table blocks put the path nodes' records and rows of the commit in place
+__global__ __launch_bounds__(256) void k_apply_table(WaAcsDev D, WaRun R, int32_t split_log2, int32_t table_blocks, int32_t gen)
 {
     const int32_t slot = blockIdx.y;
+    const int32_t spec_until = D.ctl[slot].spec_until;
+    if (gen + 1 < spec_until) return;
     // lazy evaporation: voxels that became dirty in this generation join the swept set from the next sweep on
     if (D.dcount && blockIdx.x == 0 && threadIdx.x == 0) D.dcount[slot * 2] = D.dcount[slot * 2 + 1];
     if (D.pool_n && blockIdx.x == 0) {   // stragglers: the next generation starts with no arrivals and an empty pool of its own
         const WaStrag sg = wa_strag_of(D, slot);
         sg.arr_len[threadIdx.x] = 0xffffffffu;
         if (threadIdx.x == 0) { *sg.arr_n = 0; sg.pool_n[D.ctl[slot].gen & 1] = 0; }   // (ctl.gen is already the next generation's number)
+    }
+    if (gen < spec_until) {   // the flush (the sweep blocks of the launch in front evaporated the whole field, these nodes' stale records included)
+        if ((int32_t)blockIdx.x < table_blocks) wa_conv_flush_rows(D, slot, blockIdx.x * blockDim.x + threadIdx.x, table_blocks * blockDim.x);
+        return;
     }
     if ((int32_t)blockIdx.x < table_blocks) {
         // independent loads first: deposit coefficients (rank bit l in lane l of every wavefront), control block, this row's path words
@@ -1073,6 +1098,7 @@ __global__ __launch_bounds__(64) void k_walk_dev(WaAcsDev D, WaRun R, int hash_l
     extern __shared__ int32_t lds[];
     const int32_t slot = blockIdx.y, ant = blockIdx.x;
     const WaSlotCtl *c = &D.ctl[slot];
+    if (gen < c->spec_until) return;   // a committed generation (acs_converged.hpp): ants and resume blocks alike have nothing to do
     const int32_t colony = c->colony[gen & 1];
 #ifdef WA_STRAG_TIME
     if (threadIdx.x == 0 && gen < 128) atomicMax(&wa_strag_t[gen * 8 + 0], ~(unsigned long long)wall_clock64());

@@ -175,6 +175,12 @@ static int acs_create_once(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, in
     s->drain_ok = env_int("WA_STRAGGLER_DRAIN", 1) != 0;
     s->sweep_nt_env = env_int("WA_SWEEP_NT", -1);
     s->straggler_gens = env_int("WA_STRAGGLER_GENS", 64);
+    s->conv_on = env_int("WA_CONVERGED_RUN", 1) != 0;
+    s->conv_window = env_int("WA_CONVERGED_WINDOW", 32);
+    if (s->conv_window > WA_CONV_MAX_WINDOW) s->conv_window = WA_CONV_MAX_WINDOW;
+    if (s->conv_window < 1) s->conv_on = false;
+    s->conv_nodes_env = env_int("WA_CONVERGED_NODES", 0);
+    s->conv_enqueued.assign((size_t)n_slots, 0);
     {   // sweep grid: measured on MI355X -- 100 MB fields (128^3 x 6) peak at 4096 blocks (6.0 TB/s; 2048: 5.5, 8192: 5.8),
         // 436 MB fields (128^3 x 26) want 2-3 float4 per thread (49152 blocks: 6.1 TB/s; 32768: 5.9; 4096: 4.6)
         const int64_t n4 = (int64_t)nb * n / 4;
@@ -356,6 +362,7 @@ void wa_acs_destroy(wa_acs *s)
     if (!s) return;
     hipStreamSynchronize(s->ctx->stream);
     if (s->d_stage) hipFree(s->d_stage);
+    if (s->d_conv) ctx_free(s->ctx, s->d_conv);
 #ifdef WA_STATE_HASH
     if (s->d_hashlog) hipFree(s->d_hashlog);
 #endif
@@ -569,6 +576,7 @@ int wa_acs_begin(wa_acs *s, const wa_acs_params *p, int32_t n_problems, const in
     s->n_active = n_problems;
     s->begun = true;
     s->gens_enqueued = 0;
+    s->conv_until = 0;
     s->ran_before = false;
     return WA_OK;
 }
@@ -663,6 +671,7 @@ static WaAcsDev dev_view(const wa_acs *s, int32_t slot0)
     V.ctl += q;
     if (V.trBest) { V.trBest += q * V.trace_cap; V.trIter += q * V.trace_cap; V.trColony += q * V.trace_cap; V.trFinite += q * V.trace_cap; V.trSteps += q * V.trace_cap; }
     if (V.stamp) { V.stamp += q * n; V.dirty_list += q * n; V.dcount += q * 2; }
+    if (V.conv) V.conv += q * V.conv_stride;
     if (V.pool_n) {
         V.arr_len += q * 256; V.arr_n += q; V.pool_n += q * 2;
         V.pool_rec += q * 2 * WA_RESUME_MAX * WA_POOL_REC; V.strag_cnt += q * 2;
@@ -883,7 +892,7 @@ static void enqueue_generation(wa_acs *s, WaGroupRun &G, int32_t gen, bool last_
         WA_HASH_AT(1);
         e = prof_open(s, st, WA_K_DEPOSIT, sampled);
         if (s->nb == 26) k_apply_table26<<<dim3((unsigned)(1 + WA_TABLE26_BLOCKS + mark_blocks(s)), (unsigned)P), 256, 0, st>>>(G.V, s->R);
-        else { const int32_t SL = P >= 32 ? 1 : 2, TB = P >= 32 ? 32 : WA_TABLE_BLOCKS_MAX; k_apply_table<<<dim3((unsigned)(TB + ((mark_blocks(s) >> 3) << SL)), (unsigned)P), 256, 0, st>>>(G.V, s->R, SL, TB); }
+        else { const int32_t SL = P >= 32 ? 1 : 2, TB = P >= 32 ? 32 : WA_TABLE_BLOCKS_MAX; k_apply_table<<<dim3((unsigned)(TB + ((mark_blocks(s) >> 3) << SL)), (unsigned)P), 256, 0, st>>>(G.V, s->R, SL, TB, gen); }
         prof_close(st, e);
         WA_DBG_SYNC("apply+table");
         WA_HASH_AT(2);
@@ -912,6 +921,59 @@ static void enqueue_generation(wa_acs *s, WaGroupRun &G, int32_t gen, bool last_
         else k_replay_table<<<dim3(32, (unsigned)P), 256, 0, st>>>(G.V, s->R);
     }
     prof_close(st, e);
+}
+
+// ------------------------------------------------------------------ converged generations in one launch (acs_converged.hpp)
+// Does the solver run windows at all?  Dense 6-neighbour fields on the fused three-launch path in DEV mode; WA_CONVERGED_RUN=0 switches the mechanism off
+// (no kernel is enqueued, ctl.spec_until stays 0).  The diagnostic hash build compares the state behind every launch: no windows there.
+static bool conv_rule(const wa_acs *s, bool fused)
+{
+#ifdef WA_STATE_HASH
+    return false;
+#endif
+    return s->conv_on && fused && !s->lazy && s->nb == 6 && s->R.rng_mode == WA_RNG_DEV && s->D.rtab != nullptr && s->colony_bound > 0;
+}
+// The scratch blocks: per slot a header and one snapshot of the path state per generation of a window.  They are taken from the context's allocator outside
+// the solver's plan, by the first call that needs them.  A device without room for them runs without windows.
+static bool conv_scratch(wa_acs *s)
+{
+    if (s->d_conv && s->conv_snaps >= s->conv_window) return true;
+    wa_ctx *ctx = s->ctx;
+    if (s->d_conv) { hipStreamSynchronize(ctx->stream); ctx_free(ctx, s->d_conv); s->d_conv = nullptr; s->D.conv = nullptr; }
+    int64_t nodes = s->D.path_cap < WA_CONV_NODE_CAP ? s->D.path_cap : WA_CONV_NODE_CAP;
+    if (s->conv_nodes_env > 0 && s->conv_nodes_env < nodes) nodes = s->conv_nodes_env;
+    const int64_t stride = (int64_t)sizeof(WaConvHdr) + (int64_t)s->conv_window * nodes * WA_CONV_SNAP * (int64_t)sizeof(float);
+    void *blk = nullptr;
+    if (ctx_alloc_bytes(ctx, &blk, (size_t)(stride * s->n_slots)) != hipSuccess) { (void)hipGetLastError(); s->conv_on = false; return false; }
+    if (hipMemsetAsync(blk, 0, (size_t)(stride * s->n_slots), ctx->stream) != hipSuccess) { ctx_free(ctx, blk); s->conv_on = false; return false; }
+    s->d_conv = static_cast<char *>(blk);
+    s->conv_snaps = s->conv_window;
+    s->D.conv = s->d_conv;
+    s->D.conv_stride = stride;
+    s->D.conv_nodes = (int32_t)nodes;
+    return true;
+}
+// Generations the window in front of generation `gen` may cover.  Never the last generation of the call (gen_last: the ants' arrays, the result and the
+// drain launch read what the regular kernels wrote) and never a generation whose launches are stamped for wa_acs_profile (those figures stay the
+// figures of real, full launches; the flush is never a stamped launch): windows run between stamped generations.
+static int32_t conv_window_at(const wa_acs *s, int32_t gen, int32_t gen_last)
+{
+    int32_t W = s->conv_window;
+    if (gen_last - gen < W) W = gen_last - gen;
+    if (s->prof_sweep_all) return 0;
+    if (s->prof) {
+        if (gen % s->prof_every == 0) return 0;
+        const int32_t next = (gen / s->prof_every + 1) * s->prof_every;
+        if (next - gen < W) W = next - gen;
+    }
+    return W < 0 ? 0 : W;
+}
+static hipError_t launch_converged(wa_acs *s, WaGroupRun &G, int32_t gen, int32_t W)
+{
+    G.V.pher = s->pher_buf[G.cur] + (int64_t)G.slot0 * s->D.pher_stride;   // the field as generation `gen` finds it
+    k_converged_run<<<dim3(WA_CONV_BLOCKS, (unsigned)G.P), WA_CONV_THREADS, (size_t)s->D.conv_nodes * WA_CONV_NODE_LDS, G.st>>>(G.V, s->R, gen, W);
+    for (int32_t q = 0; q < G.P; q++) s->conv_enqueued[(size_t)(G.slot0 + q)]++;
+    return hipGetLastError();
 }
 
 // The last generation of the previous wa_acs_run handed stragglers over and no further generation has been enqueued: finish them now
@@ -1014,6 +1076,7 @@ int wa_acs_run(wa_acs *s, int32_t n_generations)
         WA_LDS_ATTR(true, false, false, true, true); WA_LDS_ATTR(true, false, false, false, true); WA_LDS_ATTR(true, true, false, true, true); WA_LDS_ATTR(true, true, false, false, true);
         WA_LDS_ATTR(true, false, false, true, false, true); WA_LDS_ATTR(true, false, false, false, false, true); WA_LDS_ATTR(true, true, false, true, false, true); WA_LDS_ATTR(true, true, false, false, false, true);
 #undef WA_LDS_ATTR
+        a = a ? a : hipFuncSetAttribute((const void *)k_converged_run, hipFuncAttributeMaxDynamicSharedMemorySize, WA_CONV_NODE_CAP * WA_CONV_NODE_LDS);
         a = a ? a : hipFuncSetAttribute((const void *)k_walk_ref, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
         a = a ? a : hipFuncSetAttribute((const void *)k_walk_dev26<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
         a = a ? a : hipFuncSetAttribute((const void *)k_walk_dev26<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
@@ -1044,6 +1107,8 @@ int wa_acs_run(wa_acs *s, int32_t n_generations)
         HIPC(ctx, hipMemsetAsync(s->d_hashlog, 0, bytes, ctx->stream));
     }
 #endif
+    const bool conv = n_generations > 1 && conv_rule(s, fused) && conv_scratch(s);
+    const int32_t gen_last = s->gens_enqueued + n_generations - 1;
     const int32_t NG = n_generations > 0 ? pipe_groups(s, P) : 1;
     s->last_groups = NG;
     std::vector<WaGroupRun> groups((size_t)NG);
@@ -1075,6 +1140,16 @@ int wa_acs_run(wa_acs *s, int32_t n_generations)
     for (int32_t g = 0; g < n_generations; g++) {
         const bool sampled = s->prof && ((s->gens_enqueued % s->prof_every) == 0);
         const int32_t gen = s->gens_enqueued;  // generations since wa_acs_begin
+        if (conv && gen >= s->conv_until) {
+            const int32_t W = conv_window_at(s, gen, gen_last);
+            if (W >= 1) {
+                for (int32_t k = 0; k < NG; k++) {
+                    const hipError_t le = launch_converged(s, groups[(size_t)k], gen, W);
+                    if (le != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_acs_run: k_converged_run: %s", hipGetErrorString(le));
+                }
+                s->conv_until = gen + W;
+            }
+        }
         for (int32_t k = 0; k < NG; k++)
             enqueue_generation(s, groups[(size_t)k], gen, g + 1 == n_generations, sampled, fused, chunks, shmem, P);
         s->gens_enqueued++;
@@ -1461,3 +1536,21 @@ int wa_acs_evaporate(wa_acs *s, int32_t slot, float rho, int32_t repeats)
     return WA_OK;
 }
 
+// What the converged-run mechanism did for a slot since the solver was created: [0] windows enqueued, [1] windows committed whole, [2] windows cut
+// (0 < j < W), [3] generations committed.  All zero for a solver that runs none (WA_CONVERGED_RUN=0, lazy fields, 26 neighbours, REF mode).
+int wa_acs_converged_info(wa_acs *s, int32_t slot, uint64_t out[4])
+{
+    WaDevGuard dev_guard_(s ? s->ctx : nullptr);
+    if (!dev_guard_.ok) return WA_ERR_DEVICE;
+    if (!s || !out || slot < 0 || slot >= s->n_slots) return WA_ERR_ARG;
+    wa_ctx *ctx = s->ctx;
+    out[0] = s->conv_enqueued[(size_t)slot];
+    out[1] = out[2] = out[3] = 0;
+    if (!s->d_conv) return WA_OK;
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    WaConvHdr h;
+    HIPC(ctx, hipMemcpyAsync(&h, s->d_conv + (int64_t)slot * s->D.conv_stride, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    out[1] = h.whole; out[2] = h.cut; out[3] = h.gens;
+    return WA_OK;
+}

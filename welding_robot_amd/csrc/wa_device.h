@@ -57,7 +57,7 @@ struct WaSlotCtl {
     uint32_t evap_base;     // evaporations applied to the field before generation 0 of the current solve (carried across solves)
     int32_t tabu_gen;       // generation in which the best path last changed: the replay-table rows of that generation rebuild besttabu[]
     int32_t heur_slot;      // whose heuristic field this search reads: searches of one wa_acs_begin with the same end point share one
-    int32_t pad_;
+    int32_t spec_until;     // generations below this one are already in the field's books (k_converged_run committed them): their launches step over; 0 = none
     // bit o-1: rank o of the generation just ranked belongs to an ant that arrived on the replay track (its path is the best path, word for word).
     // The post-walk launch marks all of them through the lowest one; the apply pass skips the others (never an edge's lowest rank).  0 from k_rank
     unsigned long long rep_mask;

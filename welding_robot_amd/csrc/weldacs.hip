@@ -177,6 +177,14 @@ struct wa_acs {
     // (chunked runs, generation-by-generation loops): behind a lone call the drain launch would only add to what the caller waits for
     // (measured on bench.py --steps 20: -1 %).  ran_before / read_since_run track that pattern.
     bool ran_before = false, read_since_run = false, chained = false;
+    // converged generations in one launch (acs_converged.hpp, k_converged_run)
+    bool conv_on = true;                 // WA_CONVERGED_RUN (read at creation); off by rule for lazy fields, 26 neighbours, REF mode, colonies past the fused path
+    int32_t conv_window = 32;            // WA_CONVERGED_WINDOW: generations a window covers at most
+    int32_t conv_nodes_env = 0;          // WA_CONVERGED_NODES: a lower cap on the best path a window covers (tests); 0 = WA_CONV_NODE_CAP
+    int32_t conv_until = 0;              // generations below this one are covered by a window already enqueued
+    char *d_conv = nullptr;              // the slots' scratch blocks (header + snapshots), allocated by the first call that enqueues a window
+    int32_t conv_snaps = 0;              // snapshots a scratch block holds
+    std::vector<uint64_t> conv_enqueued; // per slot: windows enqueued since the solver was created
 };
 
 static int fail(wa_ctx *c, int code, const char *fmt, const char *a = "", const char *b = "")
