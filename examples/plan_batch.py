@@ -138,6 +138,62 @@ def plan_safe(grid, point_ids, radius, rank=0, world=1, shortcut=0):
     return cost, paths, len(mine)
 
 
+def plan_diagonal(grid, point_ids, step, rank=0, world=1, shortcut=0):
+    """--diagonal-paths A B C: the pair paths from the exact planner with diagonal moves (wa_grid_chamfer_paths: face, edge and corner
+    moves cost A, B, C; a diagonal move needs the whole box it spans free) instead of the colony.  The chamfer matrix of the points comes
+    first (what a seam order in this metric would start from; here it is held against the paths' distances).  A pair's cost for the
+    seam order is a length in metres, as in plan_exact.  Same return values as plan(); pair k belongs to rank k % world."""
+    P = len(point_ids)
+    pairs = [(i, j) for i in range(P) for j in range(i + 1, P)]
+    mine = [k for k in range(len(pairs)) if k % world == rank]
+    t0 = time.perf_counter()
+    matrix = grid.chamfer_matrix(step, point_ids)
+    t1 = time.perf_counter()
+    dist, lens, ids_all = api.chamfer_paths(grid, step, [point_ids[pairs[k][0]] for k in mine], [point_ids[pairs[k][1]] for k in mine])
+    plan.last_diagonal = dict(step=[int(v) for v in step], t_matrix_s=t1 - t0, t_paths_s=time.perf_counter() - t1)
+    assert all(matrix[pairs[k]] == dist[q] for q, k in enumerate(mine)), "matrix and paths are two routes to the same distances"
+    ids_all = [np.zeros(0, np.int64) if p is None else p for p in ids_all]
+    wps, lengths = api.shortcut_paths(grid, ids_all, shortcut or 1)
+    cost = np.zeros((P, P), np.float64)
+    paths = {}
+    plan.last_slots, plan.last_create_s, plan.last_batch_s, plan.last_shortcut = 0, 0.0, [], {}
+    for q, k in enumerate(mine):
+        i, j = pairs[k]
+        cost[i, j] = cost[j, i] = lengths[q] if dist[q] >= 0 else np.inf
+        paths[(i, j)] = ids_all[q]
+        if shortcut:
+            plan.last_shortcut[(i, j)] = wps[q]
+    return cost, paths, len(mine)
+
+
+def diagonal_report(grid, pts, paths, short, shortcut):
+    """what goes into the JSON under diagonal_paths (rank 0, which holds every pair's path): the nodes, the moves by class, the length
+    before any shortcut, the segments of the unsmoothed paths that hit the planning grid (none: the box rule is wa_traj_clearance's
+    segment test) and, with --shortcut, the shortened total beside the one of the hop-optimal paths of the same pairs"""
+    reach = [ij for ij in sorted(paths) if len(paths[ij])]
+    nx, nxy = grid.nx, grid.nx * grid.ny
+    by_class = np.zeros(4, np.int64)
+    n_hit = 0
+    for ij in reach:
+        p = np.asarray(paths[ij], np.int64)
+        a, b = p[:-1], p[1:]
+        by_class += np.bincount((a % nx != b % nx).astype(np.int64) + ((a // nx) % grid.ny != (b // nx) % grid.ny) + (a // nxy != b // nxy), minlength=4)
+        t = api.Trajectory.stitch(grid, [p])
+        n_hit += t.clearance(grid)[3]["n_hit"]
+        t.close()
+    q = dict(plan.last_diagonal, nodes_total=int(sum(len(paths[ij]) for ij in reach)), moves_by_class=[int(v) for v in by_class[1:]],
+             length_total=float(api.shortcut_paths(grid, [paths[ij] for ij in reach], 1)[1].sum()), n_hit=int(n_hit))
+    if shortcut:
+        _, hop_paths = api.geodesic_paths(grid, [pts[i] for i, _ in reach], [pts[j] for _, j in reach])
+        hop_wps, hop_short = api.shortcut_paths(grid, hop_paths, shortcut)
+        q.update(shortened_length_total=float(api.shortcut_paths(grid, [short[ij] for ij in reach], 1)[1].sum()),
+                 length_total_hop_optimal=float(api.shortcut_paths(grid, hop_paths, 1)[1].sum()),
+                 shortened_length_total_hop_optimal=float(hop_short.sum()),
+                 waypoints_total=int(sum(len(short[ij]) for ij in reach)),
+                 waypoints_total_hop_optimal=int(sum(len(w) for w in hop_wps)))
+    return q
+
+
 def smooth(ctx, grid, segs, wsegs, rev, fit=None):
     """main.cpp:283-352 on the device: the tour's segments stitched, then the two smoothing passes; wsegs (--shortcut): the shortened
     segments, whose waypoints are then the coarse points of the cubic fit.  fit = (metal grid, max_level, dump path or None) (--fit):
@@ -285,6 +341,9 @@ def main():
     ap.add_argument("--safe-paths", type=int, default=0, choices=range(1, 8), metavar="R",
                     help="take the pair paths from the clearance-weighted exact planner (wa_grid_weighted_paths) instead of the colony: "
                          "entering a voxel costs 1 + the number of bands 1^2 .. R^2 (voxels squared) its distance to the metal lies within")
+    ap.add_argument("--diagonal-paths", type=int, nargs="*", default=None, metavar="STEP",
+                    help="take the pair paths from the exact planner with diagonal moves (wa_grid_chamfer_paths) instead of the colony: "
+                         "three step costs for face, edge and corner moves, each 1 .. 16 (default 3 4 5)")
     ap.add_argument("--fit", type=int, nargs="?", const=6, default=None, choices=range(0, 9), metavar="MAX_LEVEL",
                     help="needs --shortcut: the trajectory is wa_grid_fit_trajectory's (control points on the waypoints' polyline, refined "
                          "leg by leg up to MAX_LEVEL until the sampled curve clears the metal) instead of the cubic through the waypoints")
@@ -309,6 +368,10 @@ def main():
         ap.error("--torch works on the samples of --fit or --retime")
     if args.torch is not None and not 1 <= args.torch <= 256:
         ap.error("--torch takes 1 .. 256 directions")
+    if args.diagonal_paths is not None:
+        args.diagonal_paths = args.diagonal_paths or [3, 4, 5]
+        if len(args.diagonal_paths) != 3 or not all(1 <= v <= 16 for v in args.diagonal_paths):
+            ap.error("--diagonal-paths takes three step costs in 1 .. 16")
     if args.fit is not None and not args.shortcut:
         ap.error("--fit needs the waypoints of --shortcut")
     if args.seams and (args.points % 2 or args.points < 2):
@@ -350,6 +413,8 @@ def main():
     t0 = time.perf_counter()
     if args.safe_paths:
         cost, paths, n_mine = plan_safe(grid, pts, args.safe_paths, rank, world, shortcut=args.max_span if args.shortcut else 0)
+    elif args.diagonal_paths is not None:
+        cost, paths, n_mine = plan_diagonal(grid, pts, args.diagonal_paths, rank, world, shortcut=args.max_span if args.shortcut else 0)
     elif args.exact_paths:
         cost, paths, n_mine = plan_exact(grid, pts, rank, world, shortcut=args.max_span if args.shortcut else 0)
     elif args.geodesic:
@@ -482,6 +547,8 @@ def main():
                 ptraj, pok = smooth.plain if args.fit is not None else (traj, ok)
                 q.update(n_hit=n_hit(ptraj, pok), n_hit_hop_optimal=n_hit(htraj, hok))
             out.update(safe_paths=q)
+        if args.diagonal_paths is not None and not args.safe_paths:
+            out.update(diagonal_paths=diagonal_report(grid, pts, paths, short, args.max_span if args.shortcut else 0))
         if args.clearance is not None:
             # the curve the robot follows, against the real obstacles: how close it comes, and whether it cuts through any
             final = api.Trajectory.from_points(ctx, traj[ok.astype(bool)])

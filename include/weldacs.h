@@ -479,8 +479,8 @@ int wa_grid_path_shortcut(const wa_grid *g, const int64_t *ids, const int64_t *o
 /* ---- exact shortest-path fields (not in the reference: its planner is the colony alone) ----
  * The graph: the free voxels of g (wa_grid_read_occupancy != 0); voxel (x, y, z) has raster id x + nx * (y + ny * z).  Two free voxels are
  * joined iff they differ by 1 in exactly one coordinate (the 6-neighbour lattice), every step costs 1.  Neighbours are taken in the fixed
- * order -x, +x, -y, +y, -z, +z; a neighbour outside the grid does not exist.  26-neighbour lattices have step weights 1, sqrt 2, sqrt 3
- * and need a different algorithm (unit steps make this breadth-first search): out of scope here.
+ * order -x, +x, -y, +y, -z, +z; a neighbour outside the grid does not exist.  26-neighbour lattices need a different algorithm (unit
+ * steps make this breadth-first search): see "exact shortest paths with diagonal moves" below, which takes integer step weights.
  * hops(s, v): the number of steps of a shortest such path from s to v; 0 for v = s; WA_HOPS_NONE when there is none (v lies in another
  *   component, or is occupied).  An int32, exact at any length a grid allows (also beyond 65 535).
  * path(s, e), for hops(s, e) = h >= 0: the h + 1 ids p_0 ... p_h with p_h = e and, for k = h ... 1, p_{k-1} = the first neighbour
@@ -556,6 +556,49 @@ int wa_grid_weighted_fields(const wa_grid *g, const uint8_t *cost, const int64_t
 int wa_grid_weighted_matrix(const wa_grid *g, const uint8_t *cost, const int64_t *point_ids, int32_t n_pts, int32_t *dist_out);
 int wa_grid_weighted_paths(const wa_grid *g, const uint8_t *cost, const int64_t *start_ids, const int64_t *end_ids, int32_t n_pairs,
                            const int64_t *off, int64_t *ids_out, int32_t *dist_out, int32_t *len_out);
+
+/* ---- exact shortest paths with diagonal moves: 26-neighbour chamfer fields (not in the reference) ----
+ * The graph: the nodes are the free voxels of g.  A move changes each coordinate by -1, 0 or +1, at least one of them; its class a in
+ * {1, 2, 3} is the number of coordinates that change (face, edge, corner).  The move u -> v exists iff all 2^a voxels of the box
+ * {u.x, v.x} x {u.y, v.y} x {u.z, v.z} are inside the grid and free, and it costs step[a - 1].  For two 26-neighbours the box rule is
+ * visible(u, v) of wa_grid_path_shortcut and the segment test of wa_traj_clearance (the full product set at a tie), so a returned path
+ * has no hit in wa_traj_clearance, under the proviso stated there for 6-neighbour paths.  The rule is symmetric, and so is dist.
+ * WA_STEP_MAX = 16.  step holds three int32 on the host, each in 1 .. WA_STEP_MAX; no order among them is required (3, 4, 5 approximates
+ *   the Euclidean 1, sqrt 2, sqrt 3 within 8 %; every distance stays an integer).
+ * dist(s, v): the least sum of step costs over such paths from s to v; 0 for v = s; WA_DIST_NONE where there is no path or v is occupied.
+ * path(s, e), for dist(s, e) >= 0: walking back from e, the predecessor of a node p with dist(s, p) = D > 0 is q = p + o for the first
+ *   offset o, in the fixed order below, such that the move q -> p exists and dist(s, q) = D - step[class(o) - 1]; the walk ends at s.
+ *   The order: the six face offsets -x, +x, -y, +y, -z, +z, then the 12 edge offsets, then the 8 corner offsets, edge and corner offsets
+ *   each sorted by (dz, dy, dx) ascending.  The path is returned start first; its number of nodes is an output of its own.
+ * Identities that follow from the definition:
+ *   step = {1, 2, 3}: dist equals hops of wa_grid_geodesic_fields bit for bit (a diagonal exists only where the face detours through its
+ *     box exist, so it never wins), and by the face-first order path equals wa_grid_geodesic_paths' path.
+ *   step = {1, 1, 1} on a grid without obstacles: dist is the Chebyshev distance max(|dx|, |dy|, |dz|).
+ *   step = {3, 4, 5} on a grid without obstacles: with the sorted |differences| a >= b >= c, dist = 3 (a - b) + 4 (b - c) + 5 c.
+ *
+ * The calls are stateless and repeatable: the same bytes on every call, whatever ran before on the grid.  WA_ERR_ARG, before any output
+ * is written: a NULL pointer (step included, also with a count of 0), a negative count, a step outside 1 .. WA_STEP_MAX, a grid for
+ * which max(step) * (n_free - 1) exceeds 2^31 - 1 (a distance might not fit int32; refused before any search), an id outside the grid
+ * or on an occupied voxel, decreasing offsets.  Counts of 0 with valid arguments succeed and write nothing.
+ *
+ * Memory: with R = max(step) + 1, a source costs R + 1 bitmaps of n / 8 bytes (rows in x padded to 64 voxels), plus 4 n bytes where a
+ * field is kept (_fields, _paths), plus its matrix row.  Sources are processed in chunks by the rule of the geodesic section (half of
+ * the free memory, at least 1, at most 65 535, WA_ERR_ALLOC when one source does not fit); results do not depend on the chunking.
+ *
+ * wa_grid_chamfer_fields: dist_out[s * n + v] = dist(src_ids[s], v) for every voxel v (n_src * n int32 on the host).
+ * wa_grid_chamfer_matrix: dist_out[i * n_pts + j] = dist(point_ids[i], point_ids[j]): symmetric, 0 on the diagonal, WA_DIST_NONE where
+ *   the two points are not connected.  No field is stored; a point's search ends as soon as its row is full.
+ * wa_grid_chamfer_paths: the protocol of wa_grid_weighted_paths.  Pair p = (start_ids[p], end_ids[p]); off holds n_pairs + 1
+ *   non-decreasing offsets and gives pair p the range ids_out[off[p] .. off[p+1]).  dist_out[p] and len_out[p] (the nodes of the path, 0
+ *   when unreachable) are filled for every pair.  A reachable pair whose range holds at least len_out[p] ids gets its path at
+ *   ids_out[off[p] .. off[p] + len_out[p]); later entries of its range are left untouched.  An unreachable pair writes nothing and is no
+ *   error.  If some reachable pair's range is too short, nothing is written into that pair's range, all other pairs are written as
+ *   usual and the call returns WA_ERR_CAPACITY: size off from len_out and call again.  Pairs that share a start share one field. */
+#define WA_STEP_MAX 16
+int wa_grid_chamfer_fields(const wa_grid *g, const int32_t step[3], const int64_t *src_ids, int32_t n_src, int32_t *dist_out);
+int wa_grid_chamfer_matrix(const wa_grid *g, const int32_t step[3], const int64_t *point_ids, int32_t n_pts, int32_t *dist_out);
+int wa_grid_chamfer_paths(const wa_grid *g, const int32_t step[3], const int64_t *start_ids, const int64_t *end_ids, int32_t n_pairs,
+                          const int64_t *off, int64_t *ids_out, int32_t *dist_out, int32_t *len_out);
 
 /* ---- trajectory fit that refines the spline until it clears the grid (not in the reference: main.cpp:337 fits through the path
  *      points as they are) ----

@@ -238,6 +238,25 @@ class Grid:
         cost = self._cost(cost)
         return self._search_rows(self.ctx.lib.wa_grid_weighted_matrix, (_ptr(cost),), ids, True)
 
+    @staticmethod
+    def _step(step):
+        step = np.ascontiguousarray(step, np.int32).reshape(-1)
+        assert step.size == 3, "step holds the costs of a face, an edge and a corner move"
+        return step
+
+    def chamfer_fields(self, step, ids):
+        """wa_grid_chamfer_fields: int32 [len(ids), n], the exact least sum of step costs on the 26-neighbour lattice of free voxels
+        (step = (face, edge, corner), each 1 .. WA_STEP_MAX; a diagonal move needs every voxel of the box it spans free) from each source
+        to every voxel; WA_DIST_NONE (-1) where there is no path"""
+        step = self._step(step)
+        return self._search_rows(self.ctx.lib.wa_grid_chamfer_fields, (_ptr(step),), ids, False)
+
+    def chamfer_matrix(self, step, ids):
+        """wa_grid_chamfer_matrix: int32 [P, P] of those distances between the points (symmetric, 0 on the diagonal, WA_DIST_NONE (-1)
+        where two points are not connected)"""
+        step = self._step(step)
+        return self._search_rows(self.ctx.lib.wa_grid_chamfer_matrix, (_ptr(step),), ids, True)
+
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.wa_grid_destroy(self.h)
@@ -297,6 +316,14 @@ def weighted_paths(grid, cost, starts, ends):
     is WA_DIST_NONE]), the paths in ranges of len ids (_paths_two_calls)"""
     cost = grid._cost(cost)
     (dist, lens), paths = _paths_two_calls(grid, grid.ctx.lib.wa_grid_weighted_paths, (_ptr(cost),), starts, ends, 2, lambda dist, lens: lens)
+    return dist, lens, paths
+
+
+def chamfer_paths(grid, step, starts, ends):
+    """wa_grid_chamfer_paths of a batch of pairs: (int32 dist, int32 node counts, [node-id array per pair, start first; None where dist
+    is WA_DIST_NONE]), the paths in ranges of len ids (_paths_two_calls)"""
+    step = grid._step(step)
+    (dist, lens), paths = _paths_two_calls(grid, grid.ctx.lib.wa_grid_chamfer_paths, (_ptr(step),), starts, ends, 2, lambda dist, lens: lens)
     return dist, lens, paths
 
 
