@@ -197,7 +197,10 @@ int wa_acs_rand_state(wa_acs *s, int32_t state36_inout[36], int32_t set);
 
 /* start n_problems searches on slots 0..n-1 (setPoints already resolved to voxel ids; streams[i]
  * is the DEV-mode stream key of problem i, NULL = 0..n-1), then advance all of them by
- * n_generations (enqueued on the context stream, asynchronous), then wait. */
+ * n_generations (enqueued on the context stream, asynchronous), then wait.
+ * wa_acs_run returns when everything is enqueued -- for a lone search whose converged generations run in windows (wa_acs_converged_info), once
+ * the last window of the call has reported to the host (wa_acs_converged_host_info): the call then waits, a bounded time, for the work in front
+ * of that window. */
 int wa_acs_begin(wa_acs *s, const wa_acs_params *p, int32_t n_problems, const int64_t *start_ids,
                  const int64_t *end_ids, const uint32_t *streams);
 int wa_acs_run(wa_acs *s, int32_t n_generations);
@@ -290,6 +293,15 @@ int wa_acs_set_stragglers(wa_acs *s, int32_t generations);
  * committed whole, [2] windows cut short by an ant that left the best path, [3] generations committed.  Results are bit-identical with the
  * mechanism on or off.  Waits for the work enqueued so far. */
 int wa_acs_converged_info(wa_acs *s, int32_t slot, uint64_t out[4]);
+/* A lone search (one active slot): every window of three generations or more reports the generations it committed to the host, through a word of pinned
+ * host memory, and wa_acs_run does not enqueue the launches of committed generations that would only return at their top (WA_CONVERGED_READBACK=0, read at
+ * wa_acs_create: enqueue them all, as for batches).  The host waits for a verdict at most WA_CONVERGED_WAIT_US microseconds (default 200000; 0: never) and no
+ * longer than the stream takes to drain; a wait given up enqueues every generation of the window, which is right whatever the window committed.
+ * Behind a window that committed whole the next window's flush (the two launches behind the walk of its last generation) is enqueued directly behind the
+ * window kernel, before the verdict: it flushes if that window commits whole too and returns at once otherwise (WA_CONVERGED_SPECULATE=0: never).
+ * out: [0] verdicts the host went to read since the solver was created, [1] generations whose launches were not enqueued, [2] speculative flushes
+ * cancelled, [3] waits given up, of [0].  Results are bit-identical with the read-back on or off.  Does not wait. */
+int wa_acs_converged_host_info(wa_acs *s, uint64_t out[4]);
 /* evaporation sweep alone (ACSRank_3D.hpp:268-272) over `slot` -- for roofline measurements */
 int wa_acs_evaporate(wa_acs *s, int32_t slot, float rho, int32_t repeats);
 

@@ -6,6 +6,9 @@ launches / total / average inside the window, the window's span from the first w
 three kernels against ms_per_step x K, and the roofline figure the window's sweep launches give.
 
   python tools/timed_window_stats.py <rocprof output dir or kernel_trace.csv> <bench json line file> [--csv out.csv]
+
+The run has to enqueue every generation's three launches: trace it with WA_CONVERGED_READBACK=0 (a lone search otherwise leaves out the launches of
+generations a window committed; tools/converged_split.py cuts such a trace).
 """
 import csv
 import glob
@@ -31,7 +34,7 @@ def main():
     t_first, t_last, total = None, None, 0.0
     for label, key in LOOP:
         mine = [(a, b) for a, b, k in rows if key in k]
-        assert len(mine) >= W + K, "%s: %d dispatches in the trace, the command enqueued at least %d" % (key, len(mine), W + K)
+        assert len(mine) >= W + K, "%s: %d dispatches in the trace, the command enqueued at least %d (traced without WA_CONVERGED_READBACK=0?)" % (key, len(mine), W + K)
         extra = len(mine) - (W + K)
         win = mine[W:W + K]
         us = [(b - a) / 1e3 for a, b in win]

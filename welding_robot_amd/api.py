@@ -400,6 +400,13 @@ class AcsSolver:
         self.ctx.check(self.ctx.lib.wa_acs_converged_info(self.h, slot, out))
         return dict(enqueued=int(out[0]), whole=int(out[1]), cut=int(out[2]), generations=int(out[3]))
 
+    def converged_host_info(self):
+        """what run() did with the windows' verdicts since the solver was created (a lone search): verdicts it went to read, generations whose
+        launches it did not enqueue, speculative launches cancelled, waits given up"""
+        out = (C.c_uint64 * 4)()
+        self.ctx.check(self.ctx.lib.wa_acs_converged_host_info(self.h, out))
+        return [int(v) for v in out]
+
     def set_stragglers(self, generations):
         """generations of a search during which ants may be handed over (0: off, < 0: default)"""
         self.ctx.check(self.ctx.lib.wa_acs_set_stragglers(self.h, generations))

@@ -14,6 +14,12 @@
 // no waiting on memory anywhere.  A block whose ant leaves the path (or dies) in generation g + t stops and reports t; block 0 runs the whole
 // window and writes, per generation, a snapshot of the path state to the slot's scratch block and the trace row.  The block that finishes last
 // (a ticket counter behind a fence) commits j = the smallest t reported.
+//
+// The verdict also goes to the HOST (wa_conv_report): a word of pinned, coherent host memory per slot takes (seq << 8) | j from every launch that is
+// given one -- from block 0 where the window does not apply (j = 0), from the committing block behind its writes otherwise.  The host reads it to leave
+// out the launches of committed generations (host_acs.inc: conv_verdict); nothing on the device ever waits for the host.  Behind a window that
+// committed whole the host enqueues the next window's flush before it has the verdict, marked WA_GEN_SPEC: such a flush does nothing unless the window
+// committed exactly up to its generation.
 #pragma once
 
 #define WA_CONV_THREADS 1024
@@ -80,7 +86,20 @@ __device__ __forceinline__ void wa_conv_ctl_step(WaSlotCtl &c, const WaRun &R, i
     }
 }
 
-__global__ __launch_bounds__(WA_CONV_THREADS) void k_converged_run(WaAcsDev D, WaRun R, int32_t gen0, int32_t W)
+// One lane's report of a window's verdict to the host.  j > 0: a system-scope fence and a release store -- everything this thread has seen written (a barrier in
+// front makes that the block's writes of ctl, perm and depA) is visible system-wide before the word is.  j == 0: nothing was committed, so there is
+// nothing to order the word behind, and the store is a plain system-scope one: no cache is written back for it (a window that commits nothing sits
+// between the launches of an exploring search).  verdict: the group's first slot's word, or null (no report)
+__device__ __forceinline__ void wa_conv_report(uint32_t *verdict, int32_t slot, uint32_t seq, int32_t j)
+{
+    if (!verdict) return;
+    if (j > 0) {
+        __threadfence_system();
+        __hip_atomic_store(verdict + slot, (seq << 8) | (uint32_t)j, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    } else __hip_atomic_store(verdict + slot, seq << 8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+__global__ __launch_bounds__(WA_CONV_THREADS) void k_converged_run(WaAcsDev D, WaRun R, int32_t gen0, int32_t W, uint32_t *verdict, uint32_t seq)
 {
     extern __shared__ float wa_conv_lds[];
     __shared__ WaSlotCtl s_c, s_c0;
@@ -96,7 +115,10 @@ __global__ __launch_bounds__(WA_CONV_THREADS) void k_converged_run(WaAcsDev D, W
         const WaStrag sg = wa_strag_of(D, slot);
         off = off || sg.pool_n[0] != 0 || sg.pool_n[1] != 0;
     }
-    if (off) return;
+    if (off) {   // (no ticket is taken on this path: block 0 reports that nothing was committed)
+        if (blk == 0 && tid == 0) wa_conv_report(verdict, slot, seq, 0);
+        return;
+    }
     float *s_rec = wa_conv_lds;                              // [conv_nodes][16]: records 0..5, heuristic 6..11, prefix-tabu bits 12
     float *s_row = wa_conv_lds + (int64_t)D.conv_nodes * 16;  // [conv_nodes][8]: the replay table's rows
     {
@@ -240,4 +262,7 @@ __global__ __launch_bounds__(WA_CONV_THREADS) void k_converged_run(WaAcsDev D, W
             D.depA[(int64_t)slot * D.max_colony + r] = ok ? (lambda - (float)o) * Q / bestL : 0.f;
         }
     }
+    // ---- the verdict, behind this block's writes of ctl, perm and depA
+    __syncthreads();
+    if (tid == 0) wa_conv_report(verdict, slot, seq, j);
 }

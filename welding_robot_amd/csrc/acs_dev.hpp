@@ -1,6 +1,12 @@
 // acs_dev.hpp -- the solver's device block (WaAcsDev), rank masks, straggler views, edge offsets and the per-problem kernels
 // (k_init_pheromone<NB>, k_heuristic<NB>, k_begin).  Part of acs_kernels.hpp (included from there, in this order).
 #pragma once
+
+// A SPECULATIVE flush (k_evap_rank_mark, k_apply_table; host_acs.inc: enqueue_spec_flush): this bit in the launch's generation number.  The launch is
+// enqueued before the host knows what the window in front of it committed: it flushes when the window committed up to its generation exactly
+// (ctl.spec_until == gen + 1) and does nothing at all otherwise
+#define WA_GEN_SPEC 0x40000000
+
 struct WaAcsDev {
     WaDims d;
     const float *cx, *cy, *cz;

@@ -335,6 +335,10 @@ __global__ __launch_bounds__(256) void k_evap_rank_mark(WaAcsDev D, WaRun R, con
     // committed generation is the flush: its sweep blocks apply the j evaporations the committed generations owe the field, one rounding each.  The field
     // sits where the window found it -- the host flipped src / dst j - 1 times since: this launch's src for odd j (out of place), its dst for even j
     // (in place) -- and ends up in dst, the buffer the host takes for current, either way
+    if (gen & WA_GEN_SPEC) {   // a speculative flush: only if the window committed exactly up to this generation
+        gen &= ~WA_GEN_SPEC;
+        if (gen + 1 != D.ctl[slot].spec_until) return;
+    }
     if (gen < D.ctl[slot].spec_until) {
         if (!SPARSE && NB == 6 && gen + 1 == D.ctl[slot].spec_until && (int32_t)blockIdx.x >= MB) {
             const int32_t j = wa_conv_pending(D, slot);

@@ -1059,6 +1059,10 @@ __global__ __launch_bounds__(256) void k_apply_table(WaAcsDev D, WaRun R, int32_
 {
     const int32_t slot = blockIdx.y;
     const int32_t spec_until = D.ctl[slot].spec_until;
+    if (gen & WA_GEN_SPEC) {   // a speculative flush (see WA_GEN_SPEC)
+        gen &= ~WA_GEN_SPEC;
+        if (gen + 1 != spec_until) return;
+    }
     if (gen + 1 < spec_until) return;
     // lazy evaporation: voxels that became dirty in this generation join the swept set from the next sweep on
     if (D.dcount && blockIdx.x == 0 && threadIdx.x == 0) D.dcount[slot * 2] = D.dcount[slot * 2 + 1];

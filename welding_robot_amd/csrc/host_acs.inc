@@ -180,6 +180,9 @@ static int acs_create_once(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, in
     if (s->conv_window > WA_CONV_MAX_WINDOW) s->conv_window = WA_CONV_MAX_WINDOW;
     if (s->conv_window < 1) s->conv_on = false;
     s->conv_nodes_env = env_int("WA_CONVERGED_NODES", 0);
+    s->conv_readback = env_int("WA_CONVERGED_READBACK", 1) != 0;
+    s->conv_wait_us = env_int("WA_CONVERGED_WAIT_US", 200000);
+    s->conv_spec = env_int("WA_CONVERGED_SPECULATE", 1) != 0;
     s->conv_enqueued.assign((size_t)n_slots, 0);
     {   // sweep grid: measured on MI355X -- 100 MB fields (128^3 x 6) peak at 4096 blocks (6.0 TB/s; 2048: 5.5, 8192: 5.8),
         // 436 MB fields (128^3 x 26) want 2-3 float4 per thread (49152 blocks: 6.1 TB/s; 32768: 5.9; 4096: 4.6)
@@ -363,6 +366,7 @@ void wa_acs_destroy(wa_acs *s)
     hipStreamSynchronize(s->ctx->stream);
     if (s->d_stage) hipFree(s->d_stage);
     if (s->d_conv) ctx_free(s->ctx, s->d_conv);
+    if (s->h_verdict) hipHostFree(s->h_verdict);
 #ifdef WA_STATE_HASH
     if (s->d_hashlog) hipFree(s->d_hashlog);
 #endif
@@ -577,6 +581,7 @@ int wa_acs_begin(wa_acs *s, const wa_acs_params *p, int32_t n_problems, const in
     s->begun = true;
     s->gens_enqueued = 0;
     s->conv_until = 0;
+    s->conv_prev_whole = false;
     s->ran_before = false;
     return WA_OK;
 }
@@ -934,11 +939,17 @@ static bool conv_rule(const wa_acs *s, bool fused)
     return s->conv_on && fused && !s->lazy && s->nb == 6 && s->R.rng_mode == WA_RNG_DEV && s->D.rtab != nullptr && s->colony_bound > 0;
 }
 // The scratch blocks: per slot a header and one snapshot of the path state per generation of a window.  They are taken from the context's allocator outside
-// the solver's plan, by the first call that needs them.  A device without room for them runs without windows.
+// the solver's plan, by the first call that needs them.  A device without room for them runs without windows.  With them comes the verdict word of every
+// slot, in pinned coherent host memory (k_converged_run writes it, conv_verdict polls it); a host without such memory runs its windows without read-back.
 static bool conv_scratch(wa_acs *s)
 {
     if (s->d_conv && s->conv_snaps >= s->conv_window) return true;
     wa_ctx *ctx = s->ctx;
+    if (s->conv_readback && !s->h_verdict) {
+        void *w = nullptr;
+        if (hipHostMalloc(&w, sizeof(uint32_t) * (size_t)s->n_slots, hipHostMallocCoherent) != hipSuccess) { (void)hipGetLastError(); s->conv_readback = false; }
+        else { memset(w, 0, sizeof(uint32_t) * (size_t)s->n_slots); s->h_verdict = static_cast<uint32_t *>(w); }
+    }
     if (s->d_conv) { hipStreamSynchronize(ctx->stream); ctx_free(ctx, s->d_conv); s->d_conv = nullptr; s->D.conv = nullptr; }
     int64_t nodes = s->D.path_cap < WA_CONV_NODE_CAP ? s->D.path_cap : WA_CONV_NODE_CAP;
     if (s->conv_nodes_env > 0 && s->conv_nodes_env < nodes) nodes = s->conv_nodes_env;
@@ -971,9 +982,45 @@ static int32_t conv_window_at(const wa_acs *s, int32_t gen, int32_t gen_last)
 static hipError_t launch_converged(wa_acs *s, WaGroupRun &G, int32_t gen, int32_t W)
 {
     G.V.pher = s->pher_buf[G.cur] + (int64_t)G.slot0 * s->D.pher_stride;   // the field as generation `gen` finds it
-    k_converged_run<<<dim3(WA_CONV_BLOCKS, (unsigned)G.P), WA_CONV_THREADS, (size_t)s->D.conv_nodes * WA_CONV_NODE_LDS, G.st>>>(G.V, s->R, gen, W);
+    uint32_t *verdict = s->conv_readback && s->h_verdict ? s->h_verdict + G.slot0 : nullptr;
+    k_converged_run<<<dim3(WA_CONV_BLOCKS, (unsigned)G.P), WA_CONV_THREADS, (size_t)s->D.conv_nodes * WA_CONV_NODE_LDS, G.st>>>(G.V, s->R, gen, W, verdict,
+                                                                                                                             s->conv_seq & 0xffffffu);
     for (int32_t q = 0; q < G.P; q++) s->conv_enqueued[(size_t)(G.slot0 + q)]++;
     return hipGetLastError();
+}
+// The verdict of the window just enqueued for a lone search (slot 0, sequence number conv_seq): j, the generations it committed, or -1 when the wait is
+// given up -- the stream has drained without the word changing, or WA_CONVERGED_WAIT_US (default 200 000: far beyond any window; 0 = never wait) have
+// passed.  The caller then enqueues every generation of the window, which is right for any j: a lost verdict costs time, never results.
+#define WA_CONV_QUERY_US 2000
+static int32_t conv_verdict(wa_acs *s, hipStream_t st, int32_t W)
+{
+    const uint32_t want = s->conv_seq & 0xffffffu;
+    const uint32_t *word = s->h_verdict;
+    s->conv_host[0]++;
+    int32_t j = -1;
+    if (s->conv_wait_us > 0) {
+        // the word is polled; the clock is read every 256 polls, and the stream is looked at only every WA_CONV_QUERY_US of waiting: hipStreamQuery is not
+        // free for the queue it asks about, and a verdict is never later than the work in front of its window
+        const auto t0 = std::chrono::steady_clock::now();
+        int64_t next_query = WA_CONV_QUERY_US;
+        for (uint32_t spin = 1;; spin++) {
+            uint32_t v = __atomic_load_n(word, __ATOMIC_ACQUIRE);
+            if ((v >> 8) == want) { j = (int32_t)(v & 0xffu); break; }
+            if (spin & 255u) { __builtin_ia32_pause(); continue; }
+            const int64_t waited = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+            if (waited > s->conv_wait_us) break;
+            if (waited >= next_query) {
+                next_query = waited + WA_CONV_QUERY_US;
+                const hipError_t q = hipStreamQuery(st);
+                if (q == hipErrorNotReady) { (void)hipGetLastError(); continue; }
+                v = __atomic_load_n(word, __ATOMIC_ACQUIRE);   // drained (or failed): the kernel is over, the word says so or never will
+                if ((v >> 8) == want) j = (int32_t)(v & 0xffu);
+                break;
+            }
+        }
+    }
+    if (j < 0 || j > W) { s->conv_host[3]++; return -1; }
+    return j;
 }
 
 // The last generation of the previous wa_acs_run handed stragglers over and no further generation has been enqueued: finish them now
@@ -1048,12 +1095,31 @@ int wa_acs_pipeline_info(const wa_acs *s, int32_t *groups_last_run)
     return WA_OK;
 }
 
+// The flush of generation `gen` of a lone search, SPECULATIVE (WA_GEN_SPEC): enqueued directly behind a window [g, gen] before the host has its verdict.
+// The two launches flush if the window committed whole and return at their top otherwise.  No walk launch: the walk of a flush generation returns at
+// its top either way.  The caller has flipped G.cur as the generations in front of `gen` would have
+static hipError_t enqueue_spec_flush(wa_acs *s, WaGroupRun &G, int32_t gen)
+{
+    const int64_t off = (int64_t)G.slot0 * s->D.pher_stride;
+    float *src = s->pher_buf[G.cur] + off, *dst = s->pher_buf[G.cur ^ 1] + off;
+    G.V.pher = src;
+    G.V.prev_pher = dst;
+    launch_fused(s, G, src, dst, gen | WA_GEN_SPEC, false);
+    G.cur ^= 1;
+    G.V.pher = dst;
+    const int32_t SL = 2, TB = WA_TABLE_BLOCKS_MAX;   // (one search: as enqueue_generation)
+    k_apply_table<<<dim3((unsigned)(TB + ((mark_blocks(s) >> 3) << SL)), (unsigned)G.P), 256, 0, G.st>>>(G.V, s->R, SL, TB, gen | WA_GEN_SPEC);
+    return hipGetLastError();
+}
+
 // n_generations of every active search.  The active slots are split into groups (pipe_groups) that advance independently of each
 // other on streams of their own -- the searches ARE independent (ACSRank_3D.hpp:472-499: a loop over searches with a pheromone reset
 // in between), so one group's HBM-bound sweep (:268-272) runs under another group's latency-bound walk (:252-261) -- forked from the
 // context's stream at the start of the call and joined into it at the end: whatever the caller enqueues on the context's stream
 // afterwards (results, the RCCL exchange, another call) is ordered behind all groups.  Every slot's own launch order is the single-stream
 // one, so results do not depend on the split.
+// A lone search (one slot, one group) whose converged generations run in windows: the host reads every window's verdict (conv_verdict) and leaves out
+// the launches of committed generations, so the call returns once its last window has reported, not when everything is enqueued.
 int wa_acs_run(wa_acs *s, int32_t n_generations)
 {
     WaDevGuard dev_guard_(s ? s->ctx : nullptr);
@@ -1108,6 +1174,7 @@ int wa_acs_run(wa_acs *s, int32_t n_generations)
     }
 #endif
     const bool conv = n_generations > 1 && conv_rule(s, fused) && conv_scratch(s);
+    const bool readback = conv && s->conv_readback && s->h_verdict && P == 1;   // (one search is one group)
     const int32_t gen_last = s->gens_enqueued + n_generations - 1;
     const int32_t NG = n_generations > 0 ? pipe_groups(s, P) : 1;
     s->last_groups = NG;
@@ -1140,9 +1207,13 @@ int wa_acs_run(wa_acs *s, int32_t n_generations)
     for (int32_t g = 0; g < n_generations; g++) {
         const bool sampled = s->prof && ((s->gens_enqueued % s->prof_every) == 0);
         const int32_t gen = s->gens_enqueued;  // generations since wa_acs_begin
+        int32_t ask = 0;                       // the window whose verdict the host reads (generations it covers)
         if (conv && gen >= s->conv_until) {
             const int32_t W = conv_window_at(s, gen, gen_last);
             if (W >= 1) {
+                s->conv_seq++;
+                // a lone search: a window of three generations or more may commit generations whose launches need not be enqueued at all
+                if (readback && W >= 3) ask = W;
                 for (int32_t k = 0; k < NG; k++) {
                     const hipError_t le = launch_converged(s, groups[(size_t)k], gen, W);
                     if (le != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_acs_run: k_converged_run: %s", hipGetErrorString(le));
@@ -1150,9 +1221,50 @@ int wa_acs_run(wa_acs *s, int32_t n_generations)
                 s->conv_until = gen + W;
             }
         }
+        int32_t known = -2;                    // the verdict, where the host has it already
+        if (ask && s->conv_spec && s->conv_prev_whole && s->conv_wait_us > 0) {
+            // The search's last window committed whole: this one will, most likely.  Its flush -- the launches of generation gen+ask-1 -- goes directly behind
+            // it, marked speculative, in place of generation gen's launches; the buffers are flipped as the ask-1 generations in front of it would have.
+            WaGroupRun &G = groups[0];
+            const int cur0 = G.cur;
+            G.cur ^= (ask - 1) & 1;
+            const hipError_t fe = enqueue_spec_flush(s, G, gen + ask - 1);
+            if (fe != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_acs_run: speculative flush: %s", hipGetErrorString(fe));
+            known = conv_verdict(s, G.st, ask);
+            if (known < 0) {
+                // given up, and the launches behind the window flush or not: the host has to know which before it enqueues anything else
+                HIPC(ctx, hipStreamSynchronize(G.st));
+                const uint32_t v = __atomic_load_n(s->h_verdict, __ATOMIC_ACQUIRE);
+                if ((v >> 8) != (s->conv_seq & 0xffffffu) || (int32_t)(v & 0xffu) > ask) return fail(ctx, WA_ERR_DEVICE, "wa_acs_run: a window ended without its verdict");
+                known = (int32_t)(v & 0xffu);
+            }
+            if (known == ask) {   // every generation of the window is in the field's books: none of gen .. gen+ask-2 is enqueued
+                s->gens_enqueued += ask;
+                s->conv_host[1] += (uint64_t)(ask - 1);
+                g += ask - 1;
+                continue;
+            }
+            G.cur = cur0;         // cancelled: the two launches return at their top; on as without them
+            s->conv_host[2]++;
+            s->conv_prev_whole = false;
+        }
         for (int32_t k = 0; k < NG; k++)
             enqueue_generation(s, groups[(size_t)k], gen, g + 1 == n_generations, sampled, fused, chunks, shmem, P);
         s->gens_enqueued++;
+        if (ask) {
+            // Generation gen's launches (a full generation, the flush or launches that return at once, whichever the device finds) are behind the window: the
+            // host reads the verdict while they run.  j >= 2: the launches of generations gen+1 .. gen+j-2 would return at their top -- they are not
+            // enqueued; the host flips the field's buffers and counts the generations as it would have, so that the flush of generation gen+j-1 (enqueued
+            // next, under its own number) finds src / dst and the path arrays' parity as ever.  The next window stays where it was: conv_until
+            const int32_t j = known != -2 ? known : conv_verdict(s, groups[0].st, ask);
+            s->conv_prev_whole = j == ask;
+            for (int32_t t = 2; t < j; t++) {
+                groups[0].cur ^= 1;
+                s->gens_enqueued++;
+                s->conv_host[1]++;
+                g++;
+            }
+        }
     }
     for (int32_t k = 1; k < NG; k++) {
         HIPC(ctx, hipEventRecord(s->gjoin[(size_t)k - 1], groups[(size_t)k].st));
@@ -1536,6 +1648,15 @@ int wa_acs_evaporate(wa_acs *s, int32_t slot, float rho, int32_t repeats)
     return WA_OK;
 }
 
+// What the host did with the windows' verdicts since the solver was created (a lone search only; all zero with WA_CONVERGED_READBACK=0, for batches and
+// for solvers that run no windows): [0] verdicts the host went to read, [1] generations whose launches were not enqueued, [2] speculative flushes
+// cancelled (the window in front of them did not commit whole), [3] waits given up, of [0].
+int wa_acs_converged_host_info(wa_acs *s, uint64_t out[4])
+{
+    if (!s || !out) return WA_ERR_ARG;
+    for (int i = 0; i < 4; i++) out[i] = s->conv_host[i];
+    return WA_OK;
+}
 // What the converged-run mechanism did for a slot since the solver was created: [0] windows enqueued, [1] windows committed whole, [2] windows cut
 // (0 < j < W), [3] generations committed.  All zero for a solver that runs none (WA_CONVERGED_RUN=0, lazy fields, 26 neighbours, REF mode).
 int wa_acs_converged_info(wa_acs *s, int32_t slot, uint64_t out[4])

@@ -186,6 +186,14 @@ struct wa_acs {
     char *d_conv = nullptr;              // the slots' scratch blocks (header + snapshots), allocated by the first call that enqueues a window
     int32_t conv_snaps = 0;              // snapshots a scratch block holds
     std::vector<uint64_t> conv_enqueued; // per slot: windows enqueued since the solver was created
+    // ... and their verdicts read back by the host (conv_verdict): the launches of committed generations of a lone search are not enqueued
+    bool conv_readback = true;           // WA_CONVERGED_READBACK (read at creation)
+    int32_t conv_wait_us = 200000;       // WA_CONVERGED_WAIT_US: the longest the host waits for one verdict
+    uint32_t *h_verdict = nullptr;       // [slot]: (seq << 8) | j of the slot's last window; pinned, coherent host memory, allocated and freed with d_conv
+    uint32_t conv_seq = 0;               // sequence number of the last window enqueued
+    uint64_t conv_host[4] = {0, 0, 0, 0};   // wa_acs_converged_host_info
+    bool conv_spec = true;               // WA_CONVERGED_SPECULATE (read at creation): behind a window that committed whole, the next window's flush is enqueued before its verdict
+    bool conv_prev_whole = false;        // the last window of the running search whose verdict was read committed whole
 };
 
 static int fail(wa_ctx *c, int code, const char *fmt, const char *a = "", const char *b = "")
