@@ -166,6 +166,78 @@ def plan_diagonal(grid, point_ids, step, rank=0, world=1, shortcut=0):
     return cost, paths, len(mine)
 
 
+def plan_safe_diagonal(grid, point_ids, radius, step, gain, rank=0, world=1, shortcut=0):
+    """--safe-paths R with --diagonal-paths A B C: the pair paths from the exact planner with diagonal moves AND clearance penalties
+    (wa_grid_chamfer_weighted_paths): a move costs its step plus gain * (the number of bands 1^2 .. R^2 the voxel entered lies within),
+    so the paths are short like the diagonal ones and keep off the metal like the safe ones where there is room.  The matrix of the
+    points comes first and is held against the paths' distances.  A pair's cost for the seam order is a length in metres, as in
+    plan_exact.  Same return values as plan(); pair k belongs to rank k % world."""
+    P = len(point_ids)
+    pairs = [(i, j) for i in range(P) for j in range(i + 1, P)]
+    mine = [k for k in range(len(pairs)) if k % world == rank]
+    bands = [k * k for k in range(1, radius + 1)]
+    t0 = time.perf_counter()
+    costs = grid.clearance_costs(bands)
+    pen = (gain * np.maximum(costs.astype(np.int64) - 1, 0)).astype(np.uint8)   # (occupied voxels hold cost 0; their bytes are ignored)
+    t1 = time.perf_counter()
+    matrix = grid.chamfer_weighted_matrix(step, pen, point_ids)
+    t2 = time.perf_counter()
+    dist, lens, ids_all = api.chamfer_weighted_paths(grid, step, pen, [point_ids[pairs[k][0]] for k in mine], [point_ids[pairs[k][1]] for k in mine])
+    plan.last_safe_diagonal = dict(step=[int(v) for v in step], gain=int(gain), bands=bands, t_costs_s=t1 - t0, t_matrix_s=t2 - t1,
+                                   t_paths_s=time.perf_counter() - t2)
+    plan.last_pen, plan.last_costs = pen, costs
+    assert all(matrix[pairs[k]] == dist[q] for q, k in enumerate(mine)), "matrix and paths are two routes to the same distances"
+    ids_all = [np.zeros(0, np.int64) if p is None else p for p in ids_all]
+    wps, lengths = api.shortcut_paths(grid, ids_all, shortcut or 1)
+    cost = np.zeros((P, P), np.float64)
+    paths = {}
+    plan.last_slots, plan.last_create_s, plan.last_batch_s, plan.last_shortcut = 0, 0.0, [], {}
+    for q, k in enumerate(mine):
+        i, j = pairs[k]
+        cost[i, j] = cost[j, i] = lengths[q] if dist[q] >= 0 else np.inf
+        paths[(i, j)] = ids_all[q]
+        if shortcut:
+            plan.last_shortcut[(i, j)] = wps[q]
+    return cost, paths, len(mine)
+
+
+def path_counts(grid, metal, pen, path_list, shortcut):
+    """the counts of safe_diagonal_report for one planner's paths of the same pairs: nodes, moves by class, the penalties entered, nodes
+    next to the metal (distance field <= 1), segments of the unsmoothed paths that hit the planning grid, the length and, with
+    --shortcut, the shortened length and its waypoints"""
+    nx, nxy = grid.nx, grid.nx * grid.ny
+    d2 = metal.distance_field()
+    by_class = np.zeros(4, np.int64)
+    n_hit = penalty = near = 0
+    for p in path_list:
+        p = np.asarray(p, np.int64)
+        a, b = p[:-1], p[1:]
+        by_class += np.bincount((a % nx != b % nx).astype(np.int64) + ((a // nx) % grid.ny != (b // nx) % grid.ny) + (a // nxy != b // nxy), minlength=4)
+        penalty += int(pen[b].astype(np.int64).sum())
+        near += int((d2[p] <= 1).sum())
+        t = api.Trajectory.stitch(grid, [p])
+        n_hit += t.clearance(grid)[3]["n_hit"]
+        t.close()
+    q = dict(nodes_total=int(sum(len(p) for p in path_list)), moves_by_class=[int(v) for v in by_class[1:]], penalty_total=int(penalty),
+             nodes_next_to_metal=int(near), n_hit=int(n_hit), length_total=float(api.shortcut_paths(grid, path_list, 1)[1].sum()))
+    if shortcut:
+        wps, lengths = api.shortcut_paths(grid, path_list, shortcut)
+        q.update(shortened_length_total=float(lengths.sum()), waypoints_total=int(sum(len(w) for w in wps)))
+    return q
+
+
+def safe_diagonal_report(grid, metal, pts, paths, shortcut):
+    """what goes into the JSON under safe_diagonal_paths (rank 0, which holds every pair's path): path_counts of the new paths, and of the
+    diagonal paths (wa_grid_chamfer_paths, the same steps) and the safe paths (wa_grid_weighted_paths, the same bands) of the same pairs"""
+    reach = [ij for ij in sorted(paths) if len(paths[ij])]
+    info = plan.last_safe_diagonal
+    starts, ends = [pts[i] for i, _ in reach], [pts[j] for _, j in reach]
+    q = dict(info, **path_counts(grid, metal, plan.last_pen, [paths[ij] for ij in reach], shortcut))
+    q.update(diagonal=path_counts(grid, metal, plan.last_pen, api.chamfer_paths(grid, info["step"], starts, ends)[2], shortcut),
+             safe=path_counts(grid, metal, plan.last_pen, api.weighted_paths(grid, plan.last_costs, starts, ends)[2], shortcut))
+    return q
+
+
 def diagonal_report(grid, pts, paths, short, shortcut):
     """what goes into the JSON under diagonal_paths (rank 0, which holds every pair's path): the nodes, the moves by class, the length
     before any shortcut, the segments of the unsmoothed paths that hit the planning grid (none: the box rule is wa_traj_clearance's
@@ -344,6 +416,9 @@ def main():
     ap.add_argument("--diagonal-paths", type=int, nargs="*", default=None, metavar="STEP",
                     help="take the pair paths from the exact planner with diagonal moves (wa_grid_chamfer_paths) instead of the colony: "
                          "three step costs for face, edge and corner moves, each 1 .. 16 (default 3 4 5)")
+    ap.add_argument("--safe-gain", type=int, default=None, metavar="G",
+                    help="--safe-paths R together with --diagonal-paths (wa_grid_chamfer_weighted_paths): entering a voxel adds G per band "
+                         "it lies within to the move's step cost (default: the face step); G * R is at most 31")
     ap.add_argument("--fit", type=int, nargs="?", const=6, default=None, choices=range(0, 9), metavar="MAX_LEVEL",
                     help="needs --shortcut: the trajectory is wa_grid_fit_trajectory's (control points on the waypoints' polyline, refined "
                          "leg by leg up to MAX_LEVEL until the sampled curve clears the metal) instead of the cubic through the waypoints")
@@ -372,6 +447,12 @@ def main():
         args.diagonal_paths = args.diagonal_paths or [3, 4, 5]
         if len(args.diagonal_paths) != 3 or not all(1 <= v <= 16 for v in args.diagonal_paths):
             ap.error("--diagonal-paths takes three step costs in 1 .. 16")
+    both = bool(args.safe_paths) and args.diagonal_paths is not None
+    if both:
+        if args.safe_gain is None:
+            args.safe_gain = args.diagonal_paths[0]
+        if args.safe_gain < 0 or args.safe_gain * args.safe_paths > 31:
+            ap.error("--safe-gain times --safe-paths is at most 31 (WA_PEN_MAX)")
     if args.fit is not None and not args.shortcut:
         ap.error("--fit needs the waypoints of --shortcut")
     if args.seams and (args.points % 2 or args.points < 2):
@@ -411,7 +492,10 @@ def main():
         t_geo = time.perf_counter() - t_geo
         unreachable = [(i, j) for i in range(args.points) for j in range(i + 1, args.points) if hop_matrix[i, j] == api.WA_HOPS_NONE]
     t0 = time.perf_counter()
-    if args.safe_paths:
+    if both:
+        cost, paths, n_mine = plan_safe_diagonal(grid, pts, args.safe_paths, args.diagonal_paths, args.safe_gain, rank, world,
+                                                 shortcut=args.max_span if args.shortcut else 0)
+    elif args.safe_paths:
         cost, paths, n_mine = plan_safe(grid, pts, args.safe_paths, rank, world, shortcut=args.max_span if args.shortcut else 0)
     elif args.diagonal_paths is not None:
         cost, paths, n_mine = plan_diagonal(grid, pts, args.diagonal_paths, rank, world, shortcut=args.max_span if args.shortcut else 0)
@@ -522,7 +606,14 @@ def main():
             stops = np.stack([cx[first % metal.nx], cy[(first // metal.nx) % metal.ny], cz[first // (metal.nx * metal.ny)]], 1)
             out.update(torch=torch_stage(ctx, metal, np.ascontiguousarray(traj[ok.astype(bool)], np.float32), stops, args.torch),
                        t_torch_s=time.perf_counter() - t4)
-        if args.safe_paths:
+        if both:
+            q = safe_diagonal_report(grid, metal, pts, paths, args.max_span if args.shortcut else 0)
+            if args.shortcut:
+                # as safe_paths' n_hit: segments of the cubic through the tour's waypoints that cut the metal (without --fit's refinement)
+                ptraj, pok = smooth.plain if args.fit is not None else (traj, ok)
+                q.update(n_hit_cubic=int(api.Trajectory.from_points(ctx, ptraj[pok.astype(bool)]).clearance(metal)[3]["n_hit"]))
+            out.update(safe_diagonal_paths=q)
+        if args.safe_paths and not both:
             # what the soft margin buys and costs, against the hop-optimal paths of the same pairs in the same seam order: steps over
             # the optimum, path nodes inside the outermost band, and (--shortcut) segments of the smoothed curve that cut the metal
             P = args.points

@@ -612,6 +612,47 @@ int wa_grid_chamfer_matrix(const wa_grid *g, const int32_t step[3], const int64_
 int wa_grid_chamfer_paths(const wa_grid *g, const int32_t step[3], const int64_t *start_ids, const int64_t *end_ids, int32_t n_pairs,
                           const int64_t *off, int64_t *ids_out, int32_t *dist_out, int32_t *len_out);
 
+/* ---- exact shortest paths with diagonal moves and clearance penalties (not in the reference) ----
+ * The graph, the box rule for a move, the three classes, step[3] in 1 .. WA_STEP_MAX and the order of the 26 offsets are exactly those
+ * of the section above.  New is a penalty per voxel, paid on entry, which keeps paths off the metal where there is room and still lets
+ * them through gaps that wa_grid_inflate would close.
+ * WA_PEN_MAX = 31.  pen is n = nx * ny * nz bytes on the host in raster order, like wa_grid_read_occupancy.  Every free voxel holds a
+ *   value in 0 .. WA_PEN_MAX; the bytes of occupied voxels are ignored.
+ * The move u -> v costs step[class - 1] + pen[v].  The penalty is per voxel ENTERED, not per length: a corner move pays it once, like a
+ *   face move.  The start is not paid for.
+ * dist(s, v): the least sum of move costs over paths from s to v; dist(s, s) = 0; WA_DIST_NONE where there is no path or v is occupied.
+ * path(s, e), for dist(s, e) >= 0: walking back from e, the predecessor of a node p with dist(s, p) = D > 0 is q = p + o for the first
+ *   offset o, in the order of the section above, such that the move exists and dist(s, q) = D - pen[p] - step[class(o) - 1] >= 0; the walk
+ *   ends at s.  The path is returned start first; its number of nodes is an output of its own.
+ * Identities that follow from the definition:
+ *   (a) pen = 0 on every free voxel: dist, the matrix and the paths are the bytes of wa_grid_chamfer_fields / _matrix / _paths, for any step.
+ *   (b) pen = c on every free voxel: they are those of the chamfer calls with step[k] + c, where these fit WA_STEP_MAX.
+ *   (c) dist(s, e) - dist(e, s) = pen[e] - pen[s] (a path reversed enters the same voxels but for its two ends), so the matrix is NOT
+ *       symmetric; pen[s] + dist(s, e) is.  Reachability is symmetric.
+ *
+ * The calls are stateless and repeatable: the penalty array comes in with each call, nothing about it is kept with the grid, and the
+ * same bytes come back on every call, in any chunking.  WA_ERR_ARG, before any output is written: everything the section above refuses
+ * (a NULL pointer, step included, also with a count of 0; a negative count; a step outside 1 .. WA_STEP_MAX; max(step) * (n_free - 1)
+ * above 2^31 - 1; an id outside the grid or on an occupied voxel; decreasing offsets), a NULL pen (also with a count of 0), a free voxel
+ * whose penalty is above WA_PEN_MAX, and a grid for which (max(step) + the largest penalty present on a free voxel) * (n_free - 1)
+ * exceeds 2^31 - 1 (a distance might not fit int32; refused before any search).  Counts of 0 with valid pointers succeed, write nothing
+ * and do not look at pen.
+ *
+ * Memory: a call keeps the penalty bytes (n) and five bitmaps of them on the device.  With R = max(step) + P + 1, P the largest penalty
+ * present on a free voxel, a source costs R + 1 bitmaps of n / 8 bytes (rows in x padded to 64 voxels), plus 4 n bytes where a field is
+ * kept (_fields, _paths), plus its matrix row.  Sources are processed in chunks by the rule of the geodesic section (half of the free
+ * memory, at least 1, at most 65 535, WA_ERR_ALLOC when one source does not fit); results do not depend on the chunking.
+ *
+ * wa_grid_chamfer_weighted_fields: dist_out[s * n + v] = dist(src_ids[s], v) for every voxel v (n_src * n int32 on the host).
+ * wa_grid_chamfer_weighted_matrix: dist_out[i * n_pts + j] = dist(point_ids[i], point_ids[j]): 0 on the diagonal, WA_DIST_NONE where the
+ *   two points are not connected, not symmetric (identity (c)).  No field is stored; a point's search ends as soon as its row is full.
+ * wa_grid_chamfer_weighted_paths: the protocol of wa_grid_chamfer_paths, WA_ERR_CAPACITY and what it leaves untouched included. */
+#define WA_PEN_MAX 31
+int wa_grid_chamfer_weighted_fields(const wa_grid *g, const int32_t step[3], const uint8_t *pen, const int64_t *src_ids, int32_t n_src, int32_t *dist_out);
+int wa_grid_chamfer_weighted_matrix(const wa_grid *g, const int32_t step[3], const uint8_t *pen, const int64_t *point_ids, int32_t n_pts, int32_t *dist_out);
+int wa_grid_chamfer_weighted_paths(const wa_grid *g, const int32_t step[3], const uint8_t *pen, const int64_t *start_ids, const int64_t *end_ids,
+                                   int32_t n_pairs, const int64_t *off, int64_t *ids_out, int32_t *dist_out, int32_t *len_out);
+
 /* ---- trajectory fit that refines the spline until it clears the grid (not in the reference: main.cpp:337 fits through the path
  *      points as they are) ----
  * A B-spline of degree D lies in the convex hull of D + 1 consecutive control points.  Control points placed ON a collision-free

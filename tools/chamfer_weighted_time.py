@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""Time the penalised 26-neighbour fields on the C5-sized job: the 256^3 synth_grid and its 64 weld points.  Prints the median and range
+of --reps whole calls after a warm-up (buffers, penalty upload and packing, searches, copies out; HIP events on the context's stream)
+for, alternating in one run: wa_grid_chamfer_matrix with --step (default 3 4 5), the yardstick, and wa_grid_chamfer_weighted_matrix with
+zero penalties (the same answers and the same levels: k_chm_level against k_cw_level like for like); then the matrix and the paths of
+all 2 016 pairs with penalties gain * (clearance cost - 1), bands 1, 4, 9, gain 3; and for each the launches of the longest search, the
+largest distance and the bytes a source costs.  Kernel times (mean and longest level): run it alone under
+`rocprofv3 --kernel-trace --stats -d <dir> -- python tools/chamfer_weighted_time.py --reps 3`.
+
+    python tools/chamfer_weighted_time.py [--reps N] [--grid N --points P] [--step A B C] [--gain G] [--no-paths]"""
+import ctypes as C
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+
+from welding_robot_amd import api, build, synth
+
+
+def arg(name, default):
+    return int(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+
+
+reps, n, P, gain = arg("--reps", 7), arg("--grid", 256), arg("--points", 64), arg("--gain", 3)
+step = [int(v) for v in sys.argv[sys.argv.index("--step") + 1:sys.argv.index("--step") + 4]] if "--step" in sys.argv else [3, 4, 5]
+bands = [1, 4, 9]
+hip = C.CDLL(os.path.join(build.rocm_lib_dir(), "libamdhip64.so"))
+ctx = api.Context(0)
+print("device:", ctx.device_name)
+free, cx, cy, cz, prec, wall = synth.synth_grid(n, seed=2024, occ_prob=0.10)
+grid = api.Grid.from_occupancy(ctx, free, cx, cy, cz, prec, wall)
+pts = synth.synth_weld_points(free, n, P, seed=7)
+stream = C.c_void_p(ctx.stream)
+a, b = C.c_void_p(), C.c_void_p()
+assert hip.hipEventCreate(C.byref(a)) == 0 and hip.hipEventCreate(C.byref(b)) == 0
+
+
+def once(fn):
+    ctx.sync()
+    hip.hipEventRecord(a, stream)
+    out = fn()
+    hip.hipEventRecord(b, stream)
+    hip.hipEventSynchronize(b)
+    ms = C.c_float()
+    hip.hipEventElapsedTime(C.byref(ms), a, b)
+    return out, ms.value
+
+
+def timed(fns, reps):
+    """the calls of fns in turn, reps + 1 rounds; the first round warms up (and builds the bit-packed occupancy)"""
+    times, outs = [[] for _ in fns], [None] * len(fns)
+    for r in range(reps + 1):
+        for k, fn in enumerate(fns):
+            outs[k], ms = once(fn)
+            if r:
+                times[k].append(ms)
+    return outs, times
+
+
+def line(name, times):
+    print("%s: median %.3f ms over %d calls (min %.3f, max %.3f)" % (name, np.median(times), len(times), min(times), max(times)))
+    return float(np.median(times))
+
+
+def launches(largest, window):
+    """level launches of the longest search of a matrix call: the driver enqueues blocks of 32 and stops after the block in which the
+    last live source ran `window` levels without an arrival; the kernels of dead sources return at once"""
+    return 32 * -(-(int(largest) + window + 1) // 32)
+
+
+words = ((n + 63) // 64) * n * n
+M = max(step)
+zero = np.zeros(grid.n, np.uint8)
+(m0, m1), (t0, t1) = timed([lambda: grid.chamfer_matrix(step, pts), lambda: grid.chamfer_weighted_matrix(step, zero, pts)], reps)
+c_ms = line("wa_grid_chamfer_matrix step %s, %d points on %d^3 (R = %d: %.1f MB per source)" % (step, P, n, M + 1, (M + 2) * words * 8 / 1e6), t0)
+z_ms = line("wa_grid_chamfer_weighted_matrix, zero penalties (R = %d: %.1f MB per source, + %.1f MB of penalty bytes and planes per call)"
+            % (M + 1, (M + 2) * words * 8 / 1e6, (grid.n + 5 * words * 8) / 1e6), t1)
+lv = launches(m0.max(), M)
+print("  same bytes: %s; largest distance %d, about %d launches each; whole-call ratio %.3f; per launch %.1f us against %.1f us"
+      % (m0.tobytes() == m1.tobytes(), m0.max(), lv, z_ms / c_ms, 1e3 * c_ms / lv, 1e3 * z_ms / lv))
+t_c, cost = once(lambda: grid.clearance_costs(bands))[::-1]
+pen = (gain * np.maximum(cost.astype(np.int64) - 1, 0)).astype(np.uint8)
+Pmax = int(pen[free != 0].max())
+R = M + Pmax + 1
+print("wa_grid_clearance_costs bands %s: %.3f ms; penalties gain %d: largest %d, free voxels with a penalty %.1f %%"
+      % (bands, t_c, gain, Pmax, 100.0 * float((pen[free != 0] > 0).mean())))
+(m,), (t,) = timed([lambda: grid.chamfer_weighted_matrix(step, pen, pts)], reps)
+ms = line("wa_grid_chamfer_weighted_matrix with penalties (R = %d: %d bitmaps, %.1f MB per source, %.0f MB for %d sources)"
+          % (R, R + 1, (R + 1) * words * 8 / 1e6, (R + 1) * P * words * 8 / 1e6, P), t)
+lv = launches(m.max(), M + Pmax)
+asym = m.astype(np.int64) - m.T
+pp = pen[pts].astype(np.int64)
+print("  largest distance %d (zero penalties: %d), about %d launches: %.1f us per launch; unreachable pairs %d; "
+      "[i, j] - [j, i] = pen[j] - pen[i] everywhere: %s; never below the zero-penalty distance: %s"
+      % (m.max(), m0.max(), lv, 1e3 * ms / lv, int((m < 0).sum()), bool(np.array_equal(asym, pp[None, :] - pp[:, None])), bool((m >= m0).all())))
+if "--no-paths" not in sys.argv:
+    ii, jj = np.triu_indices(P, 1)
+    ((dist, lens, paths), (d_c, l_c, p_c)), (t, tc) = timed([lambda: api.chamfer_weighted_paths(grid, step, pen, pts[ii], pts[jj]),
+                                                              lambda: api.chamfer_paths(grid, step, pts[ii], pts[jj])], 3)
+    line("api.chamfer_weighted_paths %d pairs (two calls: distances and node counts, then paths; a field of %.0f MB per start, %.1f MB per source in all)"
+         % (len(ii), grid.n * 4 / 1e6, ((R + 1) * words * 8 + grid.n * 4) / 1e6), t)
+    line("api.chamfer_paths, the same pairs", tc)
+    d2 = grid.distance_field()
+    near = lambda ps: int(sum((d2[p] <= 1).sum() for p in ps))
+    print("  path nodes %d (mean %.0f, max %d) against %d of the chamfer paths; nodes next to the metal %d against %d; distances equal the matrix: %s; "
+          "paths that differ from the chamfer path of the pair: %d"
+          % (int(lens.sum()), lens.mean(), lens.max(), int(l_c.sum()), near(paths), near(p_c), bool(np.array_equal(dist, m[ii, jj])),
+             sum(not np.array_equal(u, v) for u, v in zip(paths, p_c))))

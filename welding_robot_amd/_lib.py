@@ -190,6 +190,9 @@ SYMBOLS = {
     "wa_grid_chamfer_fields": (C.c_int, [_V, _P, _P, _I, _P]),
     "wa_grid_chamfer_matrix": (C.c_int, [_V, _P, _P, _I, _P]),
     "wa_grid_chamfer_paths": (C.c_int, [_V, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "wa_grid_chamfer_weighted_fields": (C.c_int, [_V, _P, _P, _P, _I, _P]),
+    "wa_grid_chamfer_weighted_matrix": (C.c_int, [_V, _P, _P, _P, _I, _P]),
+    "wa_grid_chamfer_weighted_paths": (C.c_int, [_V, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "wa_grid_fit_trajectory": (C.c_int, [_V, _V, _I, _F, _I, _I64, _P, C.POINTER(_V), C.POINTER(_V), C.POINTER(FitSummary)]),
     "wa_traj_retime": (C.c_int, [_V, _V, C.POINTER(RetimeLimits), _P, C.c_double, _P, _P, _P, C.POINTER(_V), C.POINTER(RetimeSummary)]),
     "wa_gtsp_seam_tour": (C.c_int, [_V, _P, _I, C.POINTER(SeamParams), _P, _P, _P, _P, _P, _P, C.POINTER(SeamSummary)]),

@@ -257,6 +257,24 @@ class Grid:
         step = self._step(step)
         return self._search_rows(self.ctx.lib.wa_grid_chamfer_matrix, (_ptr(step),), ids, True)
 
+    def _pen(self, pen):
+        pen = np.ascontiguousarray(pen, np.uint8).reshape(-1)
+        assert pen.size == self.n, "a penalty array holds one byte per voxel"
+        return pen
+
+    def chamfer_weighted_fields(self, step, pen, ids):
+        """wa_grid_chamfer_weighted_fields: int32 [len(ids), n], the exact least sum of step[class - 1] + pen[voxel entered] over the moves
+        of chamfer_fields' graph (pen: uint8 [n], 0 .. WA_PEN_MAX on free voxels; the start is not paid for) from each source to every
+        voxel; WA_DIST_NONE (-1) where there is no path"""
+        step, pen = self._step(step), self._pen(pen)
+        return self._search_rows(self.ctx.lib.wa_grid_chamfer_weighted_fields, (_ptr(step), _ptr(pen)), ids, False)
+
+    def chamfer_weighted_matrix(self, step, pen, ids):
+        """wa_grid_chamfer_weighted_matrix: int32 [P, P], [i, j] = dist(point i, point j) (not symmetric: [i, j] - [j, i] = pen[j] -
+        pen[i]); WA_DIST_NONE (-1) where two points are not connected"""
+        step, pen = self._step(step), self._pen(pen)
+        return self._search_rows(self.ctx.lib.wa_grid_chamfer_weighted_matrix, (_ptr(step), _ptr(pen)), ids, True)
+
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.wa_grid_destroy(self.h)
@@ -324,6 +342,15 @@ def chamfer_paths(grid, step, starts, ends):
     is WA_DIST_NONE]), the paths in ranges of len ids (_paths_two_calls)"""
     step = grid._step(step)
     (dist, lens), paths = _paths_two_calls(grid, grid.ctx.lib.wa_grid_chamfer_paths, (_ptr(step),), starts, ends, 2, lambda dist, lens: lens)
+    return dist, lens, paths
+
+
+def chamfer_weighted_paths(grid, step, pen, starts, ends):
+    """wa_grid_chamfer_weighted_paths of a batch of pairs: (int32 dist, int32 node counts, [node-id array per pair, start first; None
+    where dist is WA_DIST_NONE]), the paths in ranges of len ids (_paths_two_calls)"""
+    step, pen = grid._step(step), grid._pen(pen)
+    (dist, lens), paths = _paths_two_calls(grid, grid.ctx.lib.wa_grid_chamfer_weighted_paths, (_ptr(step), _ptr(pen)), starts, ends, 2,
+                                           lambda dist, lens: lens)
     return dist, lens, paths
 
 
