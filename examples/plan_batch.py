@@ -166,12 +166,13 @@ def plan_diagonal(grid, point_ids, step, rank=0, world=1, shortcut=0):
     return cost, paths, len(mine)
 
 
-def plan_safe_diagonal(grid, point_ids, radius, step, gain, rank=0, world=1, shortcut=0):
+def plan_safe_diagonal(grid, point_ids, radius, step, gain, rank=0, world=1, shortcut=0, extra_pen=None):
     """--safe-paths R with --diagonal-paths A B C: the pair paths from the exact planner with diagonal moves AND clearance penalties
     (wa_grid_chamfer_weighted_paths): a move costs its step plus gain * (the number of bands 1^2 .. R^2 the voxel entered lies within),
     so the paths are short like the diagonal ones and keep off the metal like the safe ones where there is room.  The matrix of the
     points comes first and is held against the paths' distances.  A pair's cost for the seam order is a length in metres, as in
-    plan_exact.  Same return values as plan(); pair k belongs to rank k % world."""
+    plan_exact.  extra_pen (--torch-grid): penalties of Grid.torch_penalties, added and the sum clamped at WA_PEN_MAX.
+    Same return values as plan(); pair k belongs to rank k % world."""
     P = len(point_ids)
     pairs = [(i, j) for i in range(P) for j in range(i + 1, P)]
     mine = [k for k in range(len(pairs)) if k % world == rank]
@@ -179,6 +180,8 @@ def plan_safe_diagonal(grid, point_ids, radius, step, gain, rank=0, world=1, sho
     t0 = time.perf_counter()
     costs = grid.clearance_costs(bands)
     pen = (gain * np.maximum(costs.astype(np.int64) - 1, 0)).astype(np.uint8)   # (occupied voxels hold cost 0; their bytes are ignored)
+    if extra_pen is not None:
+        pen = np.minimum(pen.astype(np.int64) + extra_pen, 31).astype(np.uint8)
     t1 = time.perf_counter()
     matrix = grid.chamfer_weighted_matrix(step, pen, point_ids)
     t2 = time.perf_counter()
@@ -343,6 +346,26 @@ def seam_stage(ctx, cost, seed, n_starts):
     return info, r["order"].tolist(), r["dir"].tolist()
 
 
+def torch_tool_and_cone(metal, K):
+    """the torch of --torch and --torch-grid: a 300 mm body of 24 beads and K directions of a cone around +z"""
+    length16 = int(min(65536, round(16 * 0.3 / float(metal.precision))))
+    tool = api.torch_tool(np.rint(np.linspace(0, length16, 24)).astype(np.int64), np.full(24, 1))
+    return tool, api.torch_cone(K, 1.2), length16
+
+
+def torch_grid_report(base, count, paths, paths_without, shortcut):
+    """what --torch-grid costs and buys on the pair paths themselves: nodes, lengths and nodes without any open direction (count:
+    Grid.torch_reach of the grid planned on without the flag), beside the same planner's paths on that grid"""
+    def totals(table):
+        reach = [np.asarray(table[ij], np.int64) for ij in sorted(table) if len(table[ij])]
+        q = dict(pairs_reached=len(reach), nodes_total=int(sum(len(p) for p in reach)), nodes_no_dir=int(sum((count[p] == 0).sum() for p in reach)),
+                 length_total=float(api.shortcut_paths(base, reach, 1)[1].sum()))
+        if shortcut:
+            q.update(shortened_length_total=float(api.shortcut_paths(base, reach, shortcut)[1].sum()))
+        return q
+    return dict(totals(paths), without=totals(paths_without) if paths_without is not None else None)
+
+
 def torch_stage(ctx, metal, xyz, stops, K):
     """Torch axes along the trajectory's samples (wa_traj_tool_axes): one of K directions of a cone around +z per sample so that a
     300 mm torch body (24 beads) stays clear of the metal.  Legs: the travel moves between the tour's stops, cut at the sample nearest to
@@ -360,9 +383,7 @@ def torch_stage(ctx, metal, xyz, stops, K):
     gz, gy, gx = np.gradient(np.sqrt(d2))
     want = np.stack([gx.ravel()[ids], gy.ravel()[ids], gz.ravel()[ids]], 1).astype(np.float32)
     want[~np.isfinite(want).all(1)] = 0                          # (a grid without metal: no wish)
-    length16 = int(min(65536, round(16 * 0.3 / float(metal.precision))))
-    tool = api.torch_tool(np.rint(np.linspace(0, length16, 24)).astype(np.int64), np.full(24, 1))
-    dirs = api.torch_cone(K, 1.2)
+    tool, dirs, length16 = torch_tool_and_cone(metal, K)
     r = curve.torch_axes(metal, dirs, tool, w_near=4, w_want=1, w_turn=8, near_add=8, max_turn=-1, want=want, off=off, feas=False)
     info = dict(r["summary"], K=K, n_legs=len(off) - 1, directions_used=int(len(set(r["dir"].tolist()))), tool_length16=length16)
     if n > 1:
@@ -438,8 +459,23 @@ def main():
                     help="after --fit or --retime: the torch axis at every sample of the trajectory, one of K directions (1 .. 256) of a cone "
                          "around +z, so that the torch body clears the metal (wa_traj_tool_axes); prints the summary and the check of the "
                          "interpolated axes between samples")
+    ap.add_argument("--torch-grid", type=int, nargs="?", const=1, default=None, metavar="MIN_DIRS",
+                    help="with --torch K: plan on the torch-fit grid (wa_grid_tool_fit), whose free voxels leave the torch body at least MIN_DIRS "
+                         "(default 1) of the K directions; around every weld point the voxels within --torch-keep-r2 (squared voxels) stay as "
+                         "they are.  With --safe-paths and --diagonal-paths the penalties of wa_grid_tool_penalties (thresholds K/8, K/4, K/2, "
+                         "each worth --safe-gain) are added to the clearance penalties, the sum clamped at 31.  --torch then also runs on the "
+                         "plain trajectory (no --fit / --retime needed).  MIN_DIRS 0 is the comparison run: the planning grid and the penalties "
+                         "are left as they are, everything else is reported alike")
+    ap.add_argument("--torch-keep-r2", type=int, default=16, metavar="R2",
+                    help="--torch-grid: the squared radius in voxels of the bubble around every weld point inside which the grid is kept (default 16)")
     args = ap.parse_args()
-    if args.torch is not None and args.fit is None and not args.retime:
+    if args.torch_grid is not None and args.torch is None:
+        ap.error("--torch-grid needs the directions of --torch K")
+    if args.torch_grid is not None and not 0 <= args.torch_grid <= (args.torch or 0):
+        ap.error("--torch-grid takes 0 .. K directions")
+    if args.torch_keep_r2 < 0:
+        ap.error("--torch-keep-r2 is at least 0")
+    if args.torch is not None and args.fit is None and not args.retime and args.torch_grid is None:
         ap.error("--torch works on the samples of --fit or --retime")
     if args.torch is not None and not 1 <= args.torch <= 256:
         ap.error("--torch takes 1 .. 256 directions")
@@ -485,16 +521,44 @@ def main():
     if args.clearance is not None:
         # plan with a safety margin: every voxel nearer the metal than the radius becomes an obstacle, except around the weld points
         grid = metal.inflate(metal.clearance_radius(args.clearance), pts)
+    torch_grid, extra_pen = None, None
+    if args.torch_grid is not None:
+        # plan where the torch body fits: the bead rule of --torch for every voxel, before any path is planned
+        t_tg = time.perf_counter()
+        base = grid
+        tool, dirs, _ = torch_tool_and_cone(metal, args.torch)
+        _, count, reach_summary = base.torch_reach(dirs, tool, masks=False)
+        torch_grid = dict(min_dirs=args.torch_grid, keep_r2=args.torch_keep_r2, reach=reach_summary, free_voxels=base.n_free)
+        if args.torch_grid > 0:
+            grid = base.torch_fit(dirs, tool, args.torch_grid, pts, args.torch_keep_r2)
+            torch_grid.update(free_voxels_fit=grid.n_free)
+            if both:
+                K, rep = args.torch, max(1, min(args.safe_gain, 10))
+                thr = [t for t in (max(1, K // 8), max(1, K // 4), max(1, K // 2)) for _ in range(rep)]
+                extra_pen = base.torch_penalties(dirs, tool, thr).astype(np.int64)
+                torch_grid.update(penalty_thresholds=thr)
+        torch_grid.update(t_grid_s=time.perf_counter() - t_tg)
     hop_matrix, unreachable = None, []
     if args.geodesic:
         t_geo = time.perf_counter()
         hop_matrix = grid.geodesic_matrix(pts)
         t_geo = time.perf_counter() - t_geo
         unreachable = [(i, j) for i in range(args.points) for j in range(i + 1, args.points) if hop_matrix[i, j] == api.WA_HOPS_NONE]
+    paths_without = None
+    if torch_grid is not None and args.torch_grid > 0 and comm is None:
+        # the same exact planner on the grid as it was, for the cost of the detour (the colony is not run twice)
+        if both:
+            paths_without = plan_safe_diagonal(base, pts, args.safe_paths, args.diagonal_paths, args.safe_gain)[1]
+        elif args.safe_paths:
+            paths_without = plan_safe(base, pts, args.safe_paths)[1]
+        elif args.diagonal_paths is not None:
+            paths_without = plan_diagonal(base, pts, args.diagonal_paths)[1]
+        elif args.exact_paths:
+            paths_without = plan_exact(base, pts)[1]
     t0 = time.perf_counter()
     if both:
         cost, paths, n_mine = plan_safe_diagonal(grid, pts, args.safe_paths, args.diagonal_paths, args.safe_gain, rank, world,
-                                                 shortcut=args.max_span if args.shortcut else 0)
+                                                 shortcut=args.max_span if args.shortcut else 0, extra_pen=extra_pen)
     elif args.safe_paths:
         cost, paths, n_mine = plan_safe(grid, pts, args.safe_paths, rank, world, shortcut=args.max_span if args.shortcut else 0)
     elif args.diagonal_paths is not None:
@@ -530,6 +594,8 @@ def main():
                pairs_this_rank=n_mine, t_pairs_s=t_pairs, all_reached=bool(finite))
     if args.exact_paths:
         out.update(exact_paths=True)
+    if torch_grid is not None and rank == 0:
+        out.update(torch_grid=dict(torch_grid, paths=torch_grid_report(base, count, paths, paths_without, args.max_span if args.shortcut else 0)))
     if rank == 0 and args.geodesic:
         # every search against the optimum: a lattice path of len nodes has len - 1 steps, never fewer than the hop count
         gone = set(unreachable)

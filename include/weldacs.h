@@ -885,6 +885,45 @@ int wa_traj_tool_axes(const wa_grid *g, const wa_traj *t, const float *dirs, int
 int wa_traj_tool_check(const wa_grid *g, const wa_traj *t, const float *axes, const wa_tool_beads *tool, int32_t near_add,
                         uint8_t *blocked_out, uint8_t *near_out, wa_tool_summary *sum);
 
+/* ---- torch-fit planning grids: rule 2 above for EVERY voxel of a grid, so that a planner can be told where the torch fits before it
+ *      plans (wa_traj_tool_axes tells it afterwards).  The rules continue the numbering above; directions, q, the offsets
+ *      o_c = floor((q_c * dist16[j] + 2^17) / 2^18) and wa_tool_beads are those of rules 1 and 2, near is not used.
+ *      K = 1 .. WA_TORCH_MAX_DIRS directions, W = ceil(K / 64), n = nx * ny * nz, v = (x, y, z) a voxel of g, o(k, j) the offset of
+ *      bead j under direction k.
+ * 10. blocked(v, k) iff some bead j has v + o(k, j) inside the grid and d2[v + o(k, j)] <= r2[j].  A bead outside the grid passes; on a
+ *     grid without obstacles nothing is blocked.  open(v, k) = v is free in g AND not blocked(v, k): an occupied voxel has no open
+ *     direction, whatever the beads say.
+ * 11. count[v] = the number of open directions, 0 .. K (uint16, raster order).  mask is word-plane-major: bit (k & 63) of
+ *     mask[(k >> 6) * n + v] is open(v, k); the unused high bits of the last plane are 0.
+ * 12. wa_reach_summary: n_free = free voxels of g; n_no_dir = free voxels with count 0; n_all_dirs = free voxels with count K;
+ *     n_blocked_pairs = the sum over free voxels of K - count.
+ * 13. wa_grid_tool_reach copies the masks (W * n uint64) and the counts (n uint16) to the host; either may be NULL, sum may not.  The
+ *     mask planes are a block of the context's arena, taken only when mask_out is given.
+ * 14. wa_grid_tool_fit builds a new planning grid like wa_grid_inflate (same dims, axis tables, precision and wall; its own buffers;
+ *     n_free recounted; destroyed with wa_grid_destroy): v is free in it iff v is free in g AND count[v] >= min_dirs (1 .. K) -- except
+ *     inside keep bubbles: for each keep id k (a free voxel of g), every voxel v with |v - k|^2 <= keep_r2 (integer index units,
+ *     0 .. 2^30) keeps the state it has in g.  The counts never leave the device between the count and the new occupancy.  sum (of g,
+ *     rule 12) may be NULL.  *out is written on success only.
+ * 15. wa_grid_tool_penalties writes a penalty array for wa_grid_chamfer_weighted_*: n bytes on the host in raster order, 0 on occupied
+ *     voxels, on free voxels the number of t with count[v] < thr[t].  0 <= n_thr <= WA_PEN_MAX (thr may be NULL when n_thr is 0),
+ *     every threshold 0 .. 65535, in any order, repeats allowed.
+ * 16. Errors.  WA_ERR_ARG, before anything is written: a NULL required pointer (g, dirs, tool, sum / out / pen_out, keep_ids with
+ *     n_keep > 0, thr with n_thr > 0); K, n_beads, dist16, r2, min_dirs, n_thr, a threshold or keep_r2 out of range; a direction that is
+ *     not finite or has zero length; a keep id outside the grid or on an occupied voxel; a negative n_keep.  WA_ERR_ALLOC when the
+ *     device blocks do not fit.
+ * Same bytes on every call; everything runs on the context's stream; g is not modified; the distance field is built on the first use,
+ * as by wa_grid_inflate.  EVERY call recomputes the counts: nothing is cached with the grid, so a caller who wants the fit grid and
+ * the penalties of one tool pays for the count twice. */
+typedef struct {
+    int64_t n_free, n_no_dir, n_all_dirs, n_blocked_pairs;
+} wa_reach_summary;
+int wa_grid_tool_reach(const wa_grid *g, const float *dirs, int32_t K, const wa_tool_beads *tool, uint64_t *mask_out, uint16_t *count_out,
+                       wa_reach_summary *sum);
+int wa_grid_tool_fit(const wa_grid *g, const float *dirs, int32_t K, const wa_tool_beads *tool, int32_t min_dirs, const int64_t *keep_ids,
+                     int32_t n_keep, int32_t keep_r2, wa_grid **out, wa_reach_summary *sum);
+int wa_grid_tool_penalties(const wa_grid *g, const float *dirs, int32_t K, const wa_tool_beads *tool, const int32_t *thr, int32_t n_thr,
+                           uint8_t *pen_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,12 @@ class ToolSummary(C.Structure):
                 ("n_over_turn", C.c_int64), ("max_turn_taken", C.c_int64), ("cost", C.c_int64)]
 
 
+class ReachSummary(C.Structure):
+    _fields_ = [("n_free", C.c_int64), ("n_no_dir", C.c_int64), ("n_all_dirs", C.c_int64), ("n_blocked_pairs", C.c_int64)]
+
+
+WA_PEN_MAX = 31
+
 # every symbol include/weldacs.h declares: name -> (restype, argtypes)
 _V, _I, _I64, _F, _P = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_void_p
 SYMBOLS = {
@@ -200,6 +206,9 @@ SYMBOLS = {
     "wa_traj_tool_axes": (C.c_int, [_V, _V, _P, _I, C.POINTER(ToolBeads), C.POINTER(ToolWeights), _P, _P, _I, _P, _P, _P, _P, _P,
                                     C.POINTER(ToolSummary)]),
     "wa_traj_tool_check": (C.c_int, [_V, _V, _P, C.POINTER(ToolBeads), _I, _P, _P, C.POINTER(ToolSummary)]),
+    "wa_grid_tool_reach": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _P, _P, C.POINTER(ReachSummary)]),
+    "wa_grid_tool_fit": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, _P, _I, _I, C.POINTER(_V), C.POINTER(ReachSummary)]),
+    "wa_grid_tool_penalties": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _P, _I, _P]),
 }
 
 _libs = {}

@@ -186,6 +186,44 @@ class Grid:
         self.ctx.check(self.ctx.lib.wa_grid_inflate(self.h, C.c_float(radius), _ptr(keep) if len(keep) else None, len(keep), C.byref(h)))
         return Grid(self.ctx, h, self.bbox)
 
+    def _torch_args(self, dirs, tool):
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        return dirs, len(dirs), tool if isinstance(tool, L.ToolBeads) else torch_tool(*tool)
+
+    def torch_reach(self, dirs, tool, masks=True):
+        """wa_grid_tool_reach: for every voxel, which of the K directions `dirs` (K x 3, tip -> body) keep the beads of `tool` clear of
+        this grid's metal when the tip is on that voxel.  Returns (mask uint64[W, n] or None with masks=False -- bit k & 63 of
+        mask[k >> 6, v] is set where direction k is open at v --, count uint16[n], summary dict).  Occupied voxels have no open direction."""
+        dirs, K, tool = self._torch_args(dirs, tool)
+        mask = np.empty(((K + 63) // 64, self.n), np.uint64) if masks else None
+        count = np.empty(self.n, np.uint16)
+        s = L.ReachSummary()
+        self.ctx.check(self.ctx.lib.wa_grid_tool_reach(self.h, _ptr(dirs), K, C.byref(tool), _ptr(mask), _ptr(count), C.byref(s)))
+        return mask, count, {k: int(getattr(s, k)) for k, _ in L.ReachSummary._fields_}
+
+    def torch_fit(self, dirs, tool, min_dirs=1, keep_ids=None, keep_r2=0):
+        """wa_grid_tool_fit: a planning grid whose free voxels are this grid's free voxels with at least `min_dirs` open directions,
+        except within sqrt(keep_r2) voxels of each keep id (weld points resolved on this grid), where this grid's state is kept.  The
+        summary of torch_reach is left in the result's `reach_summary`."""
+        dirs, K, tool = self._torch_args(dirs, tool)
+        keep = np.ascontiguousarray(keep_ids if keep_ids is not None else [], np.int64).reshape(-1)
+        h, s = C.c_void_p(), L.ReachSummary()
+        self.ctx.check(self.ctx.lib.wa_grid_tool_fit(self.h, _ptr(dirs), K, C.byref(tool), min_dirs, _ptr(keep) if len(keep) else None,
+                                                     len(keep), keep_r2, C.byref(h), C.byref(s)))
+        g = Grid(self.ctx, h, self.bbox)
+        g.reach_summary = {k: int(getattr(s, k)) for k, _ in L.ReachSummary._fields_}
+        return g
+
+    def torch_penalties(self, dirs, tool, thr):
+        """wa_grid_tool_penalties: uint8 [n] for chamfer_weighted_*: 0 on occupied voxels, else the number of thresholds in `thr` (at most
+        WA_PEN_MAX of them, each 0 .. 65535) that the voxel's count of open directions stays below"""
+        dirs, K, tool = self._torch_args(dirs, tool)
+        thr = np.ascontiguousarray(thr, np.int32).reshape(-1)
+        pen = np.empty(self.n, np.uint8)
+        self.ctx.check(self.ctx.lib.wa_grid_tool_penalties(self.h, _ptr(dirs), K, C.byref(tool), _ptr(thr) if len(thr) else None, len(thr),
+                                                           _ptr(pen)))
+        return pen
+
     def clearance_radius(self, metres):
         """a clearance in metres as a radius in voxels (exact up to the hi-side seam of the wall, see include/weldacs.h)"""
         return float(metres) / float(self.precision)

@@ -38,6 +38,7 @@
 #include "retime_kernels.hpp"
 #include "seamtour_kernels.hpp"
 #include "torch_kernels.hpp"
+#include "reach_kernels.hpp"
 #include "stl_text.hpp"
 #include "acs_plan.hpp"
 
@@ -840,5 +841,6 @@ void *wa_ctx_stream(wa_ctx *c) { return c ? (void *)c->stream : nullptr; }
 #include "host_retime.inc"
 #include "host_seamtour.inc"
 #include "host_torch.inc"
+#include "host_reach.inc"
 
 }  // extern "C"
