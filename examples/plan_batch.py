@@ -110,6 +110,30 @@ def plan_exact(grid, point_ids, rank=0, world=1, shortcut=0):
     return cost, paths, len(mine)
 
 
+def plan_pose(grid, point_ids, dirs, tool, max_turn, rank=0, world=1, shortcut=0):
+    """--pose-paths MAX_TURN: the pair paths from the exact search over (voxel, torch direction) (wa_grid_pose_paths): every node has a
+    direction in which the torch body clears the metal, and from node to node the torch turns by at most MAX_TURN.  Costs and return
+    values as plan_exact; the directions per node are left in plan_pose.last_dirs.  A shortened path (shortcut) leaves the planned
+    voxels, so the guarantee holds for the lattice path only."""
+    P = len(point_ids)
+    pairs = [(i, j) for i in range(P) for j in range(i + 1, P)]
+    mine = [k for k in range(len(pairs)) if k % world == rank]
+    hops, ids_all, ks_all = grid.pose_paths(dirs, tool, max_turn, [point_ids[pairs[k][0]] for k in mine], [point_ids[pairs[k][1]] for k in mine])
+    ids_all = [np.zeros(0, np.int64) if p is None else p for p in ids_all]
+    wps, lengths = api.shortcut_paths(grid, ids_all, shortcut or 1)
+    cost = np.zeros((P, P), np.float64)
+    paths = {}
+    plan.last_slots, plan.last_create_s, plan.last_batch_s, plan.last_shortcut, plan_pose.last_dirs = 0, 0.0, [], {}, {}
+    for q, k in enumerate(mine):
+        i, j = pairs[k]
+        cost[i, j] = cost[j, i] = lengths[q] if hops[q] >= 0 else np.inf
+        paths[(i, j)] = ids_all[q]
+        plan_pose.last_dirs[(i, j)] = ks_all[q]
+        if shortcut:
+            plan.last_shortcut[(i, j)] = wps[q]
+    return cost, paths, len(mine)
+
+
 def plan_safe(grid, point_ids, radius, rank=0, world=1, shortcut=0):
     """--safe-paths R: the pair paths that minimise the sum of clearance costs (wa_grid_clearance_costs with bands at 1^2 .. R^2, then
     wa_grid_weighted_paths) instead of the number of steps: they keep away from the metal where there is room and squeeze through where
@@ -366,7 +390,7 @@ def torch_grid_report(base, count, paths, paths_without, shortcut):
     return dict(totals(paths), without=totals(paths_without) if paths_without is not None else None)
 
 
-def torch_stage(ctx, metal, xyz, stops, K):
+def torch_stage(ctx, metal, xyz, stops, K, max_turn=-1):
     """Torch axes along the trajectory's samples (wa_traj_tool_axes): one of K directions of a cone around +z per sample so that a
     300 mm torch body (24 beads) stays clear of the metal.  Legs: the travel moves between the tour's stops, cut at the sample nearest to
     each stop.  Wish: the torch points down the gradient of the distance field (at the nearest metal), so the body -- a direction runs
@@ -384,7 +408,7 @@ def torch_stage(ctx, metal, xyz, stops, K):
     want = np.stack([gx.ravel()[ids], gy.ravel()[ids], gz.ravel()[ids]], 1).astype(np.float32)
     want[~np.isfinite(want).all(1)] = 0                          # (a grid without metal: no wish)
     tool, dirs, length16 = torch_tool_and_cone(metal, K)
-    r = curve.torch_axes(metal, dirs, tool, w_near=4, w_want=1, w_turn=8, near_add=8, max_turn=-1, want=want, off=off, feas=False)
+    r = curve.torch_axes(metal, dirs, tool, w_near=4, w_want=1, w_turn=8, near_add=8, max_turn=max_turn, want=want, off=off, feas=False)
     info = dict(r["summary"], K=K, n_legs=len(off) - 1, directions_used=int(len(set(r["dir"].tolist()))), tool_length16=length16)
     if n > 1:
         a = dirs[r["dir"]].astype(np.float64)
@@ -466,6 +490,12 @@ def main():
                          "each worth --safe-gain) are added to the clearance penalties, the sum clamped at 31.  --torch then also runs on the "
                          "plain trajectory (no --fit / --retime needed).  MIN_DIRS 0 is the comparison run: the planning grid and the penalties "
                          "are left as they are, everything else is reported alike")
+    ap.add_argument("--pose-paths", type=int, default=None, metavar="MAX_TURN",
+                    help="with --torch K: take the pair paths from the exact search over (voxel, torch direction) (wa_grid_pose_paths): every "
+                         "node of a path has one of the K directions open, and from node to node the torch turns by at most MAX_TURN (the "
+                         "measure U of wa_traj_tool_axes, 0 .. 3145728; -1: no limit).  Pairs without such a path are reported and left out, "
+                         "as with --geodesic; --torch then runs on the finished trajectory with the same limit and the line carries its "
+                         "n_no_dir and n_over_turn.  --shortcut leaves the planned voxels and so drops the guarantee")
     ap.add_argument("--torch-keep-r2", type=int, default=16, metavar="R2",
                     help="--torch-grid: the squared radius in voxels of the bubble around every weld point inside which the grid is kept (default 16)")
     args = ap.parse_args()
@@ -475,7 +505,14 @@ def main():
         ap.error("--torch-grid takes 0 .. K directions")
     if args.torch_keep_r2 < 0:
         ap.error("--torch-keep-r2 is at least 0")
-    if args.torch is not None and args.fit is None and not args.retime and args.torch_grid is None:
+    if args.pose_paths is not None:
+        if args.torch is None:
+            ap.error("--pose-paths needs the directions of --torch K")
+        if not -1 <= args.pose_paths <= 3 << 20:
+            ap.error("--pose-paths takes -1 or 0 .. 3145728")
+        if args.exact_paths or args.safe_paths or args.diagonal_paths is not None or args.geodesic:
+            ap.error("--pose-paths is a pair planner of its own: not with --exact-paths, --safe-paths, --diagonal-paths or --geodesic")
+    if args.torch is not None and args.fit is None and not args.retime and args.torch_grid is None and args.pose_paths is None:
         ap.error("--torch works on the samples of --fit or --retime")
     if args.torch is not None and not 1 <= args.torch <= 256:
         ap.error("--torch takes 1 .. 256 directions")
@@ -556,7 +593,10 @@ def main():
         elif args.exact_paths:
             paths_without = plan_exact(base, pts)[1]
     t0 = time.perf_counter()
-    if both:
+    if args.pose_paths is not None:
+        pose_tool, pose_dirs, _ = torch_tool_and_cone(metal, args.torch)
+        cost, paths, n_mine = plan_pose(grid, pts, pose_dirs, pose_tool, args.pose_paths, rank, world, shortcut=args.max_span if args.shortcut else 0)
+    elif both:
         cost, paths, n_mine = plan_safe_diagonal(grid, pts, args.safe_paths, args.diagonal_paths, args.safe_gain, rank, world,
                                                  shortcut=args.max_span if args.shortcut else 0, extra_pen=extra_pen)
     elif args.safe_paths:
@@ -594,6 +634,10 @@ def main():
                pairs_this_rank=n_mine, t_pairs_s=t_pairs, all_reached=bool(finite))
     if args.exact_paths:
         out.update(exact_paths=True)
+    if args.pose_paths is not None and rank == 0:
+        gone = [[i, j] for i in range(args.points) for j in range(i + 1, args.points) if not np.isfinite(cost[i, j])]
+        out.update(pose_paths=dict(max_turn=args.pose_paths, K=args.torch, unreachable_pairs=gone, reachable_pairs=out["pairs"] - len(gone),
+                                   nodes_total=int(sum(len(p) for p in paths.values()))))
     if torch_grid is not None and rank == 0:
         out.update(torch_grid=dict(torch_grid, paths=torch_grid_report(base, count, paths, paths_without, args.max_span if args.shortcut else 0)))
     if rank == 0 and args.geodesic:
@@ -670,8 +714,11 @@ def main():
             cx, cy, cz = metal.coords()
             first = np.asarray([(seg[-1] if r else seg[0]) for seg, r in zip(segs, rev)] + [segs[-1][0] if rev[-1] else segs[-1][-1]], np.int64)
             stops = np.stack([cx[first % metal.nx], cy[(first // metal.nx) % metal.ny], cz[first // (metal.nx * metal.ny)]], 1)
-            out.update(torch=torch_stage(ctx, metal, np.ascontiguousarray(traj[ok.astype(bool)], np.float32), stops, args.torch),
+            out.update(torch=torch_stage(ctx, metal, np.ascontiguousarray(traj[ok.astype(bool)], np.float32), stops, args.torch,
+                                         args.pose_paths if args.pose_paths is not None else -1),
                        t_torch_s=time.perf_counter() - t4)
+            if args.pose_paths is not None:
+                out.update(n_no_dir=out["torch"]["n_no_dir"], n_over_turn=out["torch"]["n_over_turn"])
         if both:
             q = safe_diagonal_report(grid, metal, pts, paths, args.max_span if args.shortcut else 0)
             if args.shortcut:

@@ -924,6 +924,45 @@ int wa_grid_tool_fit(const wa_grid *g, const float *dirs, int32_t K, const wa_to
 int wa_grid_tool_penalties(const wa_grid *g, const float *dirs, int32_t K, const wa_tool_beads *tool, const int32_t *thr, int32_t n_thr,
                            uint8_t *pen_out);
 
+/* ---- exact pose paths: shortest lattice paths over the states (voxel, direction) with a turn limit, so that a planner knows BEFORE it
+ *      plans whether a turn-limited SEQUENCE of directions exists along a path (a free voxel of wa_grid_tool_fit only promises one open
+ *      direction per voxel).  The rules continue the numbering above; directions, q, U(a, b), wa_tool_beads, open(v, k),
+ *      K = 1 .. WA_TORCH_MAX_DIRS and W = ceil(K / 64) are those of rules 1, 2, 10 and 11.  Integers only.
+ * 17. States are the pairs (v, k) with open(v, k).  adj(k, k') holds iff max_turn < 0 or U(q_k, q_k') <= max_turn; it is symmetric and
+ *     holds for k' = k.  max_turn is -1 or 0 .. 3 * 2^20.
+ * 18. One step goes from (v, k) to (v', k'): v' is a 6-neighbour of v inside the grid, adj(k, k') and open(v', k') hold.  There is no
+ *     turn in place: a path is a lattice path of distinct consecutive voxels with one direction index per node.
+ * 19. The seed of a source s with pin p: every open direction of s when p = -1, otherwise the one state (s, p) if it is open.  An
+ *     empty seed is not an error: nothing is reached, the source itself included.
+ * 20. level(s; v, k) = the breadth-first level of the state from the seed, WA_HOPS_NONE (-1) where there is none.  hops(s; v) = the
+ *     minimum over k of level(s; v, k); hops(s; t, pin) restricts that minimum to the pinned direction (pin = -1: no restriction).
+ * 21. The path of a pair is defined, not only its length D = hops(start; end, end pin).  Its end state is the lowest k allowed by the end
+ *     pin with level D.  Walking back from (p, k) at level L > 0, the predecessor voxel is the first neighbour in the order -x, +x, -y,
+ *     +y, -z, +z that is inside the grid and has some k' with level L - 1 and adj(k', k); the predecessor direction is the lowest such k'
+ *     of that voxel.  The path is returned start first: D + 1 voxel ids and D + 1 direction indices.
+ * 22. wa_grid_pose_fields: hops_out[s * n + v] = hops(s; v); state_out (may be NULL) [(s * K + k) * n + v] = level(s; v, k).
+ *     wa_grid_pose_matrix: hops_out[i * n_pts + j] = hops from point i, seeded with its pin, to point j restricted to ITS pin; with the same
+ *     pins on both sides the matrix is symmetric.  wa_grid_pose_paths follows wa_grid_geodesic_paths: pair p owns the range
+ *     [off[p], off[p + 1]) of ids_out AND of dir_out (int32); hops_out[p] = D or WA_HOPS_NONE, len_out[p] (may be NULL) = D + 1 (0 for no
+ *     path); the counts reach the caller for every pair first, WA_ERR_CAPACITY is reported once every pair has its counts, only a pair's
+ *     own D + 1 entries are written, and an unreachable pair is no error.  The pin arrays may be NULL (all -1).
+ *     With max_turn < 0 and no pins, or with K = 1, hops equals wa_grid_geodesic_* on wa_grid_tool_fit(min_dirs = 1, no keep ids); on a
+ *     grid without obstacles it equals wa_grid_geodesic_* on g.
+ * 23. Errors.  WA_ERR_ARG, before anything is written: the errors of rule 16 for g, dirs, K and the tool; a NULL id, offset or output
+ *     array other than those named optional; a negative count; decreasing offsets; max_turn out of range; a pin outside -1 .. K - 1;
+ *     an id outside the grid or on an occupied voxel.  WA_ERR_ALLOC when the buffers of one source do not fit, WA_ERR_STATE past
+ *     K * n_free + 1 levels.
+ * Same bytes on every call; everything runs on the context's stream; g is not modified.  The masks are recomputed by every call, in a
+ * block of the context's arena (rule 16).  A source costs 3 * W * 8 * n bytes of bitmaps and 4 * n bytes of hops, and 4 * K * n bytes
+ * more where states are kept (_paths always, _fields with state_out); sources are searched in chunks as for wa_grid_geodesic_*. */
+int wa_grid_pose_fields(const wa_grid *g, const float *dirs, int32_t K, const wa_tool_beads *tool, int32_t max_turn, const int64_t *src_ids,
+                        const int32_t *src_pin, int32_t n_src, int32_t *hops_out, int32_t *state_out);
+int wa_grid_pose_matrix(const wa_grid *g, const float *dirs, int32_t K, const wa_tool_beads *tool, int32_t max_turn, const int64_t *point_ids,
+                        const int32_t *point_pin, int32_t n_pts, int32_t *hops_out);
+int wa_grid_pose_paths(const wa_grid *g, const float *dirs, int32_t K, const wa_tool_beads *tool, int32_t max_turn, const int64_t *start_ids,
+                       const int64_t *end_ids, const int32_t *pin_start, const int32_t *pin_end, int32_t n_pairs, const int64_t *off,
+                       int64_t *ids_out, int32_t *dir_out, int32_t *hops_out, int32_t *len_out);
+
 #ifdef __cplusplus
 }
 #endif

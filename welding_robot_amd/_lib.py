@@ -209,6 +209,9 @@ SYMBOLS = {
     "wa_grid_tool_reach": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _P, _P, C.POINTER(ReachSummary)]),
     "wa_grid_tool_fit": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, _P, _I, _I, C.POINTER(_V), C.POINTER(ReachSummary)]),
     "wa_grid_tool_penalties": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _P, _I, _P]),
+    "wa_grid_pose_fields": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, _P, _P, _I, _P, _P]),
+    "wa_grid_pose_matrix": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, _P, _P, _I, _P]),
+    "wa_grid_pose_paths": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
 }
 
 _libs = {}

@@ -224,6 +224,75 @@ class Grid:
                                                            _ptr(pen)))
         return pen
 
+    @staticmethod
+    def _pins(pins, count, what):
+        """a pin array for the pose calls: None stays None (all -1)"""
+        if pins is None:
+            return None
+        pins = np.ascontiguousarray(pins, np.int32).reshape(-1)
+        assert len(pins) == count, "one pin per " + what
+        return pins
+
+    def pose_fields(self, dirs, tool, max_turn, ids, pins=None, states=False):
+        """wa_grid_pose_fields: exact hop counts over the states (voxel, direction) -- a step moves to a 6-neighbour voxel and turns the
+        torch by at most `max_turn` (the measure U of torch_axes; -1: no limit), and every state on the way has the direction open.
+        `pins`: per source a direction index the search starts with, or -1 for every open one.  Returns int32 hops [len(ids), n], the
+        least level over the directions (WA_HOPS_NONE (-1) where no state is reached), and with states=True also int32
+        [len(ids), K, n], the level of every state."""
+        dirs, K, tool = self._torch_args(dirs, tool)
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        pins = self._pins(pins, len(ids), "source")
+        hops = np.empty((len(ids), self.n), np.int32)
+        state = np.empty((len(ids), K, self.n), np.int32) if states else None
+        pad = np.zeros(1, np.int32)
+        self.ctx.check(self.ctx.lib.wa_grid_pose_fields(self.h, _ptr(dirs), K, C.byref(tool), int(max_turn), _ptr(ids if len(ids) else np.zeros(1, np.int64)),
+                                                        _ptr(pins) if pins is not None and len(ids) else None, len(ids),
+                                                        _ptr(hops if hops.size else pad), (_ptr(state if state.size else pad)) if states else None))
+        return (hops, state) if states else hops
+
+    def pose_matrix(self, dirs, tool, max_turn, ids, pins=None):
+        """wa_grid_pose_matrix: int32 [P, P] of those hop counts between the points; a point's pin restricts both the directions it starts
+        with as a source and the direction it must be reached with as a target (symmetric; WA_HOPS_NONE (-1) where two points are not
+        connected, on the diagonal too when the point has no open direction its pin allows)"""
+        dirs, K, tool = self._torch_args(dirs, tool)
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        pins = self._pins(pins, len(ids), "point")
+        out = np.empty((len(ids), len(ids)), np.int32)
+        self.ctx.check(self.ctx.lib.wa_grid_pose_matrix(self.h, _ptr(dirs), K, C.byref(tool), int(max_turn), _ptr(ids if len(ids) else np.zeros(1, np.int64)),
+                                                        _ptr(pins) if pins is not None and len(ids) else None, len(ids),
+                                                        _ptr(out if out.size else np.zeros(1, np.int32))))
+        return out
+
+    def pose_paths(self, dirs, tool, max_turn, starts, ends, pin_start=None, pin_end=None):
+        """wa_grid_pose_paths of a batch of pairs: (int32 hops, [node-id array per pair, start first], [int32 direction index per node]);
+        None in both lists where hops is WA_HOPS_NONE.  Two calls: the first, with empty ranges, returns the counts (WA_ERR_CAPACITY is
+        its expected status when any pair is reachable), the second writes the paths into ranges of hops + 1."""
+        dirs, K, tool = self._torch_args(dirs, tool)
+        starts = np.ascontiguousarray(starts, np.int64).reshape(-1)
+        ends = np.ascontiguousarray(ends, np.int64).reshape(-1)
+        assert len(starts) == len(ends)
+        n = len(starts)
+        ps, pe = self._pins(pin_start, n, "pair"), self._pins(pin_end, n, "pair")
+        hops, lens = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        off = np.zeros(n + 1, np.int64)
+        pad = np.zeros(1, np.int64)
+
+        def call(ids, ks):
+            return self.ctx.lib.wa_grid_pose_paths(self.h, _ptr(dirs), K, C.byref(tool), int(max_turn), _ptr(starts if n else pad),
+                                                   _ptr(ends if n else pad), _ptr(ps) if ps is not None and n else None,
+                                                   _ptr(pe) if pe is not None and n else None, n, _ptr(off), _ptr(ids), _ptr(ks), _ptr(hops),
+                                                   _ptr(lens))
+        rc = call(pad, np.zeros(1, np.int32))
+        if rc not in (0, 7):
+            self.ctx.check(rc)
+        off[1:] = np.cumsum(np.maximum(hops[:n].astype(np.int64) + 1, 0))
+        ids, ks = np.empty(max(int(off[-1]), 1), np.int64), np.empty(max(int(off[-1]), 1), np.int32)
+        if rc == 7:
+            self.ctx.check(call(ids, ks))
+        hops = hops[:n]
+        return (hops, [ids[off[k]:off[k + 1]].copy() if hops[k] >= 0 else None for k in range(n)],
+                [ks[off[k]:off[k + 1]].copy() if hops[k] >= 0 else None for k in range(n)])
+
     def clearance_radius(self, metres):
         """a clearance in metres as a radius in voxels (exact up to the hi-side seam of the wall, see include/weldacs.h)"""
         return float(metres) / float(self.precision)

@@ -25,6 +25,7 @@ static SearchKind chm_kind(const wa_grid *g, const WaGeoDims &d, const WaChmStep
     SearchKind k;
     k.fn = fn;
     k.frontiers = R; k.zeroed = R; k.window = cs.M;
+    k.words = d.nw; k.ints = d.n;
     // the largest distance is at most M * (n_free - 1) <= 2^31 - 1 (chm_steps); R more launches see the ring empty
     k.first = 1; k.bound = std::min<int64_t>((int64_t)cs.M * (g->n_free - 1) + R + 1, (int64_t)INT32_MAX - WA_GEO_BLOCK);
     hipStream_t st = g->ctx->stream;

@@ -51,6 +51,7 @@ static SearchKind cw_kind(const wa_grid *g, const WaGeoDims &d, const WaChmStep 
     SearchKind k;
     k.fn = fn;
     k.frontiers = R; k.zeroed = R; k.window = st.M + st.P;
+    k.words = d.nw; k.ints = d.n;
     // the largest distance is at most (M + P) * (n_free - 1) <= 2^31 - 1 (cw_pens); R more launches see the ring empty
     k.first = 1; k.bound = std::min<int64_t>((int64_t)(st.M + st.P) * (g->n_free - 1) + R + 1, (int64_t)INT32_MAX - WA_GEO_BLOCK);
     hipStream_t stream = g->ctx->stream;

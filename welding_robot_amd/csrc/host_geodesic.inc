@@ -81,18 +81,20 @@ struct SearchChunk {
 
 // What tells one search from another.  The driver runs: seed(c, ns), then launches level(c, ns, L, d_tgt, n_tgt) for L = first, first + 1, ...
 // in blocks of WA_GEO_BLOCK, and goes on while a source has !stop[s] && last[s] >= L - window for the next L (what the level kernels ask
-// themselves).  Both functions enqueue one kernel on the context's stream.
+// themselves).  Both functions enqueue one kernel on the context's stream.  The driver does not look into the sources: they are the kind's
+// keys (voxel ids for the searches over voxels; host_pose.inc packs a pin beside the id), copied to c.src and handed to seed.
 struct SearchKind {
     const char *fn;        // the exported function, in front of every message
     int32_t frontiers;     // frontier bitmaps per source: 2 for hops, W + 1 for the weighted ring
     int32_t zeroed;        // how many of them a search needs zeroed (per source, the first ones): the level kernels write the others whole
     int32_t window;
+    int64_t words, ints;   // the size of one bitmap in 64-bit words and of one source's field in int32: d.nw and d.n for the searches over voxels
     int64_t first, bound;  // the first level, and one the loop must not pass (WA_ERR_STATE)
     std::function<void(const SearchChunk &, int32_t)> seed;
     std::function<void(const SearchChunk &, int32_t, int64_t, const long long *, int32_t)> level;
 };
 
-// The memory rule (DESIGN 4j): a source costs frontiers + 1 bitmaps, a field of 4 bytes per voxel when one is kept and a matrix row; a
+// The memory rule (DESIGN 4j): a source costs frontiers + 1 bitmaps of k.words words, a field of k.ints int32 when one is kept and a matrix row; a
 // chunk takes at most half of what wa_ctx_memory_info reports free behind the bit-packed occupancy, at least one source, at most
 // WA_GEO_MAX_CHUNK, WA_GEO_CHUNK forces fewer, and is halved while the device refuses the allocation.
 static int search_chunk_alloc(const wa_grid *g, const WaGeoDims &d, const SearchKind &k, int32_t n_src, bool with_field, int32_t n_tgt, SearchChunk *c)
@@ -101,15 +103,15 @@ static int search_chunk_alloc(const wa_grid *g, const WaGeoDims &d, const Search
     int64_t free_b = 0;
     int rc = wa_ctx_memory_info(ctx, &free_b, nullptr);
     if (rc) return rc;
-    const int64_t per = (int64_t)(k.frontiers + 1) * d.nw * 8 + (with_field ? d.n * 4 : 0) + (int64_t)n_tgt * 4 + 16;
+    const int64_t per = (int64_t)(k.frontiers + 1) * k.words * 8 + (with_field ? k.ints * 4 : 0) + (int64_t)n_tgt * 4 + 16;
     int64_t cap = (free_b / 2) / per;
     cap = std::max<int64_t>(1, std::min<int64_t>(cap, std::min<int64_t>(n_src, WA_GEO_MAX_CHUNK)));
     if (const int forced = env_int("WA_GEO_CHUNK", 0)) cap = std::max<int64_t>(1, std::min<int64_t>(cap, forced));   // (tests: several chunks on a small grid)
     for (;; cap = (cap + 1) / 2) {
         SearchChunk t;   // (a refused attempt gives back what it got when t goes)
-        hipError_t e = t.seen.alloc((size_t)(cap * d.nw));
-        e = e ? e : t.fronts.alloc((size_t)(cap * k.frontiers * d.nw));
-        if (e == hipSuccess && with_field) e = t.field.alloc((size_t)(cap * d.n));
+        hipError_t e = t.seen.alloc((size_t)(cap * k.words));
+        e = e ? e : t.fronts.alloc((size_t)(cap * k.frontiers * k.words));
+        if (e == hipSuccess && with_field) e = t.field.alloc((size_t)(cap * k.ints));
         if (e == hipSuccess && n_tgt > 0) e = t.mat.alloc((size_t)(cap * n_tgt));
         e = e ? e : t.last.alloc((size_t)cap);
         e = e ? e : t.stop.alloc((size_t)cap);
@@ -126,9 +128,9 @@ static int search_run(const wa_grid *g, const WaGeoDims &d, const SearchKind &k,
 {
     wa_ctx *ctx = g->ctx;
     hipError_t e = hipMemcpyAsync(c.src, src, sizeof(long long) * ns, hipMemcpyHostToDevice, ctx->stream);
-    e = e ? e : hipMemsetAsync(c.seen, 0, sizeof(unsigned long long) * (size_t)(ns * d.nw), ctx->stream);
-    e = e ? e : hipMemsetAsync(c.fronts, 0, sizeof(unsigned long long) * (size_t)((int64_t)ns * k.zeroed * d.nw), ctx->stream);
-    if (e == hipSuccess && c.field) e = hipMemsetAsync(c.field, 0xff, sizeof(int32_t) * (size_t)(ns * d.n), ctx->stream);   // WA_HOPS_NONE / WA_DIST_NONE
+    e = e ? e : hipMemsetAsync(c.seen, 0, sizeof(unsigned long long) * (size_t)(ns * k.words), ctx->stream);
+    e = e ? e : hipMemsetAsync(c.fronts, 0, sizeof(unsigned long long) * (size_t)((int64_t)ns * k.zeroed * k.words), ctx->stream);
+    if (e == hipSuccess && c.field) e = hipMemsetAsync(c.field, 0xff, sizeof(int32_t) * (size_t)(ns * k.ints), ctx->stream);   // WA_HOPS_NONE / WA_DIST_NONE
     if (e == hipSuccess && c.mat) e = hipMemsetAsync(c.mat, 0xff, sizeof(int32_t) * (size_t)ns * n_tgt, ctx->stream);
     if (e == hipSuccess) {
         k.seed(c, ns);
@@ -276,6 +278,7 @@ static SearchKind geo_kind(const wa_grid *g, const WaGeoDims &d, const char *fn)
     SearchKind k;
     k.fn = fn;
     k.frontiers = 2; k.zeroed = 1; k.window = 1;
+    k.words = d.nw; k.ints = d.n;
     // a search of F free voxels has at most F - 1 productive levels; one more launch looks at the last frontier
     k.first = 1; k.bound = g->n_free + 1;
     hipStream_t st = g->ctx->stream;

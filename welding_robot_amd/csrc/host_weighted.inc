@@ -73,6 +73,7 @@ static SearchKind wgt_kind(const wa_grid *g, const WaGeoDims &d, const WgtCosts 
     SearchKind k;
     k.fn = fn;
     k.frontiers = R; k.zeroed = R; k.window = R;
+    k.words = d.nw; k.ints = d.n;
     // the largest distance is at most W * (n_free - 1) <= 2^31 - 1 (wgt_costs); R more launches see the ring empty
     k.first = 0; k.bound = std::min<int64_t>((int64_t)W * (g->n_free - 1) + R + 1, (int64_t)INT32_MAX - WA_GEO_BLOCK);
     hipStream_t st = g->ctx->stream;

@@ -39,6 +39,7 @@
 #include "seamtour_kernels.hpp"
 #include "torch_kernels.hpp"
 #include "reach_kernels.hpp"
+#include "pose_kernels.hpp"
 #include "stl_text.hpp"
 #include "acs_plan.hpp"
 
@@ -842,5 +843,6 @@ void *wa_ctx_stream(wa_ctx *c) { return c ? (void *)c->stream : nullptr; }
 #include "host_seamtour.inc"
 #include "host_torch.inc"
 #include "host_reach.inc"
+#include "host_pose.inc"
 
 }  // extern "C"
