@@ -10,10 +10,15 @@
 // put the path nodes' records and the table rows of generation g + j in place (wa_conv_flush_rows).  The walk of generation g + j then finds the
 // field, the table, the control block and the masks as the three-launch path would have left them.
 //
-// grid = (WA_CONV_BLOCKS, slots), ants dealt over the blocks; every block keeps the whole path state and advances it on its own: no grid barrier,
-// no waiting on memory anywhere.  A block whose ant leaves the path (or dies) in generation g + t stops and reports t; block 0 runs the whole
-// window and writes, per generation, a snapshot of the path state to the slot's scratch block and the trace row.  The block that finishes last
-// (a ticket counter behind a fence) commits j = the smallest t reported.
+// grid = (B, slots), the path's NODES dealt over the blocks (B: WA_CONVERGED_BLOCKS when the solver is created): block b owns nodes [b m, (b + 1) m),
+// m = ceil(best_len / B), keeps their records, heuristic values, prefix-tabu bits and rows in LDS and nobody else's.  A node's state never reads
+// another node's, and no generation's state needs the verdict of the check, so per generation a block advances its own nodes and checks EVERY ant of
+// the colony at them: nothing is computed twice except the control block's chain, which depends on neither records nor rows and is run for all W
+// generations up front, by one wavefront, into a table in LDS (beside it the generations' draw keys).  In the loop the check (lane = ant, the rows read
+// uniformly: one 64-bit ant key per ant, generation and block) and the advance (16 lanes per node, straight into the slot's snapshots at the node's own
+// offset) run in different wavefronts, the rows double-buffered, behind ONE barrier per generation.  No grid barrier, no waiting on memory anywhere.
+// A block at whose nodes an ant leaves the path (or dies) in generation g + t stops and reports t; a block without nodes reports W.  The block that
+// finishes last (a ticket counter behind a fence) commits j = the smallest t reported, with the control block and the trace rows out of its table.
 //
 // The verdict also goes to the HOST (wa_conv_report): a word of pinned, coherent host memory per slot takes (seq << 8) | j from every launch that is
 // given one -- from block 0 where the window does not apply (j = 0), from the committing block behind its writes otherwise.  The host reads it to leave
@@ -22,11 +27,14 @@
 // committed exactly up to its generation.
 #pragma once
 
-#define WA_CONV_THREADS 1024
-#define WA_CONV_BLOCKS 32
+#define WA_CONV_CHECK_WAVES 4     // wavefronts of a block that check the ants (lane = ant), ...
+#define WA_CONV_ADV_WAVES 4       // ... and that advance the block's nodes (16 lanes per node)
+#define WA_CONV_THREADS ((WA_CONV_CHECK_WAVES + WA_CONV_ADV_WAVES) * 64)
+#define WA_CONV_BLOCKS 64         // default of WA_CONVERGED_BLOCKS (profiles/converged_nodes/README.md)
+#define WA_CONV_BLOCKS_MAX 256
 #define WA_CONV_MAX_WINDOW 64
-#define WA_CONV_NODE_CAP 1024     // longest best path a window covers: 96 bytes of LDS per node (six records, six heuristic values, the prefix-tabu bits, the row)
-#define WA_CONV_NODE_LDS 96
+#define WA_CONV_NODE_CAP 1024     // longest best path a window covers (the snapshots' stride is at most this)
+#define WA_CONV_NODE_LDS 128      // LDS per node a block owns: six records, six heuristic values, the prefix-tabu bits (16 floats); the row of this generation and of the next
 #define WA_CONV_SNAP 14           // floats per node of a snapshot: six records + the row
 
 struct WaConvHdr {                // head of a slot's scratch block; the snapshots follow
@@ -99,11 +107,50 @@ __device__ __forceinline__ void wa_conv_report(uint32_t *verdict, int32_t slot, 
     } else __hip_atomic_store(verdict + slot, seq << 8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// wa_add_ranked for an edge that carries EVERY depositing rank or none, which is all a converged generation has (rep_mask: ranks 0..n-1 on the path's own
+// edge, nothing anywhere else): p += dep[b] + bonus for b = 0..n-1 in ascending order where `on`, p as it is elsewhere -- the same adds on the same
+// operands in the same order, so the bits agree with wa_add_ranked(p, on ? (1 << n) - 1 : 0, ...).  What differs is the cost of a rank: the sum
+// dep[b] + bonus is formed once in lane b (the same fp32 add as behind wa_add_ranked's readlane), and with no mask to test a rank is one readlane of a
+// constant lane and one add, where the general loop spends nine instructions on it (measured: profiles/converged_nodes/README.md).  Ranks are taken in
+// blocks of eight; the ones at and above n add -0.0f, which leaves every value as it is, bit for bit (x + -0 == x, zeros of either sign included).
+// The whole wavefront calls this together; dep_lane: lane l holds the coefficient of rank bit l.
+__device__ __forceinline__ float wa_add_all_ranked(float p, bool on, float dep_lane, float bonus, int32_t n)
+{
+    n = __builtin_amdgcn_readfirstlane(n);
+    const float t_lane = (int32_t)(threadIdx.x & 63) < n ? dep_lane + bonus : -0.f;
+    float q = p;
+    asm volatile("" : "+v"(q));   // the edge's record has arrived here: no add waits for a load
+#pragma unroll
+    for (int b0 = 0; b0 < 64; b0 += 8) {
+        if (b0 >= n) break;
+        float t[8];   // (eight scalars first, then the eight dependent adds: no add waits for its readlane)
+#pragma unroll
+        for (int j = 0; j < 8; j++) t[j] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t_lane), b0 + j));
+#pragma unroll
+        for (int j = 0; j < 8; j++) q = q + t[j];
+    }
+    return on ? q : p;
+}
+
+// nodes of a path of `nodes` nodes that one of `blocks` blocks owns at most (host: the LDS a block asks for; device: where the shares start)
+__host__ __device__ inline int32_t wa_conv_share(int32_t nodes, int32_t blocks) { return (nodes + blocks - 1) / blocks; }
+
+// What a block keeps in LDS behind its nodes' state (all of it in the dynamic region, every offset a multiple of 16 bytes)
+struct WaConvShared {
+    WaSlotCtl tab[WA_CONV_MAX_WINDOW + 1];   // tab[t]: the control block as generation gen0 + t finds it; tab[t + 1]: as it leaves it
+    unsigned long long key[WA_CONV_MAX_WINDOW];   // wa_ctr_key of generation gen0 + t
+    int32_t bad[WA_CONV_MAX_WINDOW];         // an ant left the path at one of this block's nodes in generation gen0 + t
+    int32_t run;                             // generations of the window whose colony is in range (the chain stops at the first that is not)
+    int32_t last, j, pad_;
+};
+__host__ __device__ inline size_t wa_conv_lds_bytes(int32_t conv_nodes, int32_t blocks)
+{
+    return (size_t)wa_conv_share(conv_nodes, blocks) * WA_CONV_NODE_LDS + sizeof(WaConvShared);
+}
+
 __global__ __launch_bounds__(WA_CONV_THREADS) void k_converged_run(WaAcsDev D, WaRun R, int32_t gen0, int32_t W, uint32_t *verdict, uint32_t seq)
 {
-    extern __shared__ float wa_conv_lds[];
-    __shared__ WaSlotCtl s_c, s_c0;
-    __shared__ int32_t s_bad, s_last, s_j;
+    extern __shared__ __attribute__((aligned(16))) float wa_conv_lds[];
     const int32_t slot = blockIdx.y, blk = blockIdx.x, nblk = gridDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     WaSlotCtl *ctl = &D.ctl[slot];
     WaConvHdr *hdr = wa_conv_hdr(D, slot);
@@ -119,106 +166,109 @@ __global__ __launch_bounds__(WA_CONV_THREADS) void k_converged_run(WaAcsDev D, W
         if (blk == 0 && tid == 0) wa_conv_report(verdict, slot, seq, 0);
         return;
     }
-    float *s_rec = wa_conv_lds;                              // [conv_nodes][16]: records 0..5, heuristic 6..11, prefix-tabu bits 12
-    float *s_row = wa_conv_lds + (int64_t)D.conv_nodes * 16;  // [conv_nodes][8]: the replay table's rows
+    // ---- this block's share of the path: nodes n0 .. n0 + mine - 1 (none: a grid of more blocks than the path has nodes)
+    const int32_t cap = wa_conv_share(D.conv_nodes, nblk);   // (blen <= conv_nodes: a share never exceeds it)
+    const int32_t m = wa_conv_share(blen, nblk), n0 = blk * m;
+    const int32_t mine = blen - n0 < 0 ? 0 : blen - n0 < m ? blen - n0 : m;
+    const int32_t last = blen - 1;                // decisions exist at nodes 0 .. blen-2: the last node has records and a row, and no edge taken
+    const int32_t ndec = (n0 + mine < last ? n0 + mine : last) - n0;
+    float *s_row = wa_conv_lds;                   // [2][cap][8]: the replay table's rows, generation gen0 + t in half t & 1
+    float *s_rec = wa_conv_lds + cap * 16;        // [cap][16]: records 0..5, heuristic 6..11, prefix-tabu bits 12
+    WaConvShared &S = *reinterpret_cast<WaConvShared *>(wa_conv_lds + cap * 32);
     {
-        const int32_t *bpath = D.bestpath + (int64_t)slot * D.path_cap;
-        const uint8_t *btabu = D.besttabu + (int64_t)slot * D.path_cap;
+        const int32_t *bpath = D.bestpath + (int64_t)slot * D.path_cap + n0;
+        const uint8_t *btabu = D.besttabu + (int64_t)slot * D.path_cap + n0;
         const float *pher = D.pher + (int64_t)slot * D.pher_stride;
         const float *heur = D.heur + (int64_t)ctl->heur_slot * D.pher_stride;
-        const float *T = D.rtab + (int64_t)slot * D.path_cap * 8;
-        for (int32_t x = tid; x < blen * 16; x += WA_CONV_THREADS) {
+        const float *T = D.rtab + ((int64_t)slot * D.path_cap + n0) * 8;
+        for (int32_t x = tid; x < mine * 16; x += WA_CONV_THREADS) {
             const int32_t i = x >> 4, q = x & 15;
             const int64_t v = bpath[i] & (int32_t)WA_ID_MASK;
             s_rec[x] = q < 6 ? pher[v * 6 + q] : q < 12 ? heur[v * 6 + q - 6] : q == 12 ? __uint_as_float((uint32_t)btabu[i]) : 0.f;
         }
-        for (int32_t x = tid; x < blen * 8; x += WA_CONV_THREADS) s_row[x] = T[x];
-        if (tid == 0) { s_c = *ctl; s_c0 = s_c; s_bad = 0; }
+        for (int32_t x = tid; x < mine * 8; x += WA_CONV_THREADS) {
+            const float v = T[x];
+            s_row[x] = v;
+            if ((x & 7) == 7) s_row[cap * 8 + x] = v;   // (the edge taken stays what it is: both halves hold it)
+        }
+    }
+    // ---- the control block's chain, all W steps: it depends on neither records nor rows.  One wavefront (wa_conv_ctl_step: lane 0 writes); another one
+    // forms the generations' draw keys meanwhile
+    if (wave == 0) {
+        if (lane == 0) S.tab[0] = *ctl;
+        int32_t run = 0;
+        for (; run < W; run++) {
+            const int32_t gen = gen0 + run;
+            const int32_t colony = S.tab[run].colony[gen & 1];
+            if (!(colony >= 1 && colony <= D.max_colony)) break;   // (uniform: every lane reads the same word)
+            if (lane == 0) S.tab[run + 1] = S.tab[run];
+            wa_conv_ctl_step(S.tab[run + 1], R, gen);
+        }
+        if (lane == 0) S.run = run;
+    } else if (wave == 1 && lane < W) {
+        S.key[lane] = wa_ctr_key(R.seed, ctl->stream, (uint32_t)(gen0 + lane));
+        S.bad[lane] = 0;
     }
     __syncthreads();
-    const int32_t last = blen - 1;                // decisions exist at nodes 0 .. blen-2
-    const int32_t chunks = (last + 63) >> 6;
-    int32_t my_t = W;                             // the first generation of the window in which an ant of this block left the path
-    for (int32_t t = 0; t < W; t++) {
+    const int32_t run = S.run;
+    int32_t my_t = mine > 0 ? run : W;            // the first generation of the window in which an ant left the path at one of this block's nodes
+    for (int32_t t = 0; t < run && mine > 0; t++) {
         const int32_t gen = gen0 + t;
-        const int32_t colony = s_c.colony[gen & 1];
-        const bool col_ok = colony >= 1 && colony <= D.max_colony;
-        // ---- this block's ants against the rows: the test of wa_walk_replay, one lane per node, (ant, 64 nodes) items dealt over the wavefronts
-        if (col_ok && blk < colony) {
-            const uint64_t genkey = wa_ctr_key(R.seed, s_c.stream, (uint32_t)gen);
-            const int32_t items = ((colony - blk + nblk - 1) / nblk) * chunks;
-            for (int32_t it = wave; it < items; it += WA_CONV_THREADS / 64) {
-                const int32_t q = it / chunks, node = (it - q * chunks) * 64 + lane;
-                const uint64_t antkey = wa_ctr_antkey(genkey, (uint32_t)(blk + nblk * q));
-                const bool valid = node < last;
-                const float4 *r4 = reinterpret_cast<const float4 *>(s_row + (valid ? node : 0) * 8);
-                const float4 ca = r4[0], cb = r4[1];
-                const uint32_t h = wa_replay_hits(ca, cb, (int32_t)wa_ctr_draw(antkey, (uint32_t)node));
-                const int pick = h ? 31 - __clz((int)h) : -1;
-                if (__ballot(valid && pick != __float_as_int(cb.w)) != 0 && lane == 0) s_bad = 1;
+        const int32_t colony = S.tab[t].colony[gen & 1];
+        const float *row = s_row + (t & 1) * cap * 8;
+        if (wave < WA_CONV_CHECK_WAVES) {
+            // ---- every ant of the colony against this block's rows: the test of wa_walk_replay, one lane per ant, the row the same for all lanes
+            const uint64_t genkey = S.key[t];
+            for (int32_t a = tid; a < colony; a += WA_CONV_CHECK_WAVES * 64) {
+                const uint64_t antkey = wa_ctr_antkey(genkey, (uint32_t)a);
+                bool bad = false;
+                for (int32_t n = 0; n < ndec; n++) {
+                    const float4 *r4 = reinterpret_cast<const float4 *>(row + n * 8);
+                    const float4 ca = r4[0], cb = r4[1];
+                    const uint32_t h = wa_replay_hits(ca, cb, (int32_t)wa_ctr_draw(antkey, (uint32_t)(n0 + n)));
+                    const int pick = h ? 31 - __clz((int)h) : -1;
+                    bad = bad || pick != __float_as_int(cb.w);
+                }
+                if (bad) S.bad[t] = 1;
             }
-        }
-        __syncthreads();
-        const bool bad = !col_ok || s_bad != 0;
-        if (bad && my_t == W) my_t = t;
-        if (!col_ok || (bad && blk != 0)) break;          // (uniform over the block)
-        __syncthreads();
-        // ---- generation gen is over: what the post-walk launch publishes
-        if (wave == 0) {
-            wa_conv_ctl_step(s_c, R, gen);
-            if (lane == 0) s_bad = 0;
-        }
-        __syncthreads();
-        // ---- the path's own edges: x rho (the sweep), then the ranked deposits of all n_dep ranks (rep_mask: every one on the replay track), one lane per node
-        const int32_t n_dep = s_c.n_dep;
-        const unsigned long long G = s_c.rep_mask;
-        const float lambda = s_c.dep_lambda, Q = s_c.dep_Q;
-        const bool okl = lane < colony && lane < n_dep;
-        const float dep_lane = okl ? (lambda - (float)(lane + 1)) * Q / bestL : 0.f;   // :211, rank bit l in lane l
-        const float bonus_on = wa_uniform(1.f * lambda * Q / bestL);                   // second term of :211: the edge's two ends lie on the best path (:209)
-        for (int32_t i = tid; __any(i < last); i += WA_CONV_THREADS) {
-            const bool live = i < last;
-            const int32_t ii = live ? i : 0;
-            const int32_t nk = __float_as_int(s_row[ii * 8 + 7]);
-            float p = s_rec[ii * 16 + nk] * R.rho;
-            p = wa_add_ranked(p, live ? G : 0ULL, dep_lane, bonus_on, n_dep);
-            if (live) s_rec[ii * 16 + nk] = p;
-        }
-        __syncthreads();
-        // ---- every other record x rho, and the rows of the new values (wa_table_rows' arithmetic, 16 lanes per node)
-        {
-            const int32_t k2 = tid & 15, kk = k2 < 6 ? k2 : 5;
-            for (int32_t i = tid >> 4; __any(i < blen); i += WA_CONV_THREADS / 16) {
-                const bool live = i < blen;
+        } else {
+            // ---- generation gen is over for this block's nodes.  The path's own edge (role k2 == the edge taken): x rho (the sweep), then the ranked
+            // deposits of all n_dep ranks (rep_mask: every one on the replay track); every other record x rho; the rows of the new values
+            // (wa_table_rows' arithmetic, 16 lanes per node) into the other half, and all of it into snapshot t (the state after t + 1 generations)
+            const WaSlotCtl &c = S.tab[t + 1];    // what the post-walk launch of generation gen publishes
+            const int32_t n_dep = c.n_dep;
+            const float lambda = c.dep_lambda, Q = c.dep_Q;
+            const bool okl = lane < colony && lane < n_dep;
+            const float dep_lane = okl ? (lambda - (float)(lane + 1)) * Q / bestL : 0.f;   // :211, rank bit l in lane l
+            const float bonus_on = wa_uniform(1.f * lambda * Q / bestL);                   // second term of :211: the edge's two ends lie on the best path (:209)
+            float *nrow = s_row + ((t + 1) & 1) * cap * 8;
+            float *snap = wa_conv_snap(D, slot, t) + (int64_t)n0 * WA_CONV_SNAP;
+            const int32_t k2 = lane & 15, kk = k2 < 6 ? k2 : 5;
+            // (the trips are the wavefront's: a row past the share's end goes along on its first node and writes nothing, so that wa_add_all_ranked finds every lane there)
+            for (int32_t i = (wave - WA_CONV_CHECK_WAVES) * 4 + (lane >> 4); __any(i < mine); i += WA_CONV_ADV_WAVES * 4) {
+                const bool live = i < mine;
                 const int32_t ii = live ? i : 0;
-                const int32_t nk = __float_as_int(s_row[ii * 8 + 7]);
-                float p = s_rec[ii * 16 + kk];
+                const int32_t nk = __float_as_int(row[ii * 8 + 7]);   // (-1 at the path's last node: nothing is deposited there)
+                float p = s_rec[ii * 16 + kk] * R.rho;
                 const float h = s_rec[ii * 16 + 6 + kk];
                 const uint32_t bt = __float_as_uint(s_rec[ii * 16 + 12]);
-                if (kk != nk) p = p * R.rho;
+                p = wa_add_all_ranked(p, live && k2 == nk, dep_lane, bonus_on, n_dep);
                 float thr, tot;
                 wa_row_values(R, p, h, k2, bt, thr, tot);
                 if (!live) continue;
-                if (k2 < 6) { s_rec[i * 16 + k2] = p; s_row[i * 8 + k2] = thr; }
-                if (k2 == 5) s_row[i * 8 + 6] = tot;
+                float *sn = snap + i * WA_CONV_SNAP;
+                if (k2 < 6) {
+                    s_rec[i * 16 + k2] = p;
+                    nrow[i * 8 + k2] = thr;
+                    sn[k2] = p;
+                    sn[6 + k2] = thr;
+                }
+                if (k2 == 5) { nrow[i * 8 + 6] = tot; sn[12] = tot; }
+                if (k2 == 0) sn[13] = __int_as_float(nk);
             }
         }
         __syncthreads();
-        if (blk == 0) {   // snapshot t (the state after t + 1 generations) and the trace row of generation gen
-            float *snap = wa_conv_snap(D, slot, t);
-            for (int32_t x = tid; x < blen * WA_CONV_SNAP; x += WA_CONV_THREADS) {
-                const int32_t i = x / WA_CONV_SNAP, q = x - i * WA_CONV_SNAP;
-                snap[x] = q < 6 ? s_rec[i * 16 + q] : s_row[i * 8 + (q - 6)];
-            }
-            if (tid == 0 && gen < D.trace_cap) {
-                const int64_t tr = (int64_t)slot * D.trace_cap + gen;
-                D.trBest[tr] = bestL;
-                D.trIter[tr] = bestL;
-                D.trColony[tr] = colony;
-                D.trFinite[tr] = colony;
-                D.trSteps[tr] = (long long)colony * (long long)(blen - 1);
-            }
-        }
+        if (S.bad[t] != 0) { my_t = t; break; }   // (uniform over the block; bad[t] is written in front of this barrier only)
     }
     // ---- the block that finishes last commits
     if (tid == 0) {
@@ -231,38 +281,46 @@ __global__ __launch_bounds__(WA_CONV_THREADS) void k_converged_run(WaAcsDev D, W
             is_last = 1;
             j = W - (int32_t)atomicMax(&hdr->rem, 0u);
         }
-        s_last = is_last;
-        s_j = j;
+        S.last = is_last;
+        S.j = j;
     }
     __syncthreads();
-    if (!s_last) return;
-    const int32_t j = s_j;
-    if (wave == 0) {
-        for (int32_t t = 0; t < j; t++) wa_conv_ctl_step(s_c0, R, gen0 + t);   // (the control block of generation gen0 + j, from the one the window found)
-        if (lane == 0) {
-            hdr->rem = 0;
-            hdr->ticket = 0;
-            if (j > 0) {
-                s_c0.spec_until = gen0 + j;
-                *ctl = s_c0;
-                hdr->pending = j;
-                hdr->gens += (unsigned long long)j;
-                if (j == W) hdr->whole += 1; else hdr->cut += 1;
-            }
+    if (!S.last) return;
+    const int32_t j = S.j;                        // (<= run: the block of node 0 reports no more)
+    if (tid == 0) {
+        hdr->rem = 0;
+        hdr->ticket = 0;
+        if (j > 0) {
+            WaSlotCtl c = S.tab[j];               // the control block of generation gen0 + j
+            c.spec_until = gen0 + j;
+            *ctl = c;
+            hdr->pending = j;
+            hdr->gens += (unsigned long long)j;
+            if (j == W) hdr->whole += 1; else hdr->cut += 1;
         }
     }
-    __syncthreads();
-    if (j > 0) {   // perm / depA as the ranking of generation gen0 + j - 1 leaves them
-        const int32_t colony = s_c0.colony[(gen0 + j - 1) & 1];
-        const float lambda = s_c0.dep_lambda, Q = s_c0.dep_Q;
+    if (j > 0) {   // perm / depA as the ranking of generation gen0 + j - 1 leaves them, and the trace rows of the committed generations
+        const int32_t colony = S.tab[j].colony[(gen0 + j - 1) & 1];
+        const float lambda = S.tab[j].dep_lambda, Q = S.tab[j].dep_Q;
         for (int32_t r = tid; r < colony; r += WA_CONV_THREADS) {
             const int32_t o = r + 1;
             const bool ok = !(bestL == INFINITY || (float)o > lambda - 1);
             D.perm[(int64_t)slot * D.max_colony + r] = r;
             D.depA[(int64_t)slot * D.max_colony + r] = ok ? (lambda - (float)o) * Q / bestL : 0.f;
         }
+        for (int32_t t = tid; t < j; t += WA_CONV_THREADS) {
+            const int32_t gen = gen0 + t;
+            if (gen >= D.trace_cap) continue;
+            const int32_t col = S.tab[t].colony[gen & 1];
+            const int64_t tr = (int64_t)slot * D.trace_cap + gen;
+            D.trBest[tr] = bestL;
+            D.trIter[tr] = bestL;
+            D.trColony[tr] = col;
+            D.trFinite[tr] = col;
+            D.trSteps[tr] = (long long)col * (long long)(blen - 1);
+        }
     }
-    // ---- the verdict, behind this block's writes of ctl, perm and depA
+    // ---- the verdict, behind this block's writes of ctl, perm, depA and the trace rows
     __syncthreads();
     if (tid == 0) wa_conv_report(verdict, slot, seq, j);
 }

@@ -73,7 +73,7 @@ struct WaAcsDev {
     // Null where the mechanism is off (WA_CONVERGED_RUN=0, lazy fields, 26 neighbours, REF mode, colonies past the fused path)
     char *conv;                    // [slot][conv_stride] bytes
     int64_t conv_stride;
-    int32_t conv_nodes;            // longest best path a window covers (the window kernel keeps 96 bytes of LDS per node)
+    int32_t conv_nodes;            // longest best path a window covers (the snapshots' stride)
     int32_t vbits_rows;            // bitmap rows per slot: max_colony (+ WA_RESUME_MAX rows of the resume blocks when the solver has straggler pools)
 };
 

@@ -180,6 +180,8 @@ static int acs_create_once(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, in
     if (s->conv_window > WA_CONV_MAX_WINDOW) s->conv_window = WA_CONV_MAX_WINDOW;
     if (s->conv_window < 1) s->conv_on = false;
     s->conv_nodes_env = env_int("WA_CONVERGED_NODES", 0);
+    s->conv_blocks = env_int("WA_CONVERGED_BLOCKS", WA_CONV_BLOCKS);
+    s->conv_blocks = s->conv_blocks < 1 ? 1 : s->conv_blocks > WA_CONV_BLOCKS_MAX ? WA_CONV_BLOCKS_MAX : s->conv_blocks;
     s->conv_readback = env_int("WA_CONVERGED_READBACK", 1) != 0;
     s->conv_wait_us = env_int("WA_CONVERGED_WAIT_US", 200000);
     s->conv_spec = env_int("WA_CONVERGED_SPECULATE", 1) != 0;
@@ -983,8 +985,8 @@ static hipError_t launch_converged(wa_acs *s, WaGroupRun &G, int32_t gen, int32_
 {
     G.V.pher = s->pher_buf[G.cur] + (int64_t)G.slot0 * s->D.pher_stride;   // the field as generation `gen` finds it
     uint32_t *verdict = s->conv_readback && s->h_verdict ? s->h_verdict + G.slot0 : nullptr;
-    k_converged_run<<<dim3(WA_CONV_BLOCKS, (unsigned)G.P), WA_CONV_THREADS, (size_t)s->D.conv_nodes * WA_CONV_NODE_LDS, G.st>>>(G.V, s->R, gen, W, verdict,
-                                                                                                                             s->conv_seq & 0xffffffu);
+    k_converged_run<<<dim3((unsigned)s->conv_blocks, (unsigned)G.P), WA_CONV_THREADS, wa_conv_lds_bytes(s->D.conv_nodes, s->conv_blocks), G.st>>>(
+        G.V, s->R, gen, W, verdict, s->conv_seq & 0xffffffu);
     for (int32_t q = 0; q < G.P; q++) s->conv_enqueued[(size_t)(G.slot0 + q)]++;
     return hipGetLastError();
 }
@@ -1142,7 +1144,7 @@ int wa_acs_run(wa_acs *s, int32_t n_generations)
         WA_LDS_ATTR(true, false, false, true, true); WA_LDS_ATTR(true, false, false, false, true); WA_LDS_ATTR(true, true, false, true, true); WA_LDS_ATTR(true, true, false, false, true);
         WA_LDS_ATTR(true, false, false, true, false, true); WA_LDS_ATTR(true, false, false, false, false, true); WA_LDS_ATTR(true, true, false, true, false, true); WA_LDS_ATTR(true, true, false, false, false, true);
 #undef WA_LDS_ATTR
-        a = a ? a : hipFuncSetAttribute((const void *)k_converged_run, hipFuncAttributeMaxDynamicSharedMemorySize, WA_CONV_NODE_CAP * WA_CONV_NODE_LDS);
+        a = a ? a : hipFuncSetAttribute((const void *)k_converged_run, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wa_conv_lds_bytes(WA_CONV_NODE_CAP, 1));
         a = a ? a : hipFuncSetAttribute((const void *)k_walk_ref, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
         a = a ? a : hipFuncSetAttribute((const void *)k_walk_dev26<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
         a = a ? a : hipFuncSetAttribute((const void *)k_walk_dev26<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);

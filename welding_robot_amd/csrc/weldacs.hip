@@ -184,6 +184,7 @@ struct wa_acs {
     // converged generations in one launch (acs_converged.hpp, k_converged_run)
     bool conv_on = true;                 // WA_CONVERGED_RUN (read at creation); off by rule for lazy fields, 26 neighbours, REF mode, colonies past the fused path
     int32_t conv_window = 32;            // WA_CONVERGED_WINDOW: generations a window covers at most
+    int32_t conv_blocks = 0;             // WA_CONVERGED_BLOCKS: blocks per slot of the window kernel, the path's nodes dealt over them (1 .. WA_CONV_BLOCKS_MAX)
     int32_t conv_nodes_env = 0;          // WA_CONVERGED_NODES: a lower cap on the best path a window covers (tests); 0 = WA_CONV_NODE_CAP
     int32_t conv_until = 0;              // generations below this one are covered by a window already enqueued
     char *d_conv = nullptr;              // the slots' scratch blocks (header + snapshots), allocated by the first call that enqueues a window
