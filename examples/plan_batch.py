@@ -410,6 +410,7 @@ def torch_stage(ctx, metal, xyz, stops, K, max_turn=-1):
     tool, dirs, length16 = torch_tool_and_cone(metal, K)
     r = curve.torch_axes(metal, dirs, tool, w_near=4, w_want=1, w_turn=8, near_add=8, max_turn=max_turn, want=want, off=off, feas=False)
     info = dict(r["summary"], K=K, n_legs=len(off) - 1, directions_used=int(len(set(r["dir"].tolist()))), tool_length16=length16)
+    torch_stage.last = (off, r["dir"], dirs, tool)               # (what --tick-poses goes on from)
     if n > 1:
         a = dirs[r["dir"]].astype(np.float64)
         mid = a[:-1] + a[1:]
@@ -419,6 +420,27 @@ def torch_stage(ctx, metal, xyz, stops, K, max_turn=-1):
         cs = half.torch_check(metal, mid.astype(np.float32), tool, 8)[2]
         info.update(interpolated=dict(n=cs["n"], n_blocked=cs["n_chosen_blocked"], first_blocked=cs["first_chosen_blocked"],
                                       n_near=cs["n_chosen_near"]))
+    return info
+
+
+def tick_pose_stage(ctx, metal, xyz, limits, tick, omega, h, duration_free):
+    """Tool poses at the controller's ticks (--tick-poses), on the device from end to end: the chosen directions of torch_stage as
+    quantised axes, smoothed along the path where the body stays clear of the metal (wa_traj_axes_smooth), turned into a per-sample
+    speed limit for the turn rate omega (wa_traj_axes_limits), the curve timed again under that limit (wa_traj_retime), and the axis
+    at every tick with its check against the metal (wa_traj_tick_axes).  The axes never pass through the host."""
+    off, chosen, dirs, tool = torch_stage.last
+    v_max, acc, dec, a_lat, v_near, near_d2 = limits
+    curve = api.Trajectory.from_points(ctx, xyz)
+    sm = curve.smooth_axes(api.quantise_axes(dirs)[chosen], h, 8, metal, tool, off)
+    v_limit, ls = curve.axis_limits(sm["q"], omega, v_max, v_max * 1e-3)
+    time_q, w_q, _, _, rs = curve.retime(v_max, acc, dec, tick, a_lat=a_lat, grid=metal, v_near=v_near, near_d2=int(near_d2), v_limit=v_limit,
+                                         ticks=False)
+    info = dict(omega=omega, h=h, smooth=sm["summary"], limits=ls, duration_free=duration_free, duration_turn_limited=rs["time_q"] / api.RETIME_Q,
+                ticks=None, max_tick_turn=None, blocked_ticks=None)
+    if rs["n_ticks"] <= 1 << 31:
+        axes, _, ts = curve.tick_axes(sm["q"], time_q, w_q, acc, dec, tick, metal, tool, near_add=8, blocked=False)
+        info.update(ticks=ts, max_tick_turn=ts["max_tick_turn"], blocked_ticks=ts["n_blocked"])
+        axes.close()
     return info
 
 
@@ -483,6 +505,10 @@ def main():
                     help="after --fit or --retime: the torch axis at every sample of the trajectory, one of K directions (1 .. 256) of a cone "
                          "around +z, so that the torch body clears the metal (wa_traj_tool_axes); prints the summary and the check of the "
                          "interpolated axes between samples")
+    ap.add_argument("--tick-poses", type=float, nargs="+", default=None, metavar=("OMEGA", "H"),
+                    help="--retime --torch K: the torch axis at every controller tick, on the device: the chosen directions smoothed over windows "
+                         "of half-width H along the path (default: 8 voxels) where the body stays clear, the timing limited to OMEGA (chord of "
+                         "the unit axes per second), the axes interpolated per tick and checked against the metal; reported under tick_poses")
     ap.add_argument("--torch-grid", type=int, nargs="?", const=1, default=None, metavar="MIN_DIRS",
                     help="with --torch K: plan on the torch-fit grid (wa_grid_tool_fit), whose free voxels leave the torch body at least MIN_DIRS "
                          "(default 1) of the K directions; around every weld point the voxels within --torch-keep-r2 (squared voxels) stay as "
@@ -514,6 +540,8 @@ def main():
             ap.error("--pose-paths is a pair planner of its own: not with --exact-paths, --safe-paths, --diagonal-paths or --geodesic")
     if args.torch is not None and args.fit is None and not args.retime and args.torch_grid is None and args.pose_paths is None:
         ap.error("--torch works on the samples of --fit or --retime")
+    if args.tick_poses is not None and (len(args.tick_poses) > 2 or not args.retime or args.torch is None):
+        ap.error("--tick-poses takes OMEGA and optionally H, and needs --retime and --torch K")
     if args.torch is not None and not 1 <= args.torch <= 256:
         ap.error("--torch takes 1 .. 256 directions")
     if args.diagonal_paths is not None:
@@ -719,6 +747,12 @@ def main():
                        t_torch_s=time.perf_counter() - t4)
             if args.pose_paths is not None:
                 out.update(n_no_dir=out["torch"]["n_no_dir"], n_over_turn=out["torch"]["n_over_turn"])
+            if args.tick_poses is not None:
+                t5 = time.perf_counter()
+                h = args.tick_poses[1] if len(args.tick_poses) > 1 else 8.0 * float(metal.precision)
+                out.update(tick_poses=tick_pose_stage(ctx, metal, np.ascontiguousarray(traj[ok.astype(bool)], np.float32), args.retime_limits,
+                                                      args.retime_tick, args.tick_poses[0], h, out["retime"]["duration_s"]),
+                           t_tick_poses_s=time.perf_counter() - t5)
         if both:
             q = safe_diagonal_report(grid, metal, pts, paths, args.max_span if args.shortcut else 0)
             if args.shortcut:

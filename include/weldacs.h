@@ -851,6 +851,7 @@ int wa_gtsp_seam_tour_exact(wa_ctx *ctx, const double *dist, int32_t m, int32_t 
  *    blocked_out[i] = 0 / 1, near_out[i] = near of that axis (each uint8 n, host, may be NULL).  Its summary treats the given axis as the
  *    chosen one of a single direction: n, n_outside, n_blocked_pairs = n_no_dir = n_chosen_blocked, first_chosen_blocked,
  *    n_chosen_near are filled, the other fields are 0.
+ *    (Axes at every controller TICK, interpolated and checked on the device: wa_traj_tick_axes, rules 24 - 26 at the end of this header.)
  * 9. Errors.  WA_ERR_ARG, before anything is written: a NULL required pointer (g, t, dirs / axes, tool, weights, off, sum), g and t from
  *    different contexts, K, n_beads, n_legs (< 0), a weight, dist16, r2 or near_add out of range, off that breaks rule 4, a pin outside
  *    -1 .. K-1, a direction or axis that is not finite or has zero length, a want entry or a coordinate of t that is not finite.
@@ -962,6 +963,73 @@ int wa_grid_pose_matrix(const wa_grid *g, const float *dirs, int32_t K, const wa
 int wa_grid_pose_paths(const wa_grid *g, const float *dirs, int32_t K, const wa_tool_beads *tool, int32_t max_turn, const int64_t *start_ids,
                        const int64_t *end_ids, const int32_t *pin_start, const int32_t *pin_end, int32_t n_pairs, const int64_t *off,
                        int64_t *ids_out, int32_t *dir_out, int32_t *hops_out, int32_t *len_out);
+
+/* ---- tool poses at controller ticks: smoothed axes, a turn-rate limit for the timing, one axis per tick (not in the reference) ----
+ *      wa_traj_retime gives the tip position at every controller tick, wa_traj_tool_axes one of K directions per SAMPLE.  The three
+ *      calls below join them: they spread the direction changes along the path, turn them into a per-sample speed limit for
+ *      wa_traj_retime, and give the axis at every tick, checked against the metal by rule 2.  The rules continue the numbering above;
+ *      q, U(a, b), wa_tool_beads and "blocked" are those of rules 1 and 2, Q = 2^30, ds_i, L_i and rule 6 those of the retime section.
+ *      Integers and individually rounded doubles only: the same bytes whatever computes it.
+ *      Axes travel between these calls as QUANTISED INTEGERS: q is int32, n x 3, rule 1's rint((c / len) * 16384) (api.quantise_axes);
+ *      every |q_c| <= 16384 and no triple is all zero (WA_ERR_ARG otherwise).  Floats do not round-trip: quantising q / 16384 again by
+ *      rule 1 can move a component by 1, because the length of a quantised triple is not exactly 16384.  Keep the integers.
+ * 24. wa_traj_axes_smooth.  L_i as retime rule 1, GL = its exclusive prefix sum (n entries); a total of 2^61 or more is WA_ERR_ARG.
+ *     h_q = (int64)rint(h * Q) with h finite, >= 0 and h_q <= 2^61; max_level is 0 .. 8.  Legs follow rule 4 (off[0 .. n_legs], n_legs >= 1, a
+ *     leg of at most 2^22 samples, WA_ERR_CAPACITY above); a window never crosses a leg.  The candidate axis of sample i at level
+ *     l < max_level: J = the samples j of i's leg with |GL_j - GL_i| <= (h_q >> l), a contiguous range; S = the sum of q_j over J per
+ *     component (int64).  If S = (0, 0, 0) the candidate is q_i.  Otherwise, S_c converted exactly to double,
+ *     len = sqrt((S_x*S_x + S_y*S_y) + S_z*S_z) and the candidate is (int32)rint((S_c / len) * 16384) per component.  At level max_level the
+ *     candidate is q_i itself.  A candidate is blocked by rule 2 at sample i's voxel (near is not used).  level_out[i] = the lowest l in
+ *     0 .. max_level whose candidate is not blocked, max_level if all are; q_out[i] = that level's candidate; blocked_out[i] = whether it
+ *     is blocked.  A sample's result depends on the inputs only, never on another sample's output: no rounds, no order.  g and tool
+ *     may both be NULL (one alone is WA_ERR_ARG): nothing is blocked, every level is 0, n_outside is 0.  Summary: n, n_outside,
+ *     n_level[l] = samples with level l, n_blocked and first_blocked (-1: none) over blocked_out, n_zero_sum = samples whose chosen level
+ *     had S = 0, max_turn_in / max_turn_out = the largest U between consecutive samples inside a leg before / after.  q_out (int32 n x 3),
+ *     level_out and blocked_out (uint8 n) are on the host; the last two may be NULL.  n is 1 .. 2^31.
+ * 25. wa_traj_axes_limits.  Legs play no part: the trajectory is one motion.  Per segment i: D_i = the sum over c of
+ *     (q_i,c - q_(i+1),c)^2, an exact integer <= 3 * 2^30; psi_i = sqrt((double)D_i) / 16384, the CHORD of the two unit axes -- omega caps
+ *     the rate of the chord, not of the angle: the chord understates the angle by 1.2 % at 30 degrees and by 11 % at 90.  If D_i > 0 and
+ *     L_i > 0: m_i = (ds_i * omega) / psi_i.  If D_i > 0 and L_i = 0 no speed makes room for the turn: counted in n_jump, no limit from it.
+ *     Per sample: lim_i = min(v_cap, m_(i-1), m_i, (double)v_limit_in[i]) over those that exist; f_i = the largest float <= lim_i
+ *     (convert, one step down if the float is greater); if (double)f_i < v_floor then f_i = the smallest float >= v_floor, counted in
+ *     n_floored.  v_limit_out (n floats, host) is ready to be passed to wa_traj_retime as v_limit.  WA_ERR_ARG: omega, v_cap or v_floor
+ *     not finite or <= 0, v_floor > v_cap or beyond the floats, a v_limit_in entry not finite or <= 0 (v_limit_in may be NULL).
+ *     Summary: n, n_turning (D_i > 0), n_jump, n_floored, n_limited ((double)f_i < v_cap), min_limit (the smallest f_i).
+ *     Property: with v_limit_out among the limits of wa_traj_retime, every segment with D_i > 0, L_i > 0 and neither end floored takes
+ *     T_i >= floor(psi_i / omega * Q * (1 - 2^-40)) - 1 quanta.  n is 1 .. 2^31.
+ * 26. wa_traj_tick_axes.  time_q and w_q (n int64 each, host) are what wa_traj_retime returned for the same t, acc and dec; checked:
+ *     time_q[0] = 0, non-decreasing, below 2^61; 0 <= w_q <= 2^61.  The tick set, and per tick the segment i and lambda, are exactly rule
+ *     6 (lambda = 1 where the tick is p_(i+1) exactly, 0 where it is p_i exactly); the tick position is rule 6's, the bytes of
+ *     ticks_out.  The axis: v_c = (double)q_i,c + ((double)q_(i+1),c - (double)q_i,c) * lambda; if v is all zero the axis is q_i, else v
+ *     quantised by rule 1 to qt.  *axes_out (may be NULL) is an ordinary device-resident wa_traj of n_ticks points
+ *     (float)(qt_c / 16384.0), exact in fp32, owned by the caller.  blocked_out (one byte per tick, host, may be NULL): rule 2 with qt at
+ *     the voxel of the tick POSITION (the lookup of wa_traj_clearance on the fp32 position).  g and tool may both be NULL: no check.
+ *     Summary: n_ticks, n_outside, n_blocked, first_blocked (-1: none), n_near = ticks not blocked with a near bead, max_tick_turn = the
+ *     largest U between the axes of consecutive ticks (0 with one tick).  WA_ERR_ARG as rule 7 of the retime section for n, acc, dec,
+ *     tick and the coordinates, as rule 9 for the tool and near_add.  More than 2^31 ticks: WA_ERR_CAPACITY, *axes_out = NULL and
+ *     nothing else written.
+ * Every WA_ERR_ARG is answered before anything is written.  Same bytes on every call; everything runs on the context's stream; g and
+ * t are not modified.  The scans of rule 24 live in blocks of the context's arena for the duration of the call. */
+typedef struct {
+    int64_t n, n_outside;
+    int64_t n_level[9];
+    int64_t n_blocked, first_blocked, n_zero_sum;
+    int64_t max_turn_in, max_turn_out;
+} wa_axes_smooth_summary;
+typedef struct {
+    int64_t n, n_turning, n_jump, n_floored, n_limited;
+    double min_limit;
+} wa_axes_limits_summary;
+typedef struct {
+    int64_t n_ticks, n_outside, n_blocked, first_blocked, n_near, max_tick_turn;
+} wa_tick_axes_summary;
+int wa_traj_axes_smooth(const wa_grid *g, const wa_traj *t, const int32_t *q, const wa_tool_beads *tool, const int64_t *off, int32_t n_legs,
+                        double h, int32_t max_level, int32_t *q_out, uint8_t *level_out, uint8_t *blocked_out, wa_axes_smooth_summary *sum);
+int wa_traj_axes_limits(const wa_traj *t, const int32_t *q, double omega, double v_cap, double v_floor, const float *v_limit_in,
+                        float *v_limit_out, wa_axes_limits_summary *sum);
+int wa_traj_tick_axes(const wa_grid *g, const wa_traj *t, const int32_t *q, const wa_tool_beads *tool, int32_t near_add, double acc, double dec,
+                      double tick, const int64_t *time_q, const int64_t *w_q, wa_traj **axes_out, uint8_t *blocked_out,
+                      wa_tick_axes_summary *sum);
 
 #ifdef __cplusplus
 }

@@ -85,6 +85,21 @@ class ReachSummary(C.Structure):
     _fields_ = [("n_free", C.c_int64), ("n_no_dir", C.c_int64), ("n_all_dirs", C.c_int64), ("n_blocked_pairs", C.c_int64)]
 
 
+class AxesSmoothSummary(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_outside", C.c_int64), ("n_level", C.c_int64 * 9), ("n_blocked", C.c_int64), ("first_blocked", C.c_int64),
+                ("n_zero_sum", C.c_int64), ("max_turn_in", C.c_int64), ("max_turn_out", C.c_int64)]
+
+
+class AxesLimitsSummary(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_turning", C.c_int64), ("n_jump", C.c_int64), ("n_floored", C.c_int64), ("n_limited", C.c_int64),
+                ("min_limit", C.c_double)]
+
+
+class TickAxesSummary(C.Structure):
+    _fields_ = [("n_ticks", C.c_int64), ("n_outside", C.c_int64), ("n_blocked", C.c_int64), ("first_blocked", C.c_int64),
+                ("n_near", C.c_int64), ("max_tick_turn", C.c_int64)]
+
+
 WA_PEN_MAX = 31
 
 # every symbol include/weldacs.h declares: name -> (restype, argtypes)
@@ -212,6 +227,10 @@ SYMBOLS = {
     "wa_grid_pose_fields": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, _P, _P, _I, _P, _P]),
     "wa_grid_pose_matrix": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, _P, _P, _I, _P]),
     "wa_grid_pose_paths": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "wa_traj_axes_smooth": (C.c_int, [_V, _V, _P, C.POINTER(ToolBeads), _P, _I, C.c_double, _I, _P, _P, _P, C.POINTER(AxesSmoothSummary)]),
+    "wa_traj_axes_limits": (C.c_int, [_V, _P, C.c_double, C.c_double, C.c_double, _P, _P, C.POINTER(AxesLimitsSummary)]),
+    "wa_traj_tick_axes": (C.c_int, [_V, _V, _P, C.POINTER(ToolBeads), _I, C.c_double, C.c_double, C.c_double, _P, _P, C.POINTER(_V), _P,
+                                    C.POINTER(TickAxesSummary)]),
 }
 
 _libs = {}

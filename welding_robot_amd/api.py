@@ -899,6 +899,70 @@ class Trajectory:
         self.ctx.check(self.ctx.lib.wa_traj_tool_check(grid.h, self.h, _ptr(axes), C.byref(tool), near_add, _ptr(blocked), _ptr(near), C.byref(s)))
         return blocked, near, {k: int(getattr(s, k)) for k, _ in L.ToolSummary._fields_}
 
+    def _axes(self, q):
+        q = np.ascontiguousarray(q, np.int32).reshape(-1, 3)
+        if len(q) != len(self):
+            raise ValueError("q needs one quantised axis (quantise_axes) per sample")
+        return q
+
+    def smooth_axes(self, q, h, max_level=8, grid=None, tool=None, off=None):
+        """wa_traj_axes_smooth: the quantised axes `q` (int32 n x 3, quantise_axes) averaged over windows of half-width `h` along the path,
+        per sample the widest window (h, h/2, ... down to the sample's own axis at level max_level) whose average keeps the beads of
+        `tool` clear of `grid`'s metal; `off` splits the samples into legs that no window crosses.  grid and tool come together or not
+        at all.  Returns dict(q int32[n, 3], level uint8[n], blocked uint8[n], summary)."""
+        n = len(self)
+        q = self._axes(q)
+        if tool is not None:
+            tool = tool if isinstance(tool, L.ToolBeads) else torch_tool(*tool)
+        off = np.ascontiguousarray([0, n] if off is None else off, np.int64).reshape(-1)
+        q_out, level, blocked = np.empty((n, 3), np.int32), np.empty(n, np.uint8), np.empty(n, np.uint8)
+        s = L.AxesSmoothSummary()
+        self.ctx.check(self.ctx.lib.wa_traj_axes_smooth(grid.h if grid is not None else None, self.h, _ptr(q), C.byref(tool) if tool is not None else None,
+                                                        _ptr(off), len(off) - 1, C.c_double(h), max_level, _ptr(q_out), _ptr(level), _ptr(blocked),
+                                                        C.byref(s)))
+        summary = {k: (list(getattr(s, k)) if k == "n_level" else int(getattr(s, k))) for k, _ in L.AxesSmoothSummary._fields_}
+        return dict(q=q_out, level=level, blocked=blocked, summary=summary)
+
+    def axis_limits(self, q, omega, v_cap, v_floor, v_limit=None):
+        """wa_traj_axes_limits: the per-sample speed limit under which the axes `q` turn at no more than `omega` (chord of the unit axes
+        per second), capped at v_cap, combined with `v_limit` and raised to v_floor where it falls below.  Returns (float32[n] for
+        retime(v_limit=...), summary)."""
+        n = len(self)
+        q = self._axes(q)
+        if v_limit is not None:
+            v_limit = np.ascontiguousarray(v_limit, np.float32).reshape(-1)
+            if len(v_limit) != n:
+                raise ValueError("v_limit needs one entry per sample")
+        out = np.empty(n, np.float32)
+        s = L.AxesLimitsSummary()
+        self.ctx.check(self.ctx.lib.wa_traj_axes_limits(self.h, _ptr(q), C.c_double(omega), C.c_double(v_cap), C.c_double(v_floor), _ptr(v_limit),
+                                                        _ptr(out), C.byref(s)))
+        return out, {k: (float(s.min_limit) if k == "min_limit" else int(getattr(s, k))) for k, _ in L.AxesLimitsSummary._fields_}
+
+    def tick_axes(self, q, time_q, w_q, acc, dec, tick, grid=None, tool=None, near_add=-1, axes=True, blocked=True):
+        """wa_traj_tick_axes: the axis at every controller tick of retime(...)'s result (time_q, w_q, the same acc, dec and tick), the
+        sample axes `q` interpolated along each segment like the position, each checked against `grid` with `tool` at the tick's
+        position.  Returns (Trajectory of n_ticks unit axes or None, blocked uint8[n_ticks] or None, summary)."""
+        n = len(self)
+        q = self._axes(q)
+        time_q = np.ascontiguousarray(time_q, np.int64).reshape(-1)
+        w_q = np.ascontiguousarray(w_q, np.int64).reshape(-1)
+        if len(time_q) != n or len(w_q) != n:
+            raise ValueError("time_q and w_q need one entry per sample")
+        if tool is not None:
+            tool = tool if isinstance(tool, L.ToolBeads) else torch_tool(*tool)
+        out = None
+        if blocked and n >= 2:
+            tq = int(np.rint(np.float64(tick) * RETIME_Q)) if np.isfinite(tick) else 0
+            n_ticks = int(time_q[-1]) // tq + 1 + (1 if int(time_q[-1]) % tq else 0) if tq >= 1 and time_q[-1] >= 0 else 0
+            out = np.empty(n_ticks if n_ticks <= 1 << 31 else 0, np.uint8)
+        th, s = C.c_void_p(), L.TickAxesSummary()
+        self.ctx.check(self.ctx.lib.wa_traj_tick_axes(grid.h if grid is not None else None, self.h, _ptr(q), C.byref(tool) if tool is not None else None,
+                                                      near_add, C.c_double(acc), C.c_double(dec), C.c_double(tick), _ptr(time_q), _ptr(w_q),
+                                                      C.byref(th) if axes else None, _ptr(out), C.byref(s)))
+        summary = {k: int(getattr(s, k)) for k, _ in L.TickAxesSummary._fields_}
+        return Trajectory(self.ctx, th) if th.value else None, out, summary
+
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.wa_traj_destroy(self.h)
@@ -1047,6 +1111,19 @@ def torch_tool(dist16, r2):
     for j in range(len(r2)):
         t.dist16[j], t.r2[j] = int(dist16[j]), int(r2[j])
     return t
+
+
+def quantise_axes(dirs):
+    """rule 1 of the tool section in numpy: float triples (tip -> body) to the integers the axis calls exchange,
+    q_c = rint((c / len) * 16384) with len = sqrt((x*x + y*y) + z*z) in float64 on the fp32 components.  Keep the integers: quantising
+    q / 16384 a second time can move a component by 1."""
+    d = np.asarray(dirs, np.float32).reshape(-1, 3).astype(np.float64)
+    if not np.isfinite(d).all():
+        raise ValueError("a direction is not finite")
+    ln = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+    if not (ln > 0).all():
+        raise ValueError("a direction has zero length")
+    return np.rint((d / ln[:, None]) * 16384.0).astype(np.int32)
 
 
 def torch_cone(K, half_angle, axis=(0.0, 0.0, 1.0)):

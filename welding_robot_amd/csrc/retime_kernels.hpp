@@ -324,6 +324,63 @@ __global__ __launch_bounds__(256) void k_rt_times(const float *__restrict__ xyz,
     }
 }
 
+// Rule 6 for one tau: the segment i (the largest index in [lo, hi] with time_q[i] <= tau; the caller brackets it, [0, n - 2] always
+// does), lambda on it, and the two cases in which the output is a sample as it stands.  Shared by k_rt_ticks and the tick-axis
+// kernel (ticks_kernels.hpp): one definition of where a tick lies.
+struct RtTick {
+    long long i;
+    double lam;      // 0 in the exact cases
+    int32_t exact;   // 0: interpolate with lam; 1: the tick is p_(i+1) (lambda = 1); 2: it is p_i (lambda = 0)
+};
+__device__ __forceinline__ RtTick rt_tick_locate(const float *__restrict__ xyz, double acc, double dec, const long long *__restrict__ B,
+                                                 const long long *__restrict__ time_q, long long tau, long long lo, long long hi)
+{
+    while (lo < hi) {
+        const long long mid = lo + ((hi - lo + 1) >> 1);
+        if (time_q[mid] <= tau) lo = mid; else hi = mid - 1;
+    }
+    RtTick r;
+    r.i = lo;
+    r.lam = 0.0;
+    r.exact = 0;
+    const long long i = lo;
+    const double ds = rt_seg_len(xyz, i);
+    if (tau >= time_q[i + 1]) {
+        r.exact = 1;
+    } else if (rt_quanta(ds) == 0) {
+        r.exact = 2;
+    } else {
+        const double e = (double)(tau - time_q[i]) / WA_RT_Q;
+        const long long bi = B[i], bn = B[i + 1];
+        const double vi = rt_speed(bi), vs = vi + rt_speed(bn);
+        double s;
+        if (vs == 0.0) {
+            const double wp = __ddiv_rn(((2.0 * ds) * acc) * dec, acc + dec), rr = __dsqrt_rn(wp);
+            const double t_up = __ddiv_rn(rr, acc), dt = t_up + __ddiv_rn(rr, dec);
+            if (e <= t_up) {
+                s = ((0.5 * acc) * e) * e;
+            } else {
+                const double rem = dt - e;
+                s = ds - ((0.5 * dec) * rem) * rem;
+            }
+        } else {
+            const double al = __ddiv_rn((double)(bn - bi) / WA_RT_Q, 2.0 * ds);
+            s = (vi * e) + ((0.5 * al) * e) * e;
+        }
+        double lam = __ddiv_rn(s, ds);
+        r.lam = lam < 0.0 ? 0.0 : (lam > 1.0 ? 1.0 : lam);
+    }
+    return r;
+}
+// the position of a located tick, component c
+__device__ __forceinline__ float rt_tick_pos(const float *__restrict__ xyz, const RtTick &r, int c)
+{
+    const float *a = xyz + 3 * r.i, *b = a + 3;
+    if (r.exact) return r.exact == 1 ? b[c] : a[c];
+    const double pa = (double)a[c], pb = (double)b[c];
+    return (float)(pa + (pb - pa) * r.lam);
+}
+
 // Rule 6.  Tick k < n_full sits at k * tick_q, tick n_full (when the duration is no multiple of tick_q) at the duration.  The block's
 // 256 positions go through LDS so that consecutive lanes store consecutive floats.
 __global__ __launch_bounds__(256) void k_rt_ticks(const float *__restrict__ xyz, long long n, double acc, double dec,
@@ -333,47 +390,9 @@ __global__ __launch_bounds__(256) void k_rt_ticks(const float *__restrict__ xyz,
     __shared__ float stage[256 * 3];
     const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n_ticks) {
-        const long long total = time_q[n - 1];
-        const long long tau = k < n_full ? k * tick_q : total;
-        long long lo = 0, hi = n - 2;   // the largest i in [0, n - 2] with time_q[i] <= tau (time_q[0] = 0)
-        while (lo < hi) {
-            const long long mid = lo + ((hi - lo + 1) >> 1);
-            if (time_q[mid] <= tau) lo = mid; else hi = mid - 1;
-        }
-        const long long i = lo;
-        const float *a = xyz + 3 * i, *b = a + 3;
-        const double ds = rt_seg_len(xyz, i);
-        double lam = 0.0;
-        const float *exact = nullptr;   // the output is this point as it stands
-        if (tau >= time_q[i + 1]) {
-            exact = b;
-        } else if (rt_quanta(ds) == 0) {
-            exact = a;
-        } else {
-            const double e = (double)(tau - time_q[i]) / WA_RT_Q;
-            const long long bi = B[i], bn = B[i + 1];
-            const double vi = rt_speed(bi), vs = vi + rt_speed(bn);
-            double s;
-            if (vs == 0.0) {
-                const double wp = __ddiv_rn(((2.0 * ds) * acc) * dec, acc + dec), r = __dsqrt_rn(wp);
-                const double t_up = __ddiv_rn(r, acc), dt = t_up + __ddiv_rn(r, dec);
-                if (e <= t_up) {
-                    s = ((0.5 * acc) * e) * e;
-                } else {
-                    const double rem = dt - e;
-                    s = ds - ((0.5 * dec) * rem) * rem;
-                }
-            } else {
-                const double al = __ddiv_rn((double)(bn - bi) / WA_RT_Q, 2.0 * ds);
-                s = (vi * e) + ((0.5 * al) * e) * e;
-            }
-            lam = __ddiv_rn(s, ds);
-            lam = lam < 0.0 ? 0.0 : (lam > 1.0 ? 1.0 : lam);
-        }
-        for (int c = 0; c < 3; c++) {
-            const double pa = (double)a[c], pb = (double)b[c];
-            stage[3 * threadIdx.x + c] = exact ? exact[c] : (float)(pa + (pb - pa) * lam);
-        }
+        const long long tau = k < n_full ? k * tick_q : time_q[n - 1];
+        const RtTick r = rt_tick_locate(xyz, acc, dec, B, time_q, tau, 0, n - 2);
+        for (int c = 0; c < 3; c++) stage[3 * threadIdx.x + c] = rt_tick_pos(xyz, r, c);
     }
     __syncthreads();
     const long long first = (long long)blockIdx.x * blockDim.x * 3, end = n_ticks * 3;
