@@ -110,17 +110,28 @@ def plan_exact(grid, point_ids, rank=0, world=1, shortcut=0):
     return cost, paths, len(mine)
 
 
-def plan_pose(grid, point_ids, dirs, tool, max_turn, rank=0, world=1, shortcut=0):
+def plan_pose(grid, point_ids, dirs, tool, max_turn, rank=0, world=1, shortcut=0, pose_shortcut=False):
     """--pose-paths MAX_TURN: the pair paths from the exact search over (voxel, torch direction) (wa_grid_pose_paths): every node has a
     direction in which the torch body clears the metal, and from node to node the torch turns by at most MAX_TURN.  Costs and return
-    values as plan_exact; the directions per node are left in plan_pose.last_dirs.  A shortened path (shortcut) leaves the planned
-    voxels, so the guarantee holds for the lattice path only."""
+    values as plan_exact; the directions per node are left in plan_pose.last_dirs.  A path shortened by line of sight (shortcut alone,
+    wa_grid_path_shortcut) leaves the planned voxels, so the guarantee then holds for the lattice path only.  With pose_shortcut the
+    waypoints and the costs come from wa_grid_pose_shortcut instead: a stretch is straightened only where one of its two end directions
+    stays open in every voxel the straight segment touches, the turns at the waypoints keep MAX_TURN, and a hop that cannot be held
+    stays the lattice step it was.  Its summary, its total length and the total of the plain shortcut of the same paths (this rank's
+    pairs) are left in plan_pose.last_pose_shortcut."""
     P = len(point_ids)
     pairs = [(i, j) for i in range(P) for j in range(i + 1, P)]
     mine = [k for k in range(len(pairs)) if k % world == rank]
     hops, ids_all, ks_all = grid.pose_paths(dirs, tool, max_turn, [point_ids[pairs[k][0]] for k in mine], [point_ids[pairs[k][1]] for k in mine])
     ids_all = [np.zeros(0, np.int64) if p is None else p for p in ids_all]
     wps, lengths = api.shortcut_paths(grid, ids_all, shortcut or 1)
+    plan_pose.last_pose_shortcut = None
+    if pose_shortcut:
+        plain_total = float(lengths.sum())
+        ks_some = [np.zeros(0, np.int32) if k is None else k for k in ks_all]
+        wps, _, _, lengths, summary = api.pose_shortcut_paths(grid, dirs, tool, max_turn, ids_all, ks_some, shortcut)
+        plan_pose.last_pose_shortcut = dict({k: summary[k] for k in ("n_waypoints", "n_held_start", "n_held_end", "n_unheld", "max_hold_turn")},
+                                            length_total=float(lengths.sum()), plain_length_total=plain_total)
     cost = np.zeros((P, P), np.float64)
     paths = {}
     plan.last_slots, plan.last_create_s, plan.last_batch_s, plan.last_shortcut, plan_pose.last_dirs = 0, 0.0, [], {}, {}
@@ -521,7 +532,11 @@ def main():
                          "node of a path has one of the K directions open, and from node to node the torch turns by at most MAX_TURN (the "
                          "measure U of wa_traj_tool_axes, 0 .. 3145728; -1: no limit).  Pairs without such a path are reported and left out, "
                          "as with --geodesic; --torch then runs on the finished trajectory with the same limit and the line carries its "
-                         "n_no_dir and n_over_turn.  --shortcut leaves the planned voxels and so drops the guarantee")
+                         "n_no_dir and n_over_turn.  --shortcut alone leaves the planned voxels and so drops the guarantee; add --pose-shortcut")
+    ap.add_argument("--pose-shortcut", action="store_true",
+                    help="needs --pose-paths and --shortcut: the waypoints and costs of the pair paths come from wa_grid_pose_shortcut, which "
+                         "straightens a stretch only where a planned direction stays open along the whole segment and keeps MAX_TURN at the "
+                         "waypoints; pose_paths.shortcut reports the held and unheld segments and the length beside the plain shortcut's")
     ap.add_argument("--torch-keep-r2", type=int, default=16, metavar="R2",
                     help="--torch-grid: the squared radius in voxels of the bubble around every weld point inside which the grid is kept (default 16)")
     args = ap.parse_args()
@@ -538,6 +553,8 @@ def main():
             ap.error("--pose-paths takes -1 or 0 .. 3145728")
         if args.exact_paths or args.safe_paths or args.diagonal_paths is not None or args.geodesic:
             ap.error("--pose-paths is a pair planner of its own: not with --exact-paths, --safe-paths, --diagonal-paths or --geodesic")
+    if args.pose_shortcut and (args.pose_paths is None or not args.shortcut):
+        ap.error("--pose-shortcut needs --pose-paths and --shortcut")
     if args.torch is not None and args.fit is None and not args.retime and args.torch_grid is None and args.pose_paths is None:
         ap.error("--torch works on the samples of --fit or --retime")
     if args.tick_poses is not None and (len(args.tick_poses) > 2 or not args.retime or args.torch is None):
@@ -623,7 +640,8 @@ def main():
     t0 = time.perf_counter()
     if args.pose_paths is not None:
         pose_tool, pose_dirs, _ = torch_tool_and_cone(metal, args.torch)
-        cost, paths, n_mine = plan_pose(grid, pts, pose_dirs, pose_tool, args.pose_paths, rank, world, shortcut=args.max_span if args.shortcut else 0)
+        cost, paths, n_mine = plan_pose(grid, pts, pose_dirs, pose_tool, args.pose_paths, rank, world, shortcut=args.max_span if args.shortcut else 0,
+                                        pose_shortcut=args.pose_shortcut)
     elif both:
         cost, paths, n_mine = plan_safe_diagonal(grid, pts, args.safe_paths, args.diagonal_paths, args.safe_gain, rank, world,
                                                  shortcut=args.max_span if args.shortcut else 0, extra_pen=extra_pen)
@@ -666,6 +684,8 @@ def main():
         gone = [[i, j] for i in range(args.points) for j in range(i + 1, args.points) if not np.isfinite(cost[i, j])]
         out.update(pose_paths=dict(max_turn=args.pose_paths, K=args.torch, unreachable_pairs=gone, reachable_pairs=out["pairs"] - len(gone),
                                    nodes_total=int(sum(len(p) for p in paths.values()))))
+        if plan_pose.last_pose_shortcut is not None:
+            out["pose_paths"].update(shortcut=plan_pose.last_pose_shortcut)
     if torch_grid is not None and rank == 0:
         out.update(torch_grid=dict(torch_grid, paths=torch_grid_report(base, count, paths, paths_without, args.max_span if args.shortcut else 0)))
     if rank == 0 and args.geodesic:

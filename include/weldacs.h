@@ -1031,6 +1031,53 @@ int wa_traj_tick_axes(const wa_grid *g, const wa_traj *t, const int32_t *q, cons
                       double tick, const int64_t *time_q, const int64_t *w_q, wa_traj **axes_out, uint8_t *blocked_out,
                       wa_tick_axes_summary *sum);
 
+/* ---- pose-aware path shortening: any-angle shortcuts of (voxel, direction) paths that keep the torch clear (not in the reference) ----
+ *      wa_grid_pose_paths returns a staircase of 6-neighbour hops with one open direction per node; wa_grid_path_shortcut straightens a
+ *      staircase but knows the occupancy only.  This call shortens where the torch body stays clear along the WHOLE straight segment
+ *      under a direction the plan already chose, keeps the turn limit at the waypoints and returns the direction held on every segment.
+ *      The rules continue the numbering above; dirs, q, U(a, b), wa_tool_beads, open(v, k), adj(k, k') and max_turn are those of rules 1,
+ *      2, 10 and 17, K = 1 .. WA_TORCH_MAX_DIRS.  The supercover is the one of wa_traj_clearance and wa_grid_path_shortcut: tied axes
+ *      stepped together, the full product set at a tie, voxel a itself included.  Integers only, except the length.
+ * 27. Input.  n_paths paths back to back as for wa_grid_path_shortcut: path p = the nodes off[p] .. off[p + 1] - 1 (n_paths + 1 offsets,
+ *     off[0] = 0, non-decreasing, empty paths allowed), node i has voxel v_i = ids[i] and direction index k_i = ks[i] in 0 .. K - 1.  The
+ *     paths need not come from wa_grid_pose_paths and are not checked for being pose paths.  For nodes a < m of one path:
+ *     cover_open(a, m, k) holds iff open(w, k) for EVERY voxel w of the supercover between v_a and v_m (which includes that w is free);
+ *     ok(a, m) holds iff adj(k_a, k_m) and (cover_open(a, m, k_a) or cover_open(a, m, k_m)).
+ * 28. Greedy rule: that of wa_grid_path_shortcut with ok in place of visible.  Indices are relative to the path, L its node count, w_0 = 0.
+ *     From an anchor a < L - 1, next(a) is the largest j in [a + 1, min(a + max_span, L - 1)] such that ok(a, m) holds for EVERY m in
+ *     (a, j] (prefix form); if there is none, next(a) = a + 1.  Stop when L - 1 is reached: the first and last nodes are always kept.
+ *     The hold of the segment a -> j = next(a): if ok(a, j) does not hold (only possible for the fallback j = a + 1) the hold is -1, and
+ *     the hop carries whatever guarantee the input had -- for a path of wa_grid_pose_paths the lattice step of rule 18.  Otherwise the
+ *     hold is k_a if cover_open(a, j, k_a): the torch travels with the anchor's direction and turns on arrival; else it is k_j: the
+ *     torch turns on departure.  A segment with a hold >= 0 is HELD.
+ *     Consequences.  Along a held segment one direction is open in every voxel that the straight line between the two voxel centres
+ *     touches.  Every turn at a waypoint of a held segment is between adjacent directions, both open at the waypoint's voxel (k_a -> k_j
+ *     at j, or k_a -> k_j at a: both voxels belong to the cover); up to two such turns meet at one waypoint, the arrival of one segment
+ *     and the departure of the next.
+ *     Identities.  (a) With a tool of one bead with dist16 = 0 and r2 = 0 and max_turn = -1, open(v, k) = v is free, so wp_idx, wp_count
+ *     and length_out are the bytes of wa_grid_path_shortcut whatever ks holds.  (b) max_span = 1 makes every node a waypoint.  (c) With
+ *     max_turn = 0 and pairwise distinct quantised directions a held segment joins two nodes of EQUAL direction.
+ * 29. Outputs.  wp_idx[off[p] .. off[p] + wp_count[p]) = the waypoints of path p as indices INTO path p; hold_out (int32, may be NULL)
+ *     uses the same ranges: entry t is the hold of the segment that leaves waypoint t, the last waypoint's entry is -1.  Later entries of
+ *     both ranges stay untouched.  length_out (may be NULL) is exactly wa_grid_path_shortcut's float64 length of the waypoints.  Summary
+ *     (required): n_paths, n_nodes = off[n_paths], n_waypoints = the sum of wp_count; the segments counted by their hold -- n_held_start
+ *     (the hold is k_a, also when k_j equals it), n_held_end (the hold is k_j and differs from k_a), n_unheld (-1); max_hold_turn = the
+ *     largest U(q_h, q_h') over the holds h, h' of two CONSECUTIVE segments of one path that are both held, 0 without such a pair.
+ *     WA_ERR_ARG, before anything is written: the errors of rule 16 for g, dirs, K and the tool; max_turn outside -1 .. 3 * 2^20; a NULL
+ *     ids, ks, off, wp_idx, wp_count or sum; n_paths < 0; max_span outside 1 .. 4096; off[0] != 0 or decreasing offsets; an id outside the
+ *     grid; a ks entry outside 0 .. K - 1; a path of 2^31 nodes or more; more than 2^33 nodes.  WA_ERR_ALLOC when the device blocks do
+ *     not fit.
+ * Same bytes on every call; everything runs on the context's stream; g is not modified.  The masks are recomputed by every call, in a
+ * block of the context's arena (W * 8 * n bytes, rule 16); nothing is cached with the grid. */
+typedef struct {
+    int64_t n_paths, n_nodes, n_waypoints;
+    int64_t n_held_start, n_held_end, n_unheld;  /* segments by rule 28's hold */
+    int64_t max_hold_turn;                       /* largest U between the holds of consecutive held segments of one path; 0 without one */
+} wa_pose_shortcut_summary;
+int wa_grid_pose_shortcut(const wa_grid *g, const float *dirs, int32_t K, const wa_tool_beads *tool, int32_t max_turn,
+                          const int64_t *ids, const int32_t *ks, const int64_t *off, int32_t n_paths, int32_t max_span,
+                          int64_t *wp_idx, int32_t *hold_out, int32_t *wp_count, double *length_out, wa_pose_shortcut_summary *sum);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,11 @@ class AxesLimitsSummary(C.Structure):
                 ("min_limit", C.c_double)]
 
 
+class PoseShortcutSummary(C.Structure):
+    _fields_ = [("n_paths", C.c_int64), ("n_nodes", C.c_int64), ("n_waypoints", C.c_int64), ("n_held_start", C.c_int64),
+                ("n_held_end", C.c_int64), ("n_unheld", C.c_int64), ("max_hold_turn", C.c_int64)]
+
+
 class TickAxesSummary(C.Structure):
     _fields_ = [("n_ticks", C.c_int64), ("n_outside", C.c_int64), ("n_blocked", C.c_int64), ("first_blocked", C.c_int64),
                 ("n_near", C.c_int64), ("max_tick_turn", C.c_int64)]
@@ -227,6 +232,7 @@ SYMBOLS = {
     "wa_grid_pose_fields": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, _P, _P, _I, _P, _P]),
     "wa_grid_pose_matrix": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, _P, _P, _I, _P]),
     "wa_grid_pose_paths": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "wa_grid_pose_shortcut": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, C.POINTER(PoseShortcutSummary)]),
     "wa_traj_axes_smooth": (C.c_int, [_V, _V, _P, C.POINTER(ToolBeads), _P, _I, C.c_double, _I, _P, _P, _P, C.POINTER(AxesSmoothSummary)]),
     "wa_traj_axes_limits": (C.c_int, [_V, _P, C.c_double, C.c_double, C.c_double, _P, _P, C.POINTER(AxesLimitsSummary)]),
     "wa_traj_tick_axes": (C.c_int, [_V, _V, _P, C.POINTER(ToolBeads), _I, C.c_double, C.c_double, C.c_double, _P, _P, C.POINTER(_V), _P,

@@ -405,6 +405,35 @@ def shortcut_paths(grid, paths, max_span=128):
     return [p[wp[off[k]:off[k] + cnt[k]]] for k, p in enumerate(paths)], lengths
 
 
+def pose_shortcut_paths(grid, dirs, tool, max_turn, paths, ks, max_span=128):
+    """wa_grid_pose_shortcut of a batch of (voxel, direction) paths in one call -- `paths` node-id arrays, `ks` one direction index per
+    node, as Grid.pose_paths returns them.  A stretch of a path is replaced by a straight segment only where the two directions are
+    within `max_turn` of each other and one of them is open in every voxel the segment touches.  Returns ([waypoint node ids per path],
+    [direction index of the path at each waypoint], [hold per segment: the direction that is open along it, -1 for a hop that is not
+    held; one entry fewer than waypoints], float64 lengths, summary dict)."""
+    dirs, K, tool = grid._torch_args(dirs, tool)
+    paths = [np.ascontiguousarray(p, np.int64).reshape(-1) for p in paths]
+    ks = [np.ascontiguousarray(k, np.int32).reshape(-1) for k in ks]
+    assert len(paths) == len(ks) and all(len(p) == len(k) for p, k in zip(paths, ks)), "one direction index per node"
+    ids = np.concatenate(paths) if paths else np.zeros(0, np.int64)
+    kk = np.concatenate(ks) if ks else np.zeros(0, np.int32)
+    off = np.concatenate([[0], np.cumsum([len(p) for p in paths])]).astype(np.int64)
+    wp = np.empty(max(len(ids), 1), np.int64)
+    hold = np.empty(max(len(ids), 1), np.int32)
+    cnt = np.empty(max(len(paths), 1), np.int32)
+    lengths = np.empty(len(paths), np.float64)
+    s = L.PoseShortcutSummary()
+    pad = np.zeros(1, np.int64)
+    ctx = grid.ctx
+    ctx.check(ctx.lib.wa_grid_pose_shortcut(grid.h, _ptr(dirs), K, C.byref(tool), int(max_turn), _ptr(ids if len(ids) else pad),
+                                            _ptr(kk if len(kk) else np.zeros(1, np.int32)), _ptr(off), len(paths), int(max_span), _ptr(wp),
+                                            _ptr(hold), _ptr(cnt), _ptr(lengths) if len(paths) else None, C.byref(s)))
+    idx = [wp[off[k]:off[k] + cnt[k]] for k in range(len(paths))]
+    return ([p[i] for p, i in zip(paths, idx)], [k[i] for k, i in zip(ks, idx)],
+            [hold[off[k]:off[k] + max(cnt[k] - 1, 0)].copy() for k in range(len(paths))], lengths,
+            {k: int(getattr(s, k)) for k, _ in L.PoseShortcutSummary._fields_})
+
+
 def _paths_two_calls(grid, fn, lead, starts, ends, n_counts, lengths):
     """The protocol of the _paths calls, fn(grid, *lead, starts, ends, n, off, ids, *counts) with n_counts int32 arrays of per-pair counts
     (the first is negative where there is no path): the first call, with empty ranges, returns the counts (WA_ERR_CAPACITY is its

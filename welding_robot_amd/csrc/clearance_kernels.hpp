@@ -227,12 +227,15 @@ __global__ __launch_bounds__(256) void k_clr_samples(const float *__restrict__ x
     }
 }
 
-// Does the 3-D supercover between voxels a and b meet an occupied voxel of free_ (1 = free)?  Axis c with d_c != 0 changes voxel at
-// t = (2m + 1) / (2 |d_c|), m = 0 .. |d_c| - 1; at such a t that axis holds both voxels around the boundary.  The walk visits the
-// events in order (compared by cross-multiplying), steps the axes tied at an event together and tests every voxel of the product of
-// the axes' sets there (up to 8 around a shared corner); with no event the cover is voxel a.  Returns at the first occupied voxel.
-// Shared by wa_traj_clearance (k_clr_segments) and wa_grid_path_shortcut (k_sc_reach): one definition of the segment test.
-__device__ inline bool clr_cover_hits(long long a, long long b, WaDims d, const uint8_t *__restrict__ free_)
+// The event walk over the 3-D supercover between voxels a and b.  Axis c with d_c != 0 changes voxel at t = (2m + 1) / (2 |d_c|),
+// m = 0 .. |d_c| - 1; at such a t that axis holds both voxels around the boundary.  The walk visits the events in order (compared by
+// cross-multiplying), steps the axes tied at an event together and visits every voxel of the product of the axes' sets there (up to 8
+// around a shared corner, the one the walk stands on among them); with no event the cover is voxel a.  visit(id) is called with the
+// raster id of each voxel, voxel a first, and returns true to end the walk; every id lies in the box spanned by a and b.
+// The one definition of the cover: wa_traj_clearance (k_clr_segments), wa_grid_path_shortcut (k_sc_reach) and wa_grid_pose_shortcut
+// (k_psc_reach) all walk it.
+template <class Visit>
+__device__ __forceinline__ void clr_cover_visit(long long a, long long b, WaDims d, Visit &&visit)
 {
     int32_t cur[3] = {(int32_t)(a % d.nx), (int32_t)((a / d.nx) % d.ny), (int32_t)(a / d.nxy)};
     const int32_t end[3] = {(int32_t)(b % d.nx), (int32_t)((b / d.nx) % d.ny), (int32_t)(b / d.nxy)};
@@ -243,8 +246,8 @@ __device__ inline bool clr_cover_hits(long long a, long long b, WaDims d, const 
         D[c] = dd > 0 ? dd : -dd;
         m[c] = 0;
     }
-    bool hit = !free_[a];
-    while (!hit) {
+    bool stop = visit((int64_t)a);
+    while (!stop) {
         // the earliest pending event: t_c = (2 m_c + 1) / (2 D_c)
         int best = -1;
         for (int c = 0; c < 3; c++) {
@@ -255,14 +258,21 @@ __device__ inline bool clr_cover_hits(long long a, long long b, WaDims d, const 
         bool tie[3];
         for (int c = 0; c < 3; c++)
             tie[c] = m[c] < D[c] && (int64_t)(2 * m[c] + 1) * D[best] == (int64_t)(2 * m[best] + 1) * D[c];
-        for (int q = 0; q < 8 && !hit; q++) {
+        for (int q = 0; q < 8 && !stop; q++) {
             if (((q & 1) && !tie[0]) || ((q & 2) && !tie[1]) || ((q & 4) && !tie[2])) continue;
             const int32_t x = cur[0] + ((q & 1) ? s[0] : 0), y = cur[1] + ((q & 2) ? s[1] : 0), z = cur[2] + ((q & 4) ? s[2] : 0);
-            hit = !free_[(int64_t)z * d.nxy + (int64_t)y * d.nx + x];
+            stop = visit((int64_t)z * d.nxy + (int64_t)y * d.nx + x);
         }
         for (int c = 0; c < 3; c++)
             if (tie[c]) { cur[c] += s[c]; m[c]++; }
     }
+}
+
+// Does the supercover between voxels a and b meet an occupied voxel of free_ (1 = free)?  Returns at the first occupied voxel.
+__device__ inline bool clr_cover_hits(long long a, long long b, WaDims d, const uint8_t *__restrict__ free_)
+{
+    bool hit = false;
+    clr_cover_visit(a, b, d, [&](int64_t v) { return hit = !free_[v]; });
     return hit;
 }
 
