@@ -110,7 +110,21 @@ def plan_exact(grid, point_ids, rank=0, world=1, shortcut=0):
     return cost, paths, len(mine)
 
 
-def plan_pose(grid, point_ids, dirs, tool, max_turn, rank=0, world=1, shortcut=0, pose_shortcut=False):
+def turn_totals(dirs, ids_all, ks_all):
+    """over all pair paths: the hops, the changes of direction and the sum of the turn measure U over the steps"""
+    q = api.quantise_axes(dirs).astype(np.int64)
+    hops = changes = turn = 0
+    for ids, ks in zip(ids_all, ks_all):
+        if ks is None or len(ks) < 2:
+            continue
+        d = q[ks[:-1]] - q[ks[1:]]
+        hops += len(ids) - 1
+        changes += int((ks[:-1] != ks[1:]).sum())
+        turn += int(((d * d).sum(1) >> 10).sum())
+    return dict(hops=hops, direction_changes=changes, turn_sum=turn)
+
+
+def plan_pose(grid, point_ids, dirs, tool, max_turn, rank=0, world=1, shortcut=0, pose_shortcut=False, costs=None):
     """--pose-paths MAX_TURN: the pair paths from the exact search over (voxel, torch direction) (wa_grid_pose_paths): every node has a
     direction in which the torch body clears the metal, and from node to node the torch turns by at most MAX_TURN.  Costs and return
     values as plan_exact; the directions per node are left in plan_pose.last_dirs.  A path shortened by line of sight (shortcut alone,
@@ -118,11 +132,22 @@ def plan_pose(grid, point_ids, dirs, tool, max_turn, rank=0, world=1, shortcut=0
     waypoints and the costs come from wa_grid_pose_shortcut instead: a stretch is straightened only where one of its two end directions
     stays open in every voxel the straight segment touches, the turns at the waypoints keep MAX_TURN, and a hop that cannot be held
     stays the lattice step it was.  Its summary, its total length and the total of the plain shortcut of the same paths (this rank's
-    pairs) are left in plan_pose.last_pose_shortcut."""
+    pairs) are left in plan_pose.last_pose_shortcut.
+    costs (--pose-turn-costs, an api.pose_costs): the pair paths come from wa_grid_pose_weighted_paths instead, which charges every
+    step its turn and the voxel it enters; the pair costs stay lengths.  plan_pose.last_totals holds turn_totals per planner (this
+    rank's pairs): of wa_grid_pose_paths always, of the weighted planner beside it when it is used."""
     P = len(point_ids)
     pairs = [(i, j) for i in range(P) for j in range(i + 1, P)]
     mine = [k for k in range(len(pairs)) if k % world == rank]
-    hops, ids_all, ks_all = grid.pose_paths(dirs, tool, max_turn, [point_ids[pairs[k][0]] for k in mine], [point_ids[pairs[k][1]] for k in mine])
+    starts, ends = [point_ids[pairs[k][0]] for k in mine], [point_ids[pairs[k][1]] for k in mine]
+    t0 = time.perf_counter()
+    hops, ids_all, ks_all = grid.pose_paths(dirs, tool, max_turn, starts, ends)
+    plan_pose.last_totals = dict(pose_paths=dict(turn_totals(dirs, ids_all, ks_all), t_s=time.perf_counter() - t0))
+    if costs is not None:
+        t0 = time.perf_counter()
+        hops, ids_all, ks_all = grid.pose_weighted_paths(dirs, tool, max_turn, costs, starts, ends)
+        plan_pose.last_totals.update(pose_weighted_paths=dict(turn_totals(dirs, ids_all, ks_all), t_s=time.perf_counter() - t0,
+                                                              cost_total=int(hops[hops >= 0].sum())))
     ids_all = [np.zeros(0, np.int64) if p is None else p for p in ids_all]
     wps, lengths = api.shortcut_paths(grid, ids_all, shortcut or 1)
     plan_pose.last_pose_shortcut = None
@@ -533,6 +558,12 @@ def main():
                          "measure U of wa_traj_tool_axes, 0 .. 3145728; -1: no limit).  Pairs without such a path are reported and left out, "
                          "as with --geodesic; --torch then runs on the finished trajectory with the same limit and the line carries its "
                          "n_no_dir and n_over_turn.  --shortcut alone leaves the planned voxels and so drops the guarantee; add --pose-shortcut")
+    ap.add_argument("--pose-turn-costs", nargs=2, default=None, metavar=("HOP", "U1=C1[,U2=C2...]"),
+                    help="needs --pose-paths: the pair paths come from wa_grid_pose_weighted_paths -- a step costs HOP (1 .. 8), plus C1 when "
+                         "it turns the torch by more than U1, C2 by more than U2, ... (at most 4 ascending bands, costs non-decreasing, at most "
+                         "15); the pair costs stay what they are.  With it --safe-paths G may be combined with --pose-paths: entering a "
+                         "voxel then adds min(15, its clearance cost - 1) with bands at 1^2 .. G^2.  pose_paths.planners reports hops, "
+                         "direction changes and the sum of U per planner")
     ap.add_argument("--pose-shortcut", action="store_true",
                     help="needs --pose-paths and --shortcut: the waypoints and costs of the pair paths come from wa_grid_pose_shortcut, which "
                          "straightens a stretch only where a planned direction stays open along the whole segment and keeps MAX_TURN at the "
@@ -551,8 +582,20 @@ def main():
             ap.error("--pose-paths needs the directions of --torch K")
         if not -1 <= args.pose_paths <= 3 << 20:
             ap.error("--pose-paths takes -1 or 0 .. 3145728")
-        if args.exact_paths or args.safe_paths or args.diagonal_paths is not None or args.geodesic:
-            ap.error("--pose-paths is a pair planner of its own: not with --exact-paths, --safe-paths, --diagonal-paths or --geodesic")
+        if args.exact_paths or (args.safe_paths and args.pose_turn_costs is None) or args.diagonal_paths is not None or args.geodesic:
+            ap.error("--pose-paths is a pair planner of its own: not with --exact-paths, --safe-paths (without --pose-turn-costs), "
+                     "--diagonal-paths or --geodesic")
+    pose_turn_costs = None
+    if args.pose_turn_costs is not None:
+        if args.pose_paths is None:
+            ap.error("--pose-turn-costs needs --pose-paths")
+        try:
+            bands = [tuple(int(v) for v in b.split("=")) for b in args.pose_turn_costs[1].split(",")]
+            pose_turn_costs = (int(args.pose_turn_costs[0]), [u for u, _ in bands], [0] + [c for _, c in bands])
+        except ValueError:
+            ap.error("--pose-turn-costs takes HOP and U1=C1[,U2=C2...] in integers")
+        if len(bands) > 4:
+            ap.error("--pose-turn-costs takes at most 4 bands")
     if args.pose_shortcut and (args.pose_paths is None or not args.shortcut):
         ap.error("--pose-shortcut needs --pose-paths and --shortcut")
     if args.torch is not None and args.fit is None and not args.retime and args.torch_grid is None and args.pose_paths is None:
@@ -631,7 +674,7 @@ def main():
         # the same exact planner on the grid as it was, for the cost of the detour (the colony is not run twice)
         if both:
             paths_without = plan_safe_diagonal(base, pts, args.safe_paths, args.diagonal_paths, args.safe_gain)[1]
-        elif args.safe_paths:
+        elif args.safe_paths and args.pose_paths is None:
             paths_without = plan_safe(base, pts, args.safe_paths)[1]
         elif args.diagonal_paths is not None:
             paths_without = plan_diagonal(base, pts, args.diagonal_paths)[1]
@@ -640,8 +683,14 @@ def main():
     t0 = time.perf_counter()
     if args.pose_paths is not None:
         pose_tool, pose_dirs, _ = torch_tool_and_cone(metal, args.torch)
+        pose_costs = None
+        if pose_turn_costs is not None:
+            pen = None
+            if args.safe_paths:
+                pen = np.clip(grid.clearance_costs([k * k for k in range(1, args.safe_paths + 1)]).astype(np.int32) - 1, 0, 15).astype(np.uint8)
+            pose_costs = api.pose_costs(*pose_turn_costs, pen)
         cost, paths, n_mine = plan_pose(grid, pts, pose_dirs, pose_tool, args.pose_paths, rank, world, shortcut=args.max_span if args.shortcut else 0,
-                                        pose_shortcut=args.pose_shortcut)
+                                        pose_shortcut=args.pose_shortcut, costs=pose_costs)
     elif both:
         cost, paths, n_mine = plan_safe_diagonal(grid, pts, args.safe_paths, args.diagonal_paths, args.safe_gain, rank, world,
                                                  shortcut=args.max_span if args.shortcut else 0, extra_pen=extra_pen)
@@ -683,7 +732,10 @@ def main():
     if args.pose_paths is not None and rank == 0:
         gone = [[i, j] for i in range(args.points) for j in range(i + 1, args.points) if not np.isfinite(cost[i, j])]
         out.update(pose_paths=dict(max_turn=args.pose_paths, K=args.torch, unreachable_pairs=gone, reachable_pairs=out["pairs"] - len(gone),
-                                   nodes_total=int(sum(len(p) for p in paths.values()))))
+                                   nodes_total=int(sum(len(p) for p in paths.values())), planners=plan_pose.last_totals))
+        if pose_turn_costs is not None:
+            out["pose_paths"].update(turn_costs=dict(hop=pose_turn_costs[0], bands=pose_turn_costs[1], costs=pose_turn_costs[2],
+                                                     safe_paths=args.safe_paths or 0))
         if plan_pose.last_pose_shortcut is not None:
             out["pose_paths"].update(shortcut=plan_pose.last_pose_shortcut)
     if torch_grid is not None and rank == 0:
@@ -780,7 +832,7 @@ def main():
                 ptraj, pok = smooth.plain if args.fit is not None else (traj, ok)
                 q.update(n_hit_cubic=int(api.Trajectory.from_points(ctx, ptraj[pok.astype(bool)]).clearance(metal)[3]["n_hit"]))
             out.update(safe_diagonal_paths=q)
-        if args.safe_paths and not both:
+        if args.safe_paths and not both and args.pose_paths is None:   # (with --pose-paths the penalties feed --pose-turn-costs)
             # what the soft margin buys and costs, against the hop-optimal paths of the same pairs in the same seam order: steps over
             # the optimum, path nodes inside the outermost band, and (--shortcut) segments of the smoothed curve that cut the metal
             P = args.points

@@ -1078,6 +1078,63 @@ int wa_grid_pose_shortcut(const wa_grid *g, const float *dirs, int32_t K, const 
                           const int64_t *ids, const int32_t *ks, const int64_t *off, int32_t n_paths, int32_t max_span,
                           int64_t *wp_idx, int32_t *hold_out, int32_t *wp_count, double *length_out, wa_pose_shortcut_summary *sum);
 
+/* ---- turn-cost pose paths: cheapest lattice paths over the states (voxel, direction) where a change of direction and a voxel near the
+ *      metal cost something (not in the reference).  wa_grid_pose_paths minimises hops and takes the lowest direction index among equally
+ *      short paths, so the torch swings for no reason; here a step is charged by how far it turns the torch and by the voxel it enters.
+ *      The rules continue the numbering above.  States, open(v, k), adj(k, k'), steps, seeds, pins and keys are those of rules 17 - 19,
+ *      unchanged; U(a, b) is rule 2's.  Integers only.
+ * 30. The cost description wa_pose_costs.  hop_cost = 1 .. 8.  n_bands = B = 0 .. WA_POSE_MAX_BANDS (4).  turn_band[0 .. B - 1]: strictly
+ *     ascending, each 0 .. 3 * 2^20.  turn_cost[0 .. B]: non-decreasing, each 0 .. WA_POSE_COST_MAX (15), turn_cost[0] = 0.  Entries of
+ *     both arrays behind those are ignored.  pen: one byte per voxel, 0 .. WA_POSE_COST_MAX on free voxels, an occupied voxel's byte is
+ *     ignored; NULL means all zero.  It is the array wa_grid_tool_penalties gives, or wa_grid_clearance_costs minus 1.
+ * 31. Turn class: class(k, k') = the number of bands b with U(q_k, q_k') > turn_band[b]; it is symmetric and class(k, k) = 0.
+ *     A step (v, k) -> (v', k') of rule 18 costs hop_cost + turn_cost[class(k, k')] + pen[v'] (at least 1).
+ * 32. dist(s; v, k) = the cheapest total over the paths from the seed of s to the state, WA_DIST_NONE (-1) where there is none (the seed's
+ *     states have 0: the start is not paid for).  cost(s; v) = the minimum over k of dist(s; v, k); cost(s; t, pin) restricts that
+ *     minimum to the pinned direction (pin = -1: no restriction), as in rule 20.
+ * 33. The path of a pair is defined, not only its cost D = cost(start; end, end pin).  Its end state is the lowest k allowed by the end
+ *     pin with dist D.  Walking back from (v, k) at dist L > 0, the predecessor voxel is the first neighbour in the order -x, +x, -y,
+ *     +y, -z, +z that is inside the grid and has some k' with adj(k', k) and dist(k') + hop_cost + turn_cost[class(k', k)] + pen[v] == L;
+ *     the predecessor direction is the lowest such k' of that voxel.  The path is returned start first.
+ * 34. wa_grid_pose_weighted_fields: cost_out[s * n + v] = cost(s; v); state_out (may be NULL) [(s * K + k) * n + v] = dist(s; v, k).
+ *     wa_grid_pose_weighted_matrix: cost_out[i * n_pts + j] = the cost from point i, seeded with its pin, to point j restricted to ITS
+ *     pin.  Without pen and with the same pins on both sides the matrix is symmetric; with pen and no pins
+ *     d(i, j) - pen[j] == d(j, i) - pen[i].  wa_grid_pose_weighted_paths: as wa_grid_pose_paths, pair p owns the range
+ *     [off[p], off[p + 1]) of ids_out and of dir_out; cost_out[p] = D or WA_DIST_NONE; len_out[p] (REQUIRED: the node count is not D + 1)
+ *     = the nodes of the path, 0 for no path.  The counts reach the caller for every pair first, WA_ERR_CAPACITY is reported once every
+ *     pair has its counts, only a pair's own len_out[p] entries are written, and an unreachable pair is no error.
+ *     Identities.  With hop_cost = 1, no pen, and n_bands = 0 or every turn_cost 0, all three calls return the bytes of wa_grid_pose_*
+ *     (len_out = D + 1).  Multiplying hop_cost, every turn_cost and every pen byte by one factor multiplies every distance by it and
+ *     keeps every path.  Two descriptions with the same classes of equal cost (a band between two classes of one cost) give the same bytes.
+ * 35. Errors.  Rule 23's apply (len_out is required here).  WA_ERR_ARG, before anything is written, also for: costs NULL; hop_cost,
+ *     n_bands, a band or a turn cost out of range; bands not strictly ascending; turn costs decreasing; turn_cost[0] != 0; a pen byte
+ *     above WA_POSE_COST_MAX on a free voxel.  WA_ERR_STATE past (hop_cost + max turn_cost + P) * (K * n_free - 1) + R + 1 levels (capped
+ *     at 2^31 - 33), P and R as in rule 36.
+ * 36. Memory.  The search is level-synchronous with the level the distance: R = hop_cost + max turn_cost + P + 1 settled sets per source,
+ *     P = the largest pen byte present on a free voxel.  A source costs (R + 1) * W * 8 * n bytes of bitmaps, 4 * n bytes of costs, and
+ *     4 * K * n bytes more where states are kept (_paths always, _fields with state_out): at 256^3, K = 64 and R = 12 about 1.7 GB per
+ *     source without states.  Sources are searched in chunks as for wa_grid_geodesic_* (WA_GEO_CHUNK and the chunk rule unchanged).
+ * Same bytes on every call; everything runs on the context's stream; g is not modified.  The masks, the step matrices (one K x W bit
+ * matrix per distinct step weight) and the device copy of pen are rebuilt by every call; nothing is cached with the grid. */
+#define WA_POSE_MAX_BANDS 4
+#define WA_POSE_COST_MAX 15
+typedef struct {
+    int32_t hop_cost;                          /* 1 .. 8 */
+    int32_t n_bands;                           /* B = 0 .. WA_POSE_MAX_BANDS */
+    int32_t turn_band[WA_POSE_MAX_BANDS];      /* [0 .. B - 1], strictly ascending, 0 .. 3 * 2^20 */
+    int32_t turn_cost[WA_POSE_MAX_BANDS + 1];  /* [0 .. B], non-decreasing, 0 .. WA_POSE_COST_MAX, [0] = 0 */
+    const uint8_t *pen;                        /* n bytes (host), 0 .. WA_POSE_COST_MAX on free voxels; NULL: all zero */
+} wa_pose_costs;
+int wa_grid_pose_weighted_fields(const wa_grid *g, const float *dirs, int32_t K, const wa_tool_beads *tool, int32_t max_turn,
+                                 const wa_pose_costs *costs, const int64_t *src_ids, const int32_t *src_pin, int32_t n_src, int32_t *cost_out,
+                                 int32_t *state_out);
+int wa_grid_pose_weighted_matrix(const wa_grid *g, const float *dirs, int32_t K, const wa_tool_beads *tool, int32_t max_turn,
+                                 const wa_pose_costs *costs, const int64_t *point_ids, const int32_t *point_pin, int32_t n_pts, int32_t *cost_out);
+int wa_grid_pose_weighted_paths(const wa_grid *g, const float *dirs, int32_t K, const wa_tool_beads *tool, int32_t max_turn,
+                                const wa_pose_costs *costs, const int64_t *start_ids, const int64_t *end_ids, const int32_t *pin_start,
+                                const int32_t *pin_end, int32_t n_pairs, const int64_t *off, int64_t *ids_out, int32_t *dir_out,
+                                int32_t *cost_out, int32_t *len_out);
+
 #ifdef __cplusplus
 }
 #endif

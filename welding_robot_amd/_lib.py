@@ -100,6 +100,14 @@ class PoseShortcutSummary(C.Structure):
                 ("n_held_end", C.c_int64), ("n_unheld", C.c_int64), ("max_hold_turn", C.c_int64)]
 
 
+POSE_MAX_BANDS, POSE_COST_MAX = 4, 15
+
+
+class PoseCosts(C.Structure):
+    _fields_ = [("hop_cost", C.c_int32), ("n_bands", C.c_int32), ("turn_band", C.c_int32 * POSE_MAX_BANDS),
+                ("turn_cost", C.c_int32 * (POSE_MAX_BANDS + 1)), ("pen", C.c_void_p)]
+
+
 class TickAxesSummary(C.Structure):
     _fields_ = [("n_ticks", C.c_int64), ("n_outside", C.c_int64), ("n_blocked", C.c_int64), ("first_blocked", C.c_int64),
                 ("n_near", C.c_int64), ("max_tick_turn", C.c_int64)]
@@ -232,6 +240,9 @@ SYMBOLS = {
     "wa_grid_pose_fields": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, _P, _P, _I, _P, _P]),
     "wa_grid_pose_matrix": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, _P, _P, _I, _P]),
     "wa_grid_pose_paths": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "wa_grid_pose_weighted_fields": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, C.POINTER(PoseCosts), _P, _P, _I, _P, _P]),
+    "wa_grid_pose_weighted_matrix": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, C.POINTER(PoseCosts), _P, _P, _I, _P]),
+    "wa_grid_pose_weighted_paths": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, C.POINTER(PoseCosts), _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "wa_grid_pose_shortcut": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, C.POINTER(PoseShortcutSummary)]),
     "wa_traj_axes_smooth": (C.c_int, [_V, _V, _P, C.POINTER(ToolBeads), _P, _I, C.c_double, _I, _P, _P, _P, C.POINTER(AxesSmoothSummary)]),
     "wa_traj_axes_limits": (C.c_int, [_V, _P, C.c_double, C.c_double, C.c_double, _P, _P, C.POINTER(AxesLimitsSummary)]),

@@ -293,6 +293,73 @@ class Grid:
         return (hops, [ids[off[k]:off[k + 1]].copy() if hops[k] >= 0 else None for k in range(n)],
                 [ks[off[k]:off[k + 1]].copy() if hops[k] >= 0 else None for k in range(n)])
 
+    def _pose_costs(self, costs):
+        assert isinstance(costs, PoseCosts), "costs come from api.pose_costs"
+        assert costs.pen is None or costs.pen.size == self.n, "a penalty array holds one byte per voxel"
+        return C.byref(costs.c)
+
+    def pose_weighted_fields(self, dirs, tool, max_turn, costs, ids, pins=None, states=False):
+        """wa_grid_pose_weighted_fields: pose_fields with a price on every step -- `costs` (api.pose_costs) charges a step its hop cost,
+        the turn cost of the class its change of direction falls in and the penalty of the voxel it enters.  Returns int32 cost
+        [len(ids), n], the least distance over the directions (WA_DIST_NONE (-1) where no state is reached), and with states=True also
+        int32 [len(ids), K, n], the distance of every state."""
+        dirs, K, tool = self._torch_args(dirs, tool)
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        pins = self._pins(pins, len(ids), "source")
+        cost = np.empty((len(ids), self.n), np.int32)
+        state = np.empty((len(ids), K, self.n), np.int32) if states else None
+        pad = np.zeros(1, np.int32)
+        self.ctx.check(self.ctx.lib.wa_grid_pose_weighted_fields(self.h, _ptr(dirs), K, C.byref(tool), int(max_turn), self._pose_costs(costs),
+                                                                 _ptr(ids if len(ids) else np.zeros(1, np.int64)),
+                                                                 _ptr(pins) if pins is not None and len(ids) else None, len(ids),
+                                                                 _ptr(cost if cost.size else pad), (_ptr(state if state.size else pad)) if states else None))
+        return (cost, state) if states else cost
+
+    def pose_weighted_matrix(self, dirs, tool, max_turn, costs, ids, pins=None):
+        """wa_grid_pose_weighted_matrix: int32 [P, P] of those costs between the points, pins as for pose_matrix (symmetric when `costs`
+        has no penalties and both sides carry the same pins; WA_DIST_NONE (-1) where two points are not connected)"""
+        dirs, K, tool = self._torch_args(dirs, tool)
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        pins = self._pins(pins, len(ids), "point")
+        out = np.empty((len(ids), len(ids)), np.int32)
+        self.ctx.check(self.ctx.lib.wa_grid_pose_weighted_matrix(self.h, _ptr(dirs), K, C.byref(tool), int(max_turn), self._pose_costs(costs),
+                                                                 _ptr(ids if len(ids) else np.zeros(1, np.int64)),
+                                                                 _ptr(pins) if pins is not None and len(ids) else None, len(ids),
+                                                                 _ptr(out if out.size else np.zeros(1, np.int32))))
+        return out
+
+    def pose_weighted_paths(self, dirs, tool, max_turn, costs, starts, ends, pin_start=None, pin_end=None):
+        """wa_grid_pose_weighted_paths of a batch of pairs: (int32 cost, [node-id array per pair, start first], [int32 direction index
+        per node]); None in both lists where the cost is WA_DIST_NONE.  The lists feed pose_shortcut_paths as those of pose_paths do.  Two
+        calls: the first, with empty ranges, returns the costs and node counts (WA_ERR_CAPACITY is its expected status when any pair is
+        reachable), the second writes the paths into ranges of those counts."""
+        dirs, K, tool = self._torch_args(dirs, tool)
+        starts = np.ascontiguousarray(starts, np.int64).reshape(-1)
+        ends = np.ascontiguousarray(ends, np.int64).reshape(-1)
+        assert len(starts) == len(ends)
+        n = len(starts)
+        ps, pe = self._pins(pin_start, n, "pair"), self._pins(pin_end, n, "pair")
+        cost, lens = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        off = np.zeros(n + 1, np.int64)
+        pad = np.zeros(1, np.int64)
+        cs = self._pose_costs(costs)
+
+        def call(ids, ks):
+            return self.ctx.lib.wa_grid_pose_weighted_paths(self.h, _ptr(dirs), K, C.byref(tool), int(max_turn), cs, _ptr(starts if n else pad),
+                                                            _ptr(ends if n else pad), _ptr(ps) if ps is not None and n else None,
+                                                            _ptr(pe) if pe is not None and n else None, n, _ptr(off), _ptr(ids), _ptr(ks), _ptr(cost),
+                                                            _ptr(lens))
+        rc = call(pad, np.zeros(1, np.int32))
+        if rc not in (0, 7):
+            self.ctx.check(rc)
+        off[1:] = np.cumsum(np.where(cost[:n] >= 0, lens[:n], 0).astype(np.int64))
+        ids, ks = np.empty(max(int(off[-1]), 1), np.int64), np.empty(max(int(off[-1]), 1), np.int32)
+        if rc == 7:
+            self.ctx.check(call(ids, ks))
+        cost = cost[:n]
+        return (cost, [ids[off[k]:off[k + 1]].copy() if cost[k] >= 0 else None for k in range(n)],
+                [ks[off[k]:off[k + 1]].copy() if cost[k] >= 0 else None for k in range(n)])
+
     def clearance_radius(self, metres):
         """a clearance in metres as a radius in voxels (exact up to the hi-side seam of the wall, see include/weldacs.h)"""
         return float(metres) / float(self.precision)
@@ -1140,6 +1207,36 @@ def torch_tool(dist16, r2):
     for j in range(len(r2)):
         t.dist16[j], t.r2[j] = int(dist16[j]), int(r2[j])
     return t
+
+
+class PoseCosts:
+    """a wa_pose_costs (`c`) together with the penalty array it points to (`pen`, None for none)"""
+
+    def __init__(self, c, pen):
+        self.c, self.pen = c, pen
+
+
+def pose_costs(hop, bands, turn_costs, pen=None):
+    """the cost description of Grid.pose_weighted_*: a step costs `hop` (1 .. 8), plus turn_costs[c] where c is the number of `bands`
+    (ascending thresholds on the turn measure U, at most 4) its change of direction exceeds -- turn_costs has one entry more than
+    bands, starts with 0 and does not decrease, each at most 15 -- plus pen[v] of the voxel entered (uint8 [n], at most 15 on free
+    voxels; Grid.torch_penalties, or Grid.clearance_costs minus 1).  The ranges are checked by the library."""
+    bands = np.asarray(bands, np.int64).reshape(-1)
+    turn_costs = np.asarray(turn_costs, np.int64).reshape(-1)
+    if len(bands) > L.POSE_MAX_BANDS or len(turn_costs) != len(bands) + 1:
+        raise ValueError("at most %d bands, and one turn cost more than bands" % L.POSE_MAX_BANDS)
+    if max(abs(int(hop)), np.abs(bands).max(initial=0), np.abs(turn_costs).max()) >= 2 ** 31:
+        raise ValueError("hop, bands and turn_costs are int32")
+    c = L.PoseCosts()
+    c.hop_cost, c.n_bands = int(hop), len(bands)
+    for b in range(len(bands)):
+        c.turn_band[b] = int(bands[b])
+    for b in range(len(turn_costs)):
+        c.turn_cost[b] = int(turn_costs[b])
+    if pen is not None:
+        pen = np.ascontiguousarray(pen, np.uint8).reshape(-1)
+        c.pen = pen.ctypes.data
+    return PoseCosts(c, pen)
 
 
 def quantise_axes(dirs):

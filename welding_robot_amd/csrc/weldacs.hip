@@ -40,6 +40,7 @@
 #include "torch_kernels.hpp"
 #include "reach_kernels.hpp"
 #include "pose_kernels.hpp"
+#include "pose_weighted_kernels.hpp"
 #include "pose_shortcut_kernels.hpp"
 #include "ticks_kernels.hpp"
 #include "stl_text.hpp"
@@ -847,6 +848,7 @@ void *wa_ctx_stream(wa_ctx *c) { return c ? (void *)c->stream : nullptr; }
 #include "host_torch.inc"
 #include "host_reach.inc"
 #include "host_pose.inc"
+#include "host_pose_weighted.inc"
 #include "host_pose_shortcut.inc"
 #include "host_ticks.inc"
 
