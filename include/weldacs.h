@@ -302,6 +302,14 @@ int wa_acs_converged_info(wa_acs *s, int32_t slot, uint64_t out[4]);
  * out: [0] verdicts the host went to read since the solver was created, [1] generations whose launches were not enqueued, [2] speculative flushes
  * cancelled, [3] waits given up, of [0].  Results are bit-identical with the read-back on or off.  Does not wait. */
 int wa_acs_converged_host_info(wa_acs *s, uint64_t out[4]);
+/* Owed evaporations, on the same path (a lone search whose verdicts the host reads; WA_CONVERGED_OWED=0, read at wa_acs_create: never).  A window that
+ * commits whole in front of a generation that is enqueued in full whatever happens -- the last of the call, or one stamped for wa_acs_profile -- also
+ * tests that generation: if every ant of it replays the best path too, nothing reads the field in between, the window is CARRIED and its flush leaves
+ * the pass over the field out; the sweep of the generation behind it multiplies every value once more than the window committed generations, one
+ * rounding each.  out: [0] whole windows the host read "carried" of since the solver was created, [1] generations enqueued whose sweep paid a carried
+ * window's evaporations with its own, [2] whole windows that were not carried (an ant leaves the path behind them: flushed as ever), [3] / [4]: of [1],
+ * the sweeps that ran out of place / in place.  Results are bit-identical with the switch on or off.  Does not wait. */
+int wa_acs_converged_owed_info(wa_acs *s, uint64_t out[5]);
 /* evaporation sweep alone (ACSRank_3D.hpp:268-272) over `slot` -- for roofline measurements */
 int wa_acs_evaporate(wa_acs *s, int32_t slot, float rho, int32_t repeats);
 

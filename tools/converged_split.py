@@ -14,7 +14,9 @@ A generation's three launches are classed `at once` when the sweep-carrying laun
 field takes 13 us and more, a launch that returns at its top 2-5 us under the profiler), `flush` when they follow launches that returned at once --
 or follow the window kernel directly with a walk launch shorter than --walk-us (default 3: a window that committed one generation) --, `full`
 otherwise.  A speculative flush (two launches directly behind a window kernel, no walk launch) is a `flush` if its sweep ran and `at once` if it
-was cancelled.  The gap in front of a dispatch is its start minus the latest end of everything dispatched
+was cancelled.  With owed evaporations (WA_CONVERGED_OWED) the flush of a carried window is one small launch: the table blocks of
+k_apply_table alone, or the speculative pair whose sweep blocks returned at once; both are classed `rows` (a cancelled speculative flush, whose
+two launches both return at once, cannot be told from the latter by its times and is counted there too).  The gap in front of a dispatch is its start minus the latest end of everything dispatched
 before it.  The classes' kernel time and gaps add up to the region's span."""
 import csv
 import glob
@@ -59,8 +61,12 @@ def main():
         if timed[i]["kind"] == TRIO[1]:   # a speculative flush: the two launches behind a window, no walk launch
             duo = timed[i:i + 2]
             assert tuple(x["kind"] for x in duo) == TRIO[1:], "dispatch %d of the timed region: %s" % (i, [x["kind"] for x in duo])
-            items.append(("at once" if duo[0]["us"] < empty_us else "flush", [None] + duo))
+            items.append(("rows" if duo[0]["us"] < empty_us else "flush", [None] + duo))
             i += 2
+            continue
+        if timed[i]["kind"] == TRIO[2]:   # the rows launch of a carried window, alone
+            items.append(("rows", [None, None, timed[i]]))
+            i += 1
             continue
         trio = timed[i:i + 3]
         assert tuple(x["kind"] for x in trio) == TRIO, "dispatch %d of the timed region: %s" % (i, [x["kind"] for x in trio])
@@ -88,14 +94,14 @@ def main():
     print("| class | count | kernels us | gaps us | total us | share | per item us |")
     print("|---|---|---|---|---|---|---|")
     total = 0.0
-    for cls in ("window", "at once", "flush", "full"):
+    for cls in ("window", "at once", "flush", "rows", "full"):
         mine = [xs for c, xs in region if c == cls]
         first_gap = region[0][1][0]["gap"] if region[0][0] == cls else 0.0      # (the gap in front of the region is not part of its span)
         kus, gus = sum(x["us"] for xs in mine for x in xs), sum(x["gap"] for xs in mine for x in xs) - first_gap
         total += kus + gus
         print("| %s | %d | %.1f | %.1f | %.1f | %.1f %% | %.2f |" % (cls, len(mine), kus, gus, kus + gus, 100 * (kus + gus) / span, (kus + gus) / max(len(mine), 1)))
     print("| all | %d | | | %.1f | %.1f %% | |" % (len(region), total, 100 * total / span))
-    for cls in ("window", "at once", "flush", "full"):
+    for cls in ("window", "at once", "flush", "rows", "full"):
         mine = [xs for c, xs in region if c == cls]
         if not mine:
             continue

@@ -637,6 +637,14 @@ class AcsSolver:
         self.ctx.check(self.ctx.lib.wa_acs_converged_host_info(self.h, out))
         return [int(v) for v in out]
 
+    def converged_owed_info(self):
+        """owed evaporations (a lone search whose verdicts run() reads) since the solver was created: whole windows found carried, generations
+        enqueued whose sweep paid a carried window's evaporations with its own (`merged`), whole windows that were not carried and flushed as ever
+        (`fallback`), and of the merged sweeps those that ran out of place and in place"""
+        out = (C.c_uint64 * 5)()
+        self.ctx.check(self.ctx.lib.wa_acs_converged_owed_info(self.h, out))
+        return dict(carried=int(out[0]), merged=int(out[1]), fallback=int(out[2]), out_of_place=int(out[3]), in_place=int(out[4]))
+
     def set_stragglers(self, generations):
         """generations of a search during which ants may be handed over (0: off, < 0: default)"""
         self.ctx.check(self.ctx.lib.wa_acs_set_stragglers(self.h, generations))

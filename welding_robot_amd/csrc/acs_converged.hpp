@@ -25,6 +25,14 @@
 // out the launches of committed generations (host_acs.inc: conv_verdict); nothing on the device ever waits for the host.  Behind a window that
 // committed whole the host enqueues the next window's flush before it has the verdict, marked WA_GEN_SPEC: such a flush does nothing unless the window
 // committed exactly up to its generation.
+//
+// OWED evaporations (WA_GEN_OWED, acs_dev.hpp).  The flush of generation g + W - 1 passes over the whole field, and the sweep of the full generation g + W
+// directly behind it passes over it again; between the two only the walk of generation g + W could read the field, and only through an ant that leaves
+// the path.  A launch that is told to (judge) therefore tests generation g + W as well when its blocks got through all W generations: the same per-ant
+// test with that generation's keys and colony (the chain is run one step further than it commits) against the rows of the last snapshot, nothing
+// advanced.  If every ant of g + W replays the path the commit records the window as CARRIED in the header and in the verdict (WA_CONV_CARRIED); the
+// host then leaves the flush's sweep out and has the sweep of g + W multiply W + 1 times, from the buffer the window found the field in.  The header
+// keeps what a later change needs to chain windows without a field pass in between: `pending`, the evaporations owed, and `carried`.
 #pragma once
 
 #define WA_CONV_CHECK_WAVES 4     // wavefronts of a block that check the ants (lane = ant), ...
@@ -38,13 +46,14 @@
 #define WA_CONV_SNAP 14           // floats per node of a snapshot: six records + the row
 
 struct WaConvHdr {                // head of a slot's scratch block; the snapshots follow
-    uint32_t rem;                 // max over the window's blocks of (W - generations the block's ants stayed on the path); 0 between windows
+    uint32_t rem;                 // max over the window's blocks of 2 (W - generations the block's ants stayed on the path) + (an ant leaves in the generation behind); 0 between windows
     uint32_t ticket;              // blocks of the running window that have finished; 0 between windows
-    int32_t pending;              // j of the last commit: evaporations the flush applies
-    int32_t pad_;
+    int32_t pending;              // j of the last commit: evaporations the flush applies (or, owed, the sweep of the generation behind it)
+    int32_t carried;              // the last commit was of a whole window, and every ant of the generation behind it replays the path too
     unsigned long long whole, cut, gens;   // windows committed whole / cut (0 < j < W), generations committed (wa_acs_converged_info)
     unsigned long long pad2_[3];
 };
+static_assert(WA_CONV_SNAP == 14, "wa_table_rows strides the owed records by 14 floats");
 static_assert(sizeof(WaConvHdr) == 64, "the snapshots start 64 bytes into the block");
 
 __device__ __forceinline__ WaConvHdr *wa_conv_hdr(const WaAcsDev &D, int32_t slot) { return reinterpret_cast<WaConvHdr *>(D.conv + (int64_t)slot * D.conv_stride); }
@@ -54,9 +63,14 @@ __device__ __forceinline__ float *wa_conv_snap(const WaAcsDev &D, int32_t slot, 
     return reinterpret_cast<float *>(D.conv + (int64_t)slot * D.conv_stride + sizeof(WaConvHdr)) + (int64_t)t * D.conv_nodes * WA_CONV_SNAP;
 }
 __device__ __forceinline__ int32_t wa_conv_pending(const WaAcsDev &D, int32_t slot) { return wa_conv_hdr(D, slot)->pending; }
+__device__ __forceinline__ bool wa_conv_carried(const WaAcsDev &D, int32_t slot) { return wa_conv_hdr(D, slot)->carried != 0; }
+// the path nodes' records of the last commit, [node][WA_CONV_SNAP] (the table blocks of the generation behind a carried window: wa_table_rows)
+__device__ __forceinline__ const float *wa_conv_owed_records(const WaAcsDev &D, int32_t slot) { return wa_conv_snap(D, slot, wa_conv_pending(D, slot) - 1); }
+#define WA_CONV_CARRIED 0x80u     // in the verdict word beside j (j <= WA_CONV_MAX_WINDOW < 128)
 
-// the flush's table blocks: records (into D.pher, the buffer the flush sweep wrote) and rows of the path nodes from the snapshot of the commit
-__device__ __forceinline__ void wa_conv_flush_rows(const WaAcsDev &D, int32_t slot, int32_t first, int32_t step)
+// the flush's table blocks: records (into D.pher, the buffer the flush sweep wrote) and rows of the path nodes from the snapshot of the commit.
+// rows_only: the evaporations are owed (no sweep ran, D.pher is not the field): the records stay in the snapshot for the table blocks of the next generation
+__device__ __forceinline__ void wa_conv_flush_rows(const WaAcsDev &D, int32_t slot, int32_t first, int32_t step, bool rows_only)
 {
     const int32_t blen = D.ctl[slot].best_len, j = wa_conv_pending(D, slot);
     if (j < 1) return;
@@ -67,7 +81,7 @@ __device__ __forceinline__ void wa_conv_flush_rows(const WaAcsDev &D, int32_t sl
     for (int32_t x = first; x < blen * WA_CONV_SNAP; x += step) {
         const int32_t i = x / WA_CONV_SNAP, q = x - i * WA_CONV_SNAP;
         const float v = snap[x];
-        if (q < 6) pher[(int64_t)(bpath[i] & (int32_t)WA_ID_MASK) * 6 + q] = v;
+        if (q < 6) { if (!rows_only) pher[(int64_t)(bpath[i] & (int32_t)WA_ID_MASK) * 6 + q] = v; }
         else T[(int64_t)i * 8 + (q - 6)] = v;
     }
 }
@@ -98,12 +112,12 @@ __device__ __forceinline__ void wa_conv_ctl_step(WaSlotCtl &c, const WaRun &R, i
 // front makes that the block's writes of ctl, perm and depA) is visible system-wide before the word is.  j == 0: nothing was committed, so there is
 // nothing to order the word behind, and the store is a plain system-scope one: no cache is written back for it (a window that commits nothing sits
 // between the launches of an exploring search).  verdict: the group's first slot's word, or null (no report)
-__device__ __forceinline__ void wa_conv_report(uint32_t *verdict, int32_t slot, uint32_t seq, int32_t j)
+__device__ __forceinline__ void wa_conv_report(uint32_t *verdict, int32_t slot, uint32_t seq, int32_t j, bool carried = false)
 {
     if (!verdict) return;
     if (j > 0) {
         __threadfence_system();
-        __hip_atomic_store(verdict + slot, (seq << 8) | (uint32_t)j, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(verdict + slot, (seq << 8) | (carried ? WA_CONV_CARRIED : 0u) | (uint32_t)j, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     } else __hip_atomic_store(verdict + slot, seq << 8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
@@ -138,17 +152,18 @@ __host__ __device__ inline int32_t wa_conv_share(int32_t nodes, int32_t blocks) 
 // What a block keeps in LDS behind its nodes' state (all of it in the dynamic region, every offset a multiple of 16 bytes)
 struct WaConvShared {
     WaSlotCtl tab[WA_CONV_MAX_WINDOW + 1];   // tab[t]: the control block as generation gen0 + t finds it; tab[t + 1]: as it leaves it
-    unsigned long long key[WA_CONV_MAX_WINDOW];   // wa_ctr_key of generation gen0 + t
-    int32_t bad[WA_CONV_MAX_WINDOW];         // an ant left the path at one of this block's nodes in generation gen0 + t
+    unsigned long long key[WA_CONV_MAX_WINDOW + 1];   // wa_ctr_key of generation gen0 + t (t = W: the generation behind the window, when it is judged)
+    int32_t bad[WA_CONV_MAX_WINDOW + 1];     // an ant left the path at one of this block's nodes in generation gen0 + t
     int32_t run;                             // generations of the window whose colony is in range (the chain stops at the first that is not)
-    int32_t last, j, pad_;
+    int32_t last, j, carried;
 };
 __host__ __device__ inline size_t wa_conv_lds_bytes(int32_t conv_nodes, int32_t blocks)
 {
     return (size_t)wa_conv_share(conv_nodes, blocks) * WA_CONV_NODE_LDS + sizeof(WaConvShared);
 }
 
-__global__ __launch_bounds__(WA_CONV_THREADS) void k_converged_run(WaAcsDev D, WaRun R, int32_t gen0, int32_t W, uint32_t *verdict, uint32_t seq)
+// judge: also test generation gen0 + W (see OWED above); 0: the launch is what it was
+__global__ __launch_bounds__(WA_CONV_THREADS) void k_converged_run(WaAcsDev D, WaRun R, int32_t gen0, int32_t W, uint32_t *verdict, uint32_t seq, int32_t judge)
 {
     extern __shared__ __attribute__((aligned(16))) float wa_conv_lds[];
     const int32_t slot = blockIdx.y, blk = blockIdx.x, nblk = gridDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -205,9 +220,11 @@ __global__ __launch_bounds__(WA_CONV_THREADS) void k_converged_run(WaAcsDev D, W
             wa_conv_ctl_step(S.tab[run + 1], R, gen);
         }
         if (lane == 0) S.run = run;
-    } else if (wave == 1 && lane < W) {
-        S.key[lane] = wa_ctr_key(R.seed, ctl->stream, (uint32_t)(gen0 + lane));
-        S.bad[lane] = 0;
+    } else if (wave == 1) {
+        for (int32_t t = lane; t <= W; t += 64) {   // (W <= 64: lane 0 takes a second trip for t = 64)
+            S.key[t] = wa_ctr_key(R.seed, ctl->stream, (uint32_t)(gen0 + t));
+            S.bad[t] = 0;
+        }
     }
     __syncthreads();
     const int32_t run = S.run;
@@ -270,23 +287,55 @@ __global__ __launch_bounds__(WA_CONV_THREADS) void k_converged_run(WaAcsDev D, W
         __syncthreads();
         if (S.bad[t] != 0) { my_t = t; break; }   // (uniform over the block; bad[t] is written in front of this barrier only)
     }
+    // ---- the generation behind the window, judged where the window is whole for this block: every ant of generation gen0 + W against the rows of the
+    // last snapshot (in half W & 1, complete behind the loop's last barrier), with the colony the chain's last step set.  Nothing is advanced.
+    int32_t leaves = 1;                           // an ant leaves the path in generation gen0 + W at one of this block's nodes, or that generation is not judged
+    if (judge && run == W && my_t == W) {         // (uniform over the block)
+        const int32_t gen = gen0 + W;
+        const int32_t colony = S.tab[W].colony[gen & 1];
+        leaves = !(colony >= 1 && colony <= D.max_colony);
+        if (!leaves && mine > 0) {
+            if (wave < WA_CONV_CHECK_WAVES) {
+                const float *row = s_row + (W & 1) * cap * 8;
+                const uint64_t genkey = S.key[W];
+                for (int32_t a = tid; a < colony; a += WA_CONV_CHECK_WAVES * 64) {
+                    const uint64_t antkey = wa_ctr_antkey(genkey, (uint32_t)a);
+                    bool bad = false;
+                    for (int32_t n = 0; n < ndec; n++) {
+                        const float4 *r4 = reinterpret_cast<const float4 *>(row + n * 8);
+                        const float4 ca = r4[0], cb = r4[1];
+                        const uint32_t h = wa_replay_hits(ca, cb, (int32_t)wa_ctr_draw(antkey, (uint32_t)(n0 + n)));
+                        const int pick = h ? 31 - __clz((int)h) : -1;
+                        bad = bad || pick != __float_as_int(cb.w);
+                    }
+                    if (bad) S.bad[W] = 1;
+                }
+            }
+            __syncthreads();
+            leaves = S.bad[W] != 0;
+        }
+    }
     // ---- the block that finishes last commits
     if (tid == 0) {
-        atomicMax(&hdr->rem, (uint32_t)(W - my_t));
+        atomicMax(&hdr->rem, ((uint32_t)(W - my_t) << 1) | (uint32_t)leaves);
         __threadfence();
         const uint32_t tk = atomicAdd(&hdr->ticket, 1u);
-        int32_t is_last = 0, j = 0;
+        int32_t is_last = 0, j = 0, carried = 0;
         if (tk == (uint32_t)nblk - 1u) {
             __threadfence();
             is_last = 1;
-            j = W - (int32_t)atomicMax(&hdr->rem, 0u);
+            const uint32_t rem = atomicMax(&hdr->rem, 0u);
+            j = W - (int32_t)(rem >> 1);
+            carried = rem == 0u;                  // whole, and no block saw an ant leave in the generation behind
         }
         S.last = is_last;
         S.j = j;
+        S.carried = carried;
     }
     __syncthreads();
     if (!S.last) return;
     const int32_t j = S.j;                        // (<= run: the block of node 0 reports no more)
+    const bool carried = S.carried != 0;
     if (tid == 0) {
         hdr->rem = 0;
         hdr->ticket = 0;
@@ -295,6 +344,7 @@ __global__ __launch_bounds__(WA_CONV_THREADS) void k_converged_run(WaAcsDev D, W
             c.spec_until = gen0 + j;
             *ctl = c;
             hdr->pending = j;
+            hdr->carried = carried ? 1 : 0;
             hdr->gens += (unsigned long long)j;
             if (j == W) hdr->whole += 1; else hdr->cut += 1;
         }
@@ -322,5 +372,5 @@ __global__ __launch_bounds__(WA_CONV_THREADS) void k_converged_run(WaAcsDev D, W
     }
     // ---- the verdict, behind this block's writes of ctl, perm, depA and the trace rows
     __syncthreads();
-    if (tid == 0) wa_conv_report(verdict, slot, seq, j);
+    if (tid == 0) wa_conv_report(verdict, slot, seq, j, carried);
 }

@@ -6,6 +6,15 @@
 // enqueued before the host knows what the window in front of it committed: it flushes when the window committed up to its generation exactly
 // (ctl.spec_until == gen + 1) and does nothing at all otherwise
 #define WA_GEN_SPEC 0x40000000
+// OWED evaporations (acs_converged.hpp; host_acs.inc: wa_acs_run), a second bit in the generation number of the same two launches.  A window [g, g + W)
+// that committed whole and found that every ant of generation g + W replays the path too is CARRIED (WaConvHdr::carried): nothing reads the field
+// before the sweep of generation g + W, so the W evaporations the window owes the field are paid by that sweep.
+//   on the launches of generation g + W - 1 (the flush): behind a carried window the sweep blocks do nothing and the table blocks put the rows in
+//     place, not the records; behind any other window the launches flush as ever;
+//   on the launches of generation g + W (the host has read "carried"): the sweep blocks multiply every value pending + 1 times, the table blocks take
+//     the path nodes' records from the commit's snapshot.
+#define WA_GEN_OWED 0x20000000
+#define WA_GEN_FLAGS (WA_GEN_SPEC | WA_GEN_OWED)
 
 struct WaAcsDev {
     WaDims d;

@@ -261,6 +261,7 @@ __global__ __launch_bounds__(256) void k_rank(WaAcsDev D, WaRun R, int32_t gen)
 // thread, grid-stride over E blocks.  One definition for k_evaporate and the fused k_evap_rank_mark.
 typedef float wa_v4f __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ int32_t wa_conv_pending(const WaAcsDev &D, int32_t slot);   // (acs_converged.hpp)
+__device__ __forceinline__ bool wa_conv_carried(const WaAcsDev &D, int32_t slot);
 // NT bit 0 / bit 1: non-temporal loads / stores (the `nt` bit of global_load / global_store: the lines stream through the caches instead of
 // displacing what is there).  Wrong for a lone search at 128^3 -- the next walk finds the swept field in the Infinity Cache -- and
 // right when several searches share the GPU (their fields are past every cache anyway and the walking groups' records stay in L2)
@@ -334,13 +335,16 @@ __global__ __launch_bounds__(256) void k_evap_rank_mark(WaAcsDev D, WaRun R, con
     // A generation below ctl.spec_until was committed by k_converged_run (acs_converged.hpp): nothing to rank, mark or sweep.  The launch of the LAST
     // committed generation is the flush: its sweep blocks apply the j evaporations the committed generations owe the field, one rounding each.  The field
     // sits where the window found it -- the host flipped src / dst j - 1 times since: this launch's src for odd j (out of place), its dst for even j
-    // (in place) -- and ends up in dst, the buffer the host takes for current, either way
-    if (gen & WA_GEN_SPEC) {   // a speculative flush: only if the window committed exactly up to this generation
-        gen &= ~WA_GEN_SPEC;
-        if (gen + 1 != D.ctl[slot].spec_until) return;
-    }
+    // (in place) -- and ends up in dst, the buffer the host takes for current, either way.
+    // WA_GEN_OWED on the flush: behind a carried window the evaporations stay owed, no sweep.  On the generation behind a carried window (the host sets
+    // the bit there once it has read the verdict) the sweep blocks pay them with their own: j + 1 multiplications.  The host has flipped once more
+    // since the flush, so the field as the window found it is this launch's src for even j (out of place) and its dst for odd j (in place)
+    const int32_t gflags = gen & WA_GEN_FLAGS;
+    gen &= ~WA_GEN_FLAGS;
+    if ((gflags & WA_GEN_SPEC) && gen + 1 != D.ctl[slot].spec_until) return;   // a speculative flush: only if the window committed exactly up to this generation
     if (gen < D.ctl[slot].spec_until) {
         if (!SPARSE && NB == 6 && gen + 1 == D.ctl[slot].spec_until && (int32_t)blockIdx.x >= MB) {
+            if ((gflags & WA_GEN_OWED) && wa_conv_carried(D, slot)) return;
             const int32_t j = wa_conv_pending(D, slot);
             float *to = dst_base + (int64_t)slot * D.pher_stride;
             wa_sweep_body((j & 1) ? src_base + (int64_t)slot * D.pher_stride : to, to, (int64_t)NB * D.d.n, R.rho, (int32_t)blockIdx.x - MB, E, sweep_nt, j);
@@ -354,8 +358,9 @@ __global__ __launch_bounds__(256) void k_evap_rank_mark(WaAcsDev D, WaRun R, con
         if (sweep_nt & 0x100) return;   // timing aid (tools/fused_parts.py): the launch without its sweep
 #endif
         if (!SPARSE) {
-            wa_sweep_body(src_base + (int64_t)slot * D.pher_stride, dst_base + (int64_t)slot * D.pher_stride, (int64_t)NB * D.d.n, R.rho,
-                          (int32_t)blockIdx.x - MB, E, sweep_nt);
+            float *to = dst_base + (int64_t)slot * D.pher_stride;
+            const int32_t reps = (NB == 6 && (gflags & WA_GEN_OWED)) ? wa_conv_pending(D, slot) + 1 : 1;
+            wa_sweep_body((reps & 1) ? src_base + (int64_t)slot * D.pher_stride : to, to, (int64_t)NB * D.d.n, R.rho, (int32_t)blockIdx.x - MB, E, sweep_nt, reps);
         } else {
             // lazy evaporation, background pass: every lazy_period-th entry of the dirty list (phase = generation) is brought
             // current in place, so no record has more than ~lazy_period multiplications pending (whoever reads a record applies

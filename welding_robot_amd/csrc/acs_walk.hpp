@@ -957,8 +957,10 @@ __device__ __forceinline__ void wa_row_values(const WaRun &R, float p, float h, 
 // ascending rank order as wa_apply_body -- writes them back, clears the masks, and evaluates on the new values.
 // dep_lane, n_dep: the deposit coefficients, rank bit l in lane l of every wavefront, and how many ranks deposit (wa_add_ranked).
 __device__ __forceinline__ void wa_table_rows(const WaAcsDev &D, const WaRun &R, int32_t slot, int32_t row0, int32_t rows, bool apply_here,
-                                              float dep_lane, int32_t n_dep, int32_t w_first, int32_t w_first_next)
+                                              float dep_lane, int32_t n_dep, int32_t w_first, int32_t w_first_next, const float *owed_rec = nullptr)
 {
+    // owed_rec: the path nodes' records as the last window's commit left them ([node][WA_CONV_SNAP], acs_converged.hpp), one evaporation short of this
+    // generation's: what the swept field holds for these nodes is stale and is overwritten, never read
     // w_first / w_first_next = bestpath[row0], bestpath[row0 + 1], loaded by the caller before the best length was
     // known (speculatively, inside the allocation) so that the row's record loads start one round trip earlier
     const WaSlotCtl *ctl = &D.ctl[slot];
@@ -998,7 +1000,7 @@ __device__ __forceinline__ void wa_table_rows(const WaAcsDev &D, const WaRun &R,
         const int32_t v = wv & (int32_t)WA_ID_MASK;
         // all record loads of the row are independent of each other
         const int64_t e = (int64_t)v * 6 + kk;
-        float p = pher[e];
+        float p = owed_rec ? owed_rec[(int64_t)(live ? i : 0) * 14 + kk] * R.rho : pher[e];
         const float h = heur[e];
         if (stamp) {
             const uint32_t stv = stamp[v];
@@ -1020,10 +1022,8 @@ __device__ __forceinline__ void wa_table_rows(const WaAcsDev &D, const WaRun &R,
         if (apply_here) {
             // somebody walked (v, k2): apply the ranked deposits in ascending rank order (:210-211); v itself is on the best path, so mk == ver is :209
             p = wa_add_ranked(p, m, dep_lane, mk == ver ? bonus_on : bonus_off, n_dep);
-            if (m) {
-                pher[e] = p;
-                wa_mask_clear(mask, e);
-            }
+            if (m || (owed_rec && live && k2 < 6)) pher[e] = p;
+            if (m) wa_mask_clear(mask, e);
         }
         float thr, t;
         wa_row_values(R, p, h, k2, bt, thr, t);
@@ -1052,17 +1052,18 @@ __global__ __launch_bounds__(256) void k_replay_table(WaAcsDev D, WaRun R)
 #define WA_TABLE_BLOCKS_MAX 64
 // split_log2: apply blocks per depositing rank = 1 << this (the host passes 2 for one or a few searches -- 8 blocks per rank are no
 // faster --, 1 for launches that carry 32 searches or more)
-__device__ __forceinline__ void wa_conv_flush_rows(const WaAcsDev &D, int32_t slot, int32_t first, int32_t step);   // (acs_converged.hpp)
+__device__ __forceinline__ void wa_conv_flush_rows(const WaAcsDev &D, int32_t slot, int32_t first, int32_t step, bool rows_only);   // (acs_converged.hpp)
+__device__ __forceinline__ bool wa_conv_carried(const WaAcsDev &D, int32_t slot);
+__device__ __forceinline__ const float *wa_conv_owed_records(const WaAcsDev &D, int32_t slot);
 // gen: the generation this launch belongs to.  Below ctl.spec_until the generation was committed by k_converged_run and the launch returns at once --
 // except the launch of the LAST committed generation, whose table blocks put the path nodes' records and rows of the commit in place
 __global__ __launch_bounds__(256) void k_apply_table(WaAcsDev D, WaRun R, int32_t split_log2, int32_t table_blocks, int32_t gen)
 {
     const int32_t slot = blockIdx.y;
     const int32_t spec_until = D.ctl[slot].spec_until;
-    if (gen & WA_GEN_SPEC) {   // a speculative flush (see WA_GEN_SPEC)
-        gen &= ~WA_GEN_SPEC;
-        if (gen + 1 != spec_until) return;
-    }
+    const int32_t gflags = gen & WA_GEN_FLAGS;
+    gen &= ~WA_GEN_FLAGS;
+    if ((gflags & WA_GEN_SPEC) && gen + 1 != spec_until) return;   // a speculative flush (see WA_GEN_SPEC)
     if (gen + 1 < spec_until) return;
     // lazy evaporation: voxels that became dirty in this generation join the swept set from the next sweep on
     if (D.dcount && blockIdx.x == 0 && threadIdx.x == 0) D.dcount[slot * 2] = D.dcount[slot * 2 + 1];
@@ -1072,7 +1073,9 @@ __global__ __launch_bounds__(256) void k_apply_table(WaAcsDev D, WaRun R, int32_
         if (threadIdx.x == 0) { *sg.arr_n = 0; sg.pool_n[D.ctl[slot].gen & 1] = 0; }   // (ctl.gen is already the next generation's number)
     }
     if (gen < spec_until) {   // the flush (the sweep blocks of the launch in front evaporated the whole field, these nodes' stale records included)
-        if ((int32_t)blockIdx.x < table_blocks) wa_conv_flush_rows(D, slot, blockIdx.x * blockDim.x + threadIdx.x, table_blocks * blockDim.x);
+        // (WA_GEN_OWED behind a carried window: no sweep ran and D.pher is not the field -- the rows alone, the records stay in the snapshot)
+        if ((int32_t)blockIdx.x < table_blocks)
+            wa_conv_flush_rows(D, slot, blockIdx.x * blockDim.x + threadIdx.x, table_blocks * blockDim.x, (gflags & WA_GEN_OWED) && wa_conv_carried(D, slot));
         return;
     }
     if ((int32_t)blockIdx.x < table_blocks) {
@@ -1082,7 +1085,10 @@ __global__ __launch_bounds__(256) void k_apply_table(WaAcsDev D, WaRun R, int32_
         const int32_t *bpath = D.bestpath + (int64_t)slot * D.path_cap;
         const int32_t w0 = row0 < D.path_cap ? bpath[row0] : 0, w1 = row0 + 1 < D.path_cap ? bpath[row0 + 1] : 0;
         const int32_t n_dep = D.ctl[slot].n_dep;
-        wa_table_rows(D, R, slot, row0, (table_blocks * blockDim.x) >> 4, true, dep_lane, n_dep < 64 ? n_dep : 64, w0, w1);
+        // (WA_GEN_OWED: the generation behind a carried window.  The sweep in front paid the owed evaporations on every value, the path nodes' stale
+        //  records included: those are taken from the commit's snapshot, x rho, and written whether or not anything was deposited on them)
+        wa_table_rows(D, R, slot, row0, (table_blocks * blockDim.x) >> 4, true, dep_lane, n_dep < 64 ? n_dep : 64, w0, w1,
+                      (gflags & WA_GEN_OWED) ? wa_conv_owed_records(D, slot) : nullptr);
         return;
     }
     const int32_t ab = (int32_t)blockIdx.x - table_blocks;  // 0..(ranks << split_log2)-1: (bx, rank bit)

@@ -185,6 +185,7 @@ static int acs_create_once(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, in
     s->conv_readback = env_int("WA_CONVERGED_READBACK", 1) != 0;
     s->conv_wait_us = env_int("WA_CONVERGED_WAIT_US", 200000);
     s->conv_spec = env_int("WA_CONVERGED_SPECULATE", 1) != 0;
+    s->conv_owed = env_int("WA_CONVERGED_OWED", 1) != 0;
     s->conv_enqueued.assign((size_t)n_slots, 0);
     {   // sweep grid: measured on MI355X -- 100 MB fields (128^3 x 6) peak at 4096 blocks (6.0 TB/s; 2048: 5.5, 8192: 5.8),
         // 436 MB fields (128^3 x 26) want 2-3 float4 per thread (49152 blocks: 6.1 TB/s; 32768: 5.9; 4096: 4.6)
@@ -584,6 +585,7 @@ int wa_acs_begin(wa_acs *s, const wa_acs_params *p, int32_t n_problems, const in
     s->gens_enqueued = 0;
     s->conv_until = 0;
     s->conv_prev_whole = false;
+    s->conv_owed_flush = s->conv_owed_gen = -1;
     s->ran_before = false;
     return WA_OK;
 }
@@ -791,8 +793,9 @@ static void launch_fused(wa_acs *s, WaGroupRun &G, const float *src, float *dst,
 // Measured and dropped (profiles/HISTORY.md): sweep on a second stream beside the walk OF THE SAME SEARCH, sweep + rank + mark inside
 // the walk launch, rank beside the sweep, in-place sweep, hipGraph replay of the loop, non-temporal hints on the sweep -- all
 // bit-identical, all slower.
+// owed: the generation behind a carried window (a lone dense 6-neighbour search on the fused path): its sweep pays the window's evaporations too (WA_GEN_OWED)
 static void enqueue_generation(wa_acs *s, WaGroupRun &G, int32_t gen, bool last_of_call, bool sampled, bool fused, int32_t chunks,
-                               size_t shmem, int32_t P_all)
+                               size_t shmem, int32_t P_all, bool owed = false)
 {
     wa_ctx *ctx = s->ctx;
     const int32_t P = G.P;
@@ -892,14 +895,14 @@ static void enqueue_generation(wa_acs *s, WaGroupRun &G, int32_t gen, bool last_
 #define WA_DBG_SYNC(name) do { if (dbg_sync) { fprintf(stderr, "[dbg] %s gen %d slot0 %d P %d ...", name, gen, G.slot0, P); fflush(stderr); hipError_t e_ = hipStreamSynchronize(st); fprintf(stderr, " %s\n", hipGetErrorString(e_)); } } while (0)
     WA_DBG_SYNC("walk");
     if (fused) {
-        launch_fused(s, G, src, dst, gen, sampled || s->prof_sweep_all);
+        launch_fused(s, G, src, dst, owed ? gen | WA_GEN_OWED : gen, sampled || s->prof_sweep_all);
         WA_DBG_SYNC("fused sweep+rank+mark");
         if (!s->lazy) G.cur ^= 1;
         G.V.pher = dst;
         WA_HASH_AT(1);
         e = prof_open(s, st, WA_K_DEPOSIT, sampled);
         if (s->nb == 26) k_apply_table26<<<dim3((unsigned)(1 + WA_TABLE26_BLOCKS + mark_blocks(s)), (unsigned)P), 256, 0, st>>>(G.V, s->R);
-        else { const int32_t SL = P >= 32 ? 1 : 2, TB = P >= 32 ? 32 : WA_TABLE_BLOCKS_MAX; k_apply_table<<<dim3((unsigned)(TB + ((mark_blocks(s) >> 3) << SL)), (unsigned)P), 256, 0, st>>>(G.V, s->R, SL, TB, gen); }
+        else { const int32_t SL = P >= 32 ? 1 : 2, TB = P >= 32 ? 32 : WA_TABLE_BLOCKS_MAX; k_apply_table<<<dim3((unsigned)(TB + ((mark_blocks(s) >> 3) << SL)), (unsigned)P), 256, 0, st>>>(G.V, s->R, SL, TB, owed ? gen | WA_GEN_OWED : gen); }
         prof_close(st, e);
         WA_DBG_SYNC("apply+table");
         WA_HASH_AT(2);
@@ -981,18 +984,20 @@ static int32_t conv_window_at(const wa_acs *s, int32_t gen, int32_t gen_last)
     }
     return W < 0 ? 0 : W;
 }
-static hipError_t launch_converged(wa_acs *s, WaGroupRun &G, int32_t gen, int32_t W)
+// judge: the launch also tests generation gen + W (the host reads its verdict and may leave the flush's sweep out: WA_GEN_OWED)
+static hipError_t launch_converged(wa_acs *s, WaGroupRun &G, int32_t gen, int32_t W, bool judge)
 {
     G.V.pher = s->pher_buf[G.cur] + (int64_t)G.slot0 * s->D.pher_stride;   // the field as generation `gen` finds it
     uint32_t *verdict = s->conv_readback && s->h_verdict ? s->h_verdict + G.slot0 : nullptr;
     k_converged_run<<<dim3((unsigned)s->conv_blocks, (unsigned)G.P), WA_CONV_THREADS, wa_conv_lds_bytes(s->D.conv_nodes, s->conv_blocks), G.st>>>(
-        G.V, s->R, gen, W, verdict, s->conv_seq & 0xffffffu);
+        G.V, s->R, gen, W, verdict, s->conv_seq & 0xffffffu, judge ? 1 : 0);
     for (int32_t q = 0; q < G.P; q++) s->conv_enqueued[(size_t)(G.slot0 + q)]++;
     return hipGetLastError();
 }
 // The verdict of the window just enqueued for a lone search (slot 0, sequence number conv_seq): j, the generations it committed, or -1 when the wait is
 // given up -- the stream has drained without the word changing, or WA_CONVERGED_WAIT_US (default 200 000: far beyond any window; 0 = never wait) have
 // passed.  The caller then enqueues every generation of the window, which is right for any j: a lost verdict costs time, never results.
+// s->conv_carried: the word's WA_CONV_CARRIED bit (false when the wait is given up).
 #define WA_CONV_QUERY_US 2000
 static int32_t conv_verdict(wa_acs *s, hipStream_t st, int32_t W)
 {
@@ -1000,6 +1005,8 @@ static int32_t conv_verdict(wa_acs *s, hipStream_t st, int32_t W)
     const uint32_t *word = s->h_verdict;
     s->conv_host[0]++;
     int32_t j = -1;
+    uint32_t got = 0;
+    s->conv_carried = false;
     if (s->conv_wait_us > 0) {
         // the word is polled; the clock is read every 256 polls, and the stream is looked at only every WA_CONV_QUERY_US of waiting: hipStreamQuery is not
         // free for the queue it asks about, and a verdict is never later than the work in front of its window
@@ -1007,7 +1014,7 @@ static int32_t conv_verdict(wa_acs *s, hipStream_t st, int32_t W)
         int64_t next_query = WA_CONV_QUERY_US;
         for (uint32_t spin = 1;; spin++) {
             uint32_t v = __atomic_load_n(word, __ATOMIC_ACQUIRE);
-            if ((v >> 8) == want) { j = (int32_t)(v & 0xffu); break; }
+            if ((v >> 8) == want) { got = v; j = (int32_t)(v & 0x7fu); break; }
             if (spin & 255u) { __builtin_ia32_pause(); continue; }
             const int64_t waited = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
             if (waited > s->conv_wait_us) break;
@@ -1016,12 +1023,13 @@ static int32_t conv_verdict(wa_acs *s, hipStream_t st, int32_t W)
                 const hipError_t q = hipStreamQuery(st);
                 if (q == hipErrorNotReady) { (void)hipGetLastError(); continue; }
                 v = __atomic_load_n(word, __ATOMIC_ACQUIRE);   // drained (or failed): the kernel is over, the word says so or never will
-                if ((v >> 8) == want) j = (int32_t)(v & 0xffu);
+                if ((v >> 8) == want) { got = v; j = (int32_t)(v & 0x7fu); }
                 break;
             }
         }
     }
     if (j < 0 || j > W) { s->conv_host[3]++; return -1; }
+    s->conv_carried = j == W && (got & WA_CONV_CARRIED) != 0;
     return j;
 }
 
@@ -1100,17 +1108,29 @@ int wa_acs_pipeline_info(const wa_acs *s, int32_t *groups_last_run)
 // The flush of generation `gen` of a lone search, SPECULATIVE (WA_GEN_SPEC): enqueued directly behind a window [g, gen] before the host has its verdict.
 // The two launches flush if the window committed whole and return at their top otherwise.  No walk launch: the walk of a flush generation returns at
 // its top either way.  The caller has flipped G.cur as the generations in front of `gen` would have
-static hipError_t enqueue_spec_flush(wa_acs *s, WaGroupRun &G, int32_t gen)
+// gflags: WA_GEN_SPEC, and WA_GEN_OWED where a carried window's evaporations may stay owed (the device knows whether the window was carried; the host
+// learns it from the verdict)
+static hipError_t enqueue_spec_flush(wa_acs *s, WaGroupRun &G, int32_t gen, int32_t gflags)
 {
     const int64_t off = (int64_t)G.slot0 * s->D.pher_stride;
     float *src = s->pher_buf[G.cur] + off, *dst = s->pher_buf[G.cur ^ 1] + off;
     G.V.pher = src;
     G.V.prev_pher = dst;
-    launch_fused(s, G, src, dst, gen | WA_GEN_SPEC, false);
+    launch_fused(s, G, src, dst, gen | gflags, false);
     G.cur ^= 1;
     G.V.pher = dst;
     const int32_t SL = 2, TB = WA_TABLE_BLOCKS_MAX;   // (one search: as enqueue_generation)
-    k_apply_table<<<dim3((unsigned)(TB + ((mark_blocks(s) >> 3) << SL)), (unsigned)G.P), 256, 0, G.st>>>(G.V, s->R, SL, TB, gen | WA_GEN_SPEC);
+    k_apply_table<<<dim3((unsigned)(TB + ((mark_blocks(s) >> 3) << SL)), (unsigned)G.P), 256, 0, G.st>>>(G.V, s->R, SL, TB, gen | gflags);
+    return hipGetLastError();
+}
+// The flush of generation `gen` behind a window the host knows was carried: its evaporations stay owed, so all that is left of the flush are the rows
+// of the replay table and the reset of the straggler arrivals -- the table blocks of k_apply_table alone.  The buffers are flipped as by any generation
+static hipError_t enqueue_owed_rows(wa_acs *s, WaGroupRun &G, int32_t gen)
+{
+    G.cur ^= 1;
+    G.V.pher = s->pher_buf[G.cur] + (int64_t)G.slot0 * s->D.pher_stride;
+    const int32_t SL = 2, TB = WA_TABLE_BLOCKS_MAX;
+    k_apply_table<<<dim3((unsigned)TB, (unsigned)G.P), 256, 0, G.st>>>(G.V, s->R, SL, TB, gen | WA_GEN_OWED);
     return hipGetLastError();
 }
 
@@ -1177,6 +1197,7 @@ int wa_acs_run(wa_acs *s, int32_t n_generations)
 #endif
     const bool conv = n_generations > 1 && conv_rule(s, fused) && conv_scratch(s);
     const bool readback = conv && s->conv_readback && s->h_verdict && P == 1;   // (one search is one group)
+    const bool owed_on = readback && s->conv_owed;   // carried windows leave their evaporations to the sweep of the generation behind them
     const int32_t gen_last = s->gens_enqueued + n_generations - 1;
     const int32_t NG = n_generations > 0 ? pipe_groups(s, P) : 1;
     s->last_groups = NG;
@@ -1210,14 +1231,33 @@ int wa_acs_run(wa_acs *s, int32_t n_generations)
         const bool sampled = s->prof && ((s->gens_enqueued % s->prof_every) == 0);
         const int32_t gen = s->gens_enqueued;  // generations since wa_acs_begin
         int32_t ask = 0;                       // the window whose verdict the host reads (generations it covers)
+        bool owe = false;                      // ... and whose evaporations may stay owed: the generation behind it is a full one whatever happens
+        if (gen == s->conv_owed_flush) {
+            // the last generation of a window the host has read "carried" of: the rows launch alone, and the next generation pays the evaporations
+            s->conv_owed_flush = -1;
+            const hipError_t re = enqueue_owed_rows(s, groups[0], gen);
+            if (re != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_acs_run: rows of a carried window: %s", hipGetErrorString(re));
+            s->conv_owed_gen = gen + 1;
+            s->gens_enqueued++;
+            continue;
+        }
+        const bool owed = gen == s->conv_owed_gen;
+        if (owed) {
+            s->conv_owed_gen = -1;
+            s->conv_owed_info[1]++;
+            s->conv_owed_info[(s->conv_owed_reps & 1) ? 3 : 4]++;
+        }
         if (conv && gen >= s->conv_until) {
             const int32_t W = conv_window_at(s, gen, gen_last);
             if (W >= 1) {
                 s->conv_seq++;
                 // a lone search: a window of three generations or more may commit generations whose launches need not be enqueued at all
                 if (readback && W >= 3) ask = W;
+                // (a generation in front of which the next window is enqueued is no full generation, and that window would load the path's records from a
+                //  field that has not got them: only the last generation of the call and a stamped one have no window in front)
+                owe = owed_on && ask && conv_window_at(s, gen + W, gen_last) < 1;
                 for (int32_t k = 0; k < NG; k++) {
-                    const hipError_t le = launch_converged(s, groups[(size_t)k], gen, W);
+                    const hipError_t le = launch_converged(s, groups[(size_t)k], gen, W, owe);
                     if (le != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_acs_run: k_converged_run: %s", hipGetErrorString(le));
                 }
                 s->conv_until = gen + W;
@@ -1230,20 +1270,26 @@ int wa_acs_run(wa_acs *s, int32_t n_generations)
             WaGroupRun &G = groups[0];
             const int cur0 = G.cur;
             G.cur ^= (ask - 1) & 1;
-            const hipError_t fe = enqueue_spec_flush(s, G, gen + ask - 1);
+            const hipError_t fe = enqueue_spec_flush(s, G, gen + ask - 1, WA_GEN_SPEC | (owe ? WA_GEN_OWED : 0));
             if (fe != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_acs_run: speculative flush: %s", hipGetErrorString(fe));
             known = conv_verdict(s, G.st, ask);
             if (known < 0) {
                 // given up, and the launches behind the window flush or not: the host has to know which before it enqueues anything else
                 HIPC(ctx, hipStreamSynchronize(G.st));
                 const uint32_t v = __atomic_load_n(s->h_verdict, __ATOMIC_ACQUIRE);
-                if ((v >> 8) != (s->conv_seq & 0xffffffu) || (int32_t)(v & 0xffu) > ask) return fail(ctx, WA_ERR_DEVICE, "wa_acs_run: a window ended without its verdict");
-                known = (int32_t)(v & 0xffu);
+                if ((v >> 8) != (s->conv_seq & 0xffffffu) || (int32_t)(v & 0x7fu) > ask) return fail(ctx, WA_ERR_DEVICE, "wa_acs_run: a window ended without its verdict");
+                known = (int32_t)(v & 0x7fu);
+                s->conv_carried = known == ask && (v & WA_CONV_CARRIED) != 0;
             }
             if (known == ask) {   // every generation of the window is in the field's books: none of gen .. gen+ask-2 is enqueued
                 s->gens_enqueued += ask;
                 s->conv_host[1] += (uint64_t)(ask - 1);
                 g += ask - 1;
+                if (owe) {
+                    // carried: the two launches left the sweep out and put the rows in place; generation gen + ask pays.  Whole but not carried: they flushed
+                    if (s->conv_carried) { s->conv_owed_info[0]++; s->conv_owed_gen = gen + ask; s->conv_owed_reps = ask + 1; }
+                    else s->conv_owed_info[2]++;
+                }
                 continue;
             }
             G.cur = cur0;         // cancelled: the two launches return at their top; on as without them
@@ -1251,7 +1297,7 @@ int wa_acs_run(wa_acs *s, int32_t n_generations)
             s->conv_prev_whole = false;
         }
         for (int32_t k = 0; k < NG; k++)
-            enqueue_generation(s, groups[(size_t)k], gen, g + 1 == n_generations, sampled, fused, chunks, shmem, P);
+            enqueue_generation(s, groups[(size_t)k], gen, g + 1 == n_generations, sampled, fused, chunks, shmem, P, owed);
         s->gens_enqueued++;
         if (ask) {
             // Generation gen's launches (a full generation, the flush or launches that return at once, whichever the device finds) are behind the window: the
@@ -1260,6 +1306,12 @@ int wa_acs_run(wa_acs *s, int32_t n_generations)
             // next, under its own number) finds src / dst and the path arrays' parity as ever.  The next window stays where it was: conv_until
             const int32_t j = known != -2 ? known : conv_verdict(s, groups[0].st, ask);
             s->conv_prev_whole = j == ask;
+            if (owe && j == ask) {
+                // carried: the flush (generation gen + ask - 1, enqueued behind the generations skipped below) is the rows launch alone.  Whole but not
+                // carried: an ant leaves the path in generation gen + ask and reads the field: today's flush
+                if (s->conv_carried) { s->conv_owed_info[0]++; s->conv_owed_flush = gen + ask - 1; s->conv_owed_reps = ask + 1; }
+                else s->conv_owed_info[2]++;
+            }
             for (int32_t t = 2; t < j; t++) {
                 groups[0].cur ^= 1;
                 s->gens_enqueued++;
@@ -1653,6 +1705,15 @@ int wa_acs_evaporate(wa_acs *s, int32_t slot, float rho, int32_t repeats)
 // What the host did with the windows' verdicts since the solver was created (a lone search only; all zero with WA_CONVERGED_READBACK=0, for batches and
 // for solvers that run no windows): [0] verdicts the host went to read, [1] generations whose launches were not enqueued, [2] speculative flushes
 // cancelled (the window in front of them did not commit whole), [3] waits given up, of [0].
+// Owed evaporations (WA_CONVERGED_OWED; a lone search whose verdicts the host reads, all zero otherwise): [0] whole windows the host read "carried" of --
+// every ant of the generation behind them replays the path too --, [1] generations enqueued whose sweep paid a carried window's evaporations with its
+// own, [2] whole windows that were not carried (flushed as ever), [3] / [4] of [1], the sweeps that ran out of place / in place.
+int wa_acs_converged_owed_info(wa_acs *s, uint64_t out[5])
+{
+    if (!s || !out) return WA_ERR_ARG;
+    for (int i = 0; i < 5; i++) out[i] = s->conv_owed_info[i];
+    return WA_OK;
+}
 int wa_acs_converged_host_info(wa_acs *s, uint64_t out[4])
 {
     if (!s || !out) return WA_ERR_ARG;

@@ -200,6 +200,12 @@ struct wa_acs {
     uint32_t conv_seq = 0;               // sequence number of the last window enqueued
     uint64_t conv_host[4] = {0, 0, 0, 0};   // wa_acs_converged_host_info
     bool conv_spec = true;               // WA_CONVERGED_SPECULATE (read at creation): behind a window that committed whole, the next window's flush is enqueued before its verdict
+    bool conv_owed = true;               // WA_CONVERGED_OWED (read at creation): a carried window's evaporations are left to the sweep of the generation behind it
+    bool conv_carried = false;           // the verdict last read said "carried" (WA_CONV_CARRIED)
+    int32_t conv_owed_flush = -1;        // the generation whose flush is the rows launch alone (the last of a carried window), -1: none
+    int32_t conv_owed_gen = -1;          // the generation whose launches carry WA_GEN_OWED (the one behind a carried window), -1: none
+    int32_t conv_owed_reps = 0;          // multiplications its sweep applies (the window's length + 1)
+    uint64_t conv_owed_info[5] = {0, 0, 0, 0, 0};   // wa_acs_converged_owed_info
     bool conv_prev_whole = false;        // the last window of the running search whose verdict was read committed whole
 };
 
