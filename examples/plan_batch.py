@@ -132,7 +132,7 @@ def plan_pose(grid, point_ids, dirs, tool, max_turn, rank=0, world=1, shortcut=0
     waypoints and the costs come from wa_grid_pose_shortcut instead: a stretch is straightened only where one of its two end directions
     stays open in every voxel the straight segment touches, the turns at the waypoints keep MAX_TURN, and a hop that cannot be held
     stays the lattice step it was.  Its summary, its total length and the total of the plain shortcut of the same paths (this rank's
-    pairs) are left in plan_pose.last_pose_shortcut.
+    pairs) are left in plan_pose.last_pose_shortcut, the hold of every shortened segment in plan_pose.last_holds (what --pose-fit fits with).
     costs (--pose-turn-costs, an api.pose_costs): the pair paths come from wa_grid_pose_weighted_paths instead, which charges every
     step its turn and the voxel it enters; the pair costs stay lengths.  plan_pose.last_totals holds turn_totals per planner (this
     rank's pairs): of wa_grid_pose_paths always, of the weighted planner beside it when it is used."""
@@ -150,16 +150,16 @@ def plan_pose(grid, point_ids, dirs, tool, max_turn, rank=0, world=1, shortcut=0
                                                               cost_total=int(hops[hops >= 0].sum())))
     ids_all = [np.zeros(0, np.int64) if p is None else p for p in ids_all]
     wps, lengths = api.shortcut_paths(grid, ids_all, shortcut or 1)
-    plan_pose.last_pose_shortcut = None
+    plan_pose.last_pose_shortcut, holds = None, None
     if pose_shortcut:
         plain_total = float(lengths.sum())
         ks_some = [np.zeros(0, np.int32) if k is None else k for k in ks_all]
-        wps, _, _, lengths, summary = api.pose_shortcut_paths(grid, dirs, tool, max_turn, ids_all, ks_some, shortcut)
+        wps, _, holds, lengths, summary = api.pose_shortcut_paths(grid, dirs, tool, max_turn, ids_all, ks_some, shortcut)
         plan_pose.last_pose_shortcut = dict({k: summary[k] for k in ("n_waypoints", "n_held_start", "n_held_end", "n_unheld", "max_hold_turn")},
                                             length_total=float(lengths.sum()), plain_length_total=plain_total)
     cost = np.zeros((P, P), np.float64)
     paths = {}
-    plan.last_slots, plan.last_create_s, plan.last_batch_s, plan.last_shortcut, plan_pose.last_dirs = 0, 0.0, [], {}, {}
+    plan.last_slots, plan.last_create_s, plan.last_batch_s, plan.last_shortcut, plan_pose.last_dirs, plan_pose.last_holds = 0, 0.0, [], {}, {}, {}
     for q, k in enumerate(mine):
         i, j = pairs[k]
         cost[i, j] = cost[j, i] = lengths[q] if hops[q] >= 0 else np.inf
@@ -167,6 +167,8 @@ def plan_pose(grid, point_ids, dirs, tool, max_turn, rank=0, world=1, shortcut=0
         plan_pose.last_dirs[(i, j)] = ks_all[q]
         if shortcut:
             plan.last_shortcut[(i, j)] = wps[q]
+        if holds is not None:
+            plan_pose.last_holds[(i, j)] = holds[q]
     return cost, paths, len(mine)
 
 
@@ -329,10 +331,14 @@ def diagonal_report(grid, pts, paths, short, shortcut):
     return q
 
 
-def smooth(ctx, grid, segs, wsegs, rev, fit=None):
+def smooth(ctx, grid, segs, wsegs, rev, fit=None, pose_fit=None):
     """main.cpp:283-352 on the device: the tour's segments stitched, then the two smoothing passes; wsegs (--shortcut): the shortened
     segments, whose waypoints are then the coarse points of the cubic fit.  fit = (metal grid, max_level, dump path or None) (--fit):
     the curve is wa_grid_fit_trajectory's instead, control points ON the waypoints' polyline, refined until its samples clear the metal.
+    pose_fit = (dirs, tool, hold segments) (--pose-fit): the curve is wa_grid_pose_fit_trajectory's, refined until one of the planned holds
+    stays open along every piece of it; the holds are stitched as the waypoints are (a reversed segment's holds reversed, the
+    zero-length leg between two segments unheld).  Its summary goes beside the plain fit's; the plain fit's samples and the directions
+    per segment are left in smooth.fit_samples and smooth.seg_dir.
     Returns (samples, ok flags, what goes into the JSON)."""
     info = {}
     path = api.Trajectory.stitch(grid, segs, rev)
@@ -354,6 +360,18 @@ def smooth(ctx, grid, segs, wsegs, rev, fit=None):
         info.update(shortened_length_total=float(lens.sum()), lattice_length_total=float(lattice.sum()))
         info.update(fit=dict(summary, max_level=max_level, n_hit_plain_fit=int(before)), waypoints=len(wpath), stitched_nodes=len(path),
                     trajectory_samples=len(traj), trajectory_length=float(np.linalg.norm(np.diff(traj, axis=0), axis=1).sum()))
+        if pose_fit is not None:
+            dirs, tool, hsegs = pose_fit
+            parts = []
+            for h, r in zip(hsegs, rev):
+                parts += [np.asarray(h[::-1] if r else h, np.int32), np.full(1, -1, np.int32)]
+            holds = np.concatenate(parts)[:-1]
+            t0 = time.perf_counter()
+            _, psamples, _, seg_dir, _, psummary = wpath.pose_fit(metal, dirs, tool, holds, degree=3, max_level=max_level, n_samples=6001)
+            smooth.fit_samples, smooth.seg_dir = traj, seg_dir
+            traj = psamples.points()
+            info.update(pose_fit=dict(psummary, max_level=max_level, n_held_legs=int((holds >= 0).sum()), t_s=time.perf_counter() - t0),
+                        trajectory_length=float(np.linalg.norm(np.diff(traj, axis=0), axis=1).sum()))
         return traj, np.ones(len(traj), np.uint8), info
     if wsegs is not None:
         # the shortened segments stitched the same way: their waypoints are the coarse points of the cubic fit
@@ -426,12 +444,13 @@ def torch_grid_report(base, count, paths, paths_without, shortcut):
     return dict(totals(paths), without=totals(paths_without) if paths_without is not None else None)
 
 
-def torch_stage(ctx, metal, xyz, stops, K, max_turn=-1):
+def torch_stage(ctx, metal, xyz, stops, K, max_turn=-1, want=None):
     """Torch axes along the trajectory's samples (wa_traj_tool_axes): one of K directions of a cone around +z per sample so that a
     300 mm torch body (24 beads) stays clear of the metal.  Legs: the travel moves between the tour's stops, cut at the sample nearest to
     each stop.  Wish: the torch points down the gradient of the distance field (at the nearest metal), so the body -- a direction runs
     from the tip into the body -- is wished along the gradient itself; computed here in numpy.  Beside the plan, the check of the
-    linearly interpolated, renormalised axes half-way between consecutive samples: what a controller that interpolates would send."""
+    linearly interpolated, renormalised axes half-way between consecutive samples: what a controller that interpolates would send.
+    want (--pose-fit): the wish per sample instead, the direction the fit found open along the sample's segment (zero rows: none)."""
     curve = api.Trajectory.from_points(ctx, xyz)
     n = len(xyz)
     cuts = [0]
@@ -441,8 +460,9 @@ def torch_stage(ctx, metal, xyz, stops, K, max_turn=-1):
     ids = curve.clearance(metal)[0]
     d2 = metal.distance_field().astype(np.float64).reshape(metal.nz, metal.ny, metal.nx)
     gz, gy, gx = np.gradient(np.sqrt(d2))
-    want = np.stack([gx.ravel()[ids], gy.ravel()[ids], gz.ravel()[ids]], 1).astype(np.float32)
-    want[~np.isfinite(want).all(1)] = 0                          # (a grid without metal: no wish)
+    if want is None:
+        want = np.stack([gx.ravel()[ids], gy.ravel()[ids], gz.ravel()[ids]], 1).astype(np.float32)
+        want[~np.isfinite(want).all(1)] = 0                      # (a grid without metal: no wish)
     tool, dirs, length16 = torch_tool_and_cone(metal, K)
     r = curve.torch_axes(metal, dirs, tool, w_near=4, w_want=1, w_turn=8, near_add=8, max_turn=max_turn, want=want, off=off, feas=False)
     info = dict(r["summary"], K=K, n_legs=len(off) - 1, directions_used=int(len(set(r["dir"].tolist()))), tool_length16=length16)
@@ -568,6 +588,10 @@ def main():
                     help="needs --pose-paths and --shortcut: the waypoints and costs of the pair paths come from wa_grid_pose_shortcut, which "
                          "straightens a stretch only where a planned direction stays open along the whole segment and keeps MAX_TURN at the "
                          "waypoints; pose_paths.shortcut reports the held and unheld segments and the length beside the plain shortcut's")
+    ap.add_argument("--pose-fit", action="store_true",
+                    help="needs --pose-paths, --shortcut, --pose-shortcut and --fit: the trajectory comes from wa_grid_pose_fit_trajectory, "
+                         "which refines the spline until one of the holds of --pose-shortcut stays open along every piece of the sampled "
+                         "curve; its summary stands beside the plain fit's, and --torch takes the directions it found as wishes")
     ap.add_argument("--torch-keep-r2", type=int, default=16, metavar="R2",
                     help="--torch-grid: the squared radius in voxels of the bubble around every weld point inside which the grid is kept (default 16)")
     args = ap.parse_args()
@@ -598,6 +622,8 @@ def main():
             ap.error("--pose-turn-costs takes at most 4 bands")
     if args.pose_shortcut and (args.pose_paths is None or not args.shortcut):
         ap.error("--pose-shortcut needs --pose-paths and --shortcut")
+    if args.pose_fit and (not args.pose_shortcut or args.fit is None):
+        ap.error("--pose-fit needs --pose-paths, --shortcut, --pose-shortcut and --fit")
     if args.torch is not None and args.fit is None and not args.retime and args.torch_grid is None and args.pose_paths is None:
         ap.error("--torch works on the samples of --fit or --retime")
     if args.tick_poses is not None and (len(args.tick_poses) > 2 or not args.retime or args.torch is None):
@@ -707,6 +733,8 @@ def main():
         cost, paths, n_mine = plan(ctx, grid, pts, args.generations, predict, args.seed, args.slots, rank, world, lazy=args.lazy, neighbourhood=args.neighbourhood,
                                    shortcut=args.max_span if args.shortcut else 0)
     short = plan.last_shortcut
+    if args.pose_fit and comm is not None:
+        raise SystemExit("--pose-fit runs on one GPU: the holds are not gathered")
     if comm is not None:
         # every pair is owned by exactly one rank: its cost goes to every rank, its path to rank 0 (the library's own collectives)
         P = args.points
@@ -793,7 +821,8 @@ def main():
         t2 = time.perf_counter()
         segs = seg_list(paths)
         wsegs = seg_list(short) if args.shortcut else None
-        traj, ok, info = smooth(ctx, grid, segs, wsegs, rev, fit=(metal, args.fit, args.fit_dump) if args.fit is not None else None)
+        traj, ok, info = smooth(ctx, grid, segs, wsegs, rev, fit=(metal, args.fit, args.fit_dump) if args.fit is not None else None,
+                                pose_fit=(pose_dirs, pose_tool, seg_list(plan_pose.last_holds)) if args.pose_fit else None)
         out.update(info, t_trajectory_s=time.perf_counter() - t2)
         if args.retime:
             # what the controller is sent: the same curve at a fixed period, as fast as the limits allow
@@ -814,8 +843,15 @@ def main():
             cx, cy, cz = metal.coords()
             first = np.asarray([(seg[-1] if r else seg[0]) for seg, r in zip(segs, rev)] + [segs[-1][0] if rev[-1] else segs[-1][-1]], np.int64)
             stops = np.stack([cx[first % metal.nx], cy[(first // metal.nx) % metal.ny], cz[first // (metal.nx * metal.ny)]], 1)
-            out.update(torch=torch_stage(ctx, metal, np.ascontiguousarray(traj[ok.astype(bool)], np.float32), stops, args.torch,
-                                         args.pose_paths if args.pose_paths is not None else -1),
+            turn = args.pose_paths if args.pose_paths is not None else -1
+            want = None
+            if args.pose_fit:
+                # the same stage on the plain fit's samples first, then on the pose fit's with the directions it found as wishes
+                before = torch_stage(ctx, metal, np.ascontiguousarray(smooth.fit_samples, np.float32), stops, args.torch, turn)
+                out["pose_fit"].update(n_no_dir_plain_fit=before["n_no_dir"], n_over_turn_plain_fit=before["n_over_turn"])
+                per_sample = np.concatenate([smooth.seg_dir, smooth.seg_dir[-1:]])
+                want = np.where(per_sample[:, None] >= 0, pose_dirs[np.maximum(per_sample, 0)], 0).astype(np.float32)
+            out.update(torch=torch_stage(ctx, metal, np.ascontiguousarray(traj[ok.astype(bool)], np.float32), stops, args.torch, turn, want),
                        t_torch_s=time.perf_counter() - t4)
             if args.pose_paths is not None:
                 out.update(n_no_dir=out["torch"]["n_no_dir"], n_over_turn=out["torch"]["n_over_turn"])

@@ -1143,6 +1143,68 @@ int wa_grid_pose_weighted_paths(const wa_grid *g, const float *dirs, int32_t K, 
                                 const int32_t *pin_end, int32_t n_pairs, const int64_t *off, int64_t *ids_out, int32_t *dir_out,
                                 int32_t *cost_out, int32_t *len_out);
 
+/* ---- pose-aware trajectory fit: refine the spline until a planned direction stays open along it (not in the reference) ----
+ *      wa_grid_pose_shortcut returns waypoints and, per segment between them, the direction (hold) that is open in every voxel the
+ *      straight segment touches.  wa_grid_fit_trajectory turns waypoints into the B-spline the robot drives but checks the sampled curve
+ *      against the occupancy only: the curve cuts corners inside the hull of its control points, through voxels where no planned
+ *      direction fits the torch body.  This call is the loop of wa_grid_fit_trajectory with "a planned direction is open along this
+ *      piece of curve" in place of "this piece of curve is free", and it returns the direction it found for every segment.
+ *      The rules continue the numbering above; dirs, q, U(a, b), wa_tool_beads and open(v, k) are those of rules 1, 2 and 10, K = 1 ..
+ *      WA_TORCH_MAX_DIRS; "step n" is step n of wa_grid_fit_trajectory.  Integers only, except what the fit computes.
+ * 37. Input.  g, poly, degree, spacing, max_level and n_samples are wa_grid_fit_trajectory's, with the same rules; dirs, K and tool are
+ *     wa_grid_pose_shortcut's, with the same rules.  leg_hold: n - 1 int32 (host), one per leg of poly, each -1 or 0 .. K - 1: what rule
+ *     29's hold_out gives for the segments between waypoints; paths stitched end to start simply concatenate their holds.
+ *     Definition.  Steps 1 - 3, 5 and 6 of wa_grid_fit_trajectory, unchanged.  Step 4 samples the same way and looks the samples' voxels
+ *     up as wa_traj_clearance does; it then tests each segment i (samples i and i + 1):
+ *     Candidates.  Take the knot span step 5 would use for u_i, then the one for u_(i+1) (the same _findSpan after the same clamp; a
+ *     sample is skipped under the conditions step 5 skips it: _findSpan refuses, span - D < 0 or span >= the number of control points).
+ *     For each span take the control points span - D .. span in ascending order, and of each the hold of its owner leg (step 2's
+ *     owner).  Drop -1; keep the first occurrence of each value.  That leaves at most 2 (D + 1) = 8 candidates, in a defined order.
+ *     With at least one candidate, the segment's direction is the FIRST candidate c with open(w, c) for EVERY voxel w of the supercover
+ *     between the two samples' voxels (the supercover of wa_traj_clearance: tied axes stepped together, the full product set at a tie,
+ *     voxel a itself included).  If no candidate qualifies the segment is BLOCKED and its direction is -1.
+ *     Without a candidate (every owner unheld) the segment is blocked iff wa_traj_clearance would report a hit there; its direction
+ *     is -1, and it carries whatever guarantee the input had, as rule 28 says of an unheld hop.
+ *     Loop.  Blocked segments take the place of hit segments in steps 4 - 6: the loop ends when no segment is blocked, when no level
+ *     rose, or after round 32.
+ * 38. Outputs.  *spline_out, *samples_out (may be NULL) and leg_level_out (may be NULL) as wa_grid_fit_trajectory returns them.
+ *     seg_dir_out (n_samples - 1 int32, host, may be NULL): the direction of every segment of the last round, -1 where it has none.
+ *     blocked_out (n_samples - 1 bytes, host, may be NULL): 1 where that segment is blocked.  Summary (required): rounds,
+ *     max_level_used, n_legs, n_legs_at_cap, n_cps as in wa_fit_summary with "blamed" meaning blamed for a blocked segment;
+ *     n_blocked_first = the blocked segments of round 1; final = the OCCUPANCY clearance summary of the final samples, exactly what
+ *     wa_traj_clearance reports for them; n_blocked and first_blocked (-1 without one) of the last round; n_no_candidate = its segments
+ *     without a candidate; n_dir_changes = the pairs of consecutive segments whose directions are both >= 0 and differ; max_dir_turn =
+ *     the largest U(q_c, q_c') over such pairs, 0 without one.  As for the fit, n_blocked == 0 is not promised: rounds == 32 or
+ *     n_legs_at_cap > 0 with n_blocked > 0 tell the caller so.
+ *     Identities.  (a) With a tool of one bead with dist16 = 0 and r2 = 0 and every hold >= 0, open(v, k) = v is free, so the spline,
+ *     the samples, the levels, rounds, n_cps, n_legs_at_cap, n_blocked_first (= n_hit_first) and final are the bytes of
+ *     wa_grid_fit_trajectory.  (b) The same holds with every hold -1, whatever the tool.  (c) A segment that is not blocked and has a
+ *     direction c >= 0 has c open on its whole cover, so every voxel of the cover is free.
+ * 39. Errors.  WA_ERR_ARG, before anything is written: every argument error of wa_grid_fit_trajectory (NULL g / poly / sum /
+ *     spline_out, different contexts, n < 2, degree, spacing, max_level, n_samples, a coordinate that is not finite, more than 2^24
+ *     control points); the errors of rule 16 for dirs, K and the tool; a NULL leg_hold; a hold outside -1 .. K - 1.  WA_ERR_ALLOC when
+ *     the masks or the device buffers do not fit.
+ * Same bytes on every call; everything runs on the context's stream; g is not modified.  The masks are recomputed by every call, once,
+ * before round 1, in a block of the context's arena (W * 8 * n bytes, rule 16); nothing is cached with the grid. */
+typedef struct {
+    int32_t rounds;          /* fits made (>= 1) */
+    int32_t max_level_used;  /* the highest level of any leg */
+    int64_t n_legs;          /* n - 1 */
+    int64_t n_legs_at_cap;   /* legs at max_level that were still blamed in the last round */
+    int64_t n_cps;           /* control points of the final spline */
+    int64_t n_blocked_first; /* blocked segments of round 1: the unrefined fit on the same control spacing */
+    wa_clearance_summary final; /* of the final samples against g's occupancy */
+    int64_t n_blocked;       /* blocked segments of the last round: 0 is the success case */
+    int64_t first_blocked;   /* the first of them, -1 without one */
+    int64_t n_no_candidate;  /* segments of the last round whose owner legs are all unheld */
+    int64_t n_dir_changes;   /* consecutive segments with directions >= 0 that differ */
+    int64_t max_dir_turn;    /* largest U over those pairs; 0 without one */
+} wa_pose_fit_summary;
+int wa_grid_pose_fit_trajectory(const wa_grid *g, const wa_traj *poly, int32_t degree, float spacing, int32_t max_level, int64_t n_samples,
+                                const float *dirs, int32_t K, const wa_tool_beads *tool, const int32_t *leg_hold, int32_t *leg_level_out,
+                                wa_bspline **spline_out, wa_traj **samples_out, int32_t *seg_dir_out, uint8_t *blocked_out,
+                                wa_pose_fit_summary *sum);
+
 #ifdef __cplusplus
 }
 #endif

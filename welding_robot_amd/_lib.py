@@ -100,6 +100,12 @@ class PoseShortcutSummary(C.Structure):
                 ("n_held_end", C.c_int64), ("n_unheld", C.c_int64), ("max_hold_turn", C.c_int64)]
 
 
+class PoseFitSummary(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("max_level_used", C.c_int32), ("n_legs", C.c_int64), ("n_legs_at_cap", C.c_int64),
+                ("n_cps", C.c_int64), ("n_blocked_first", C.c_int64), ("final", ClearanceSummary), ("n_blocked", C.c_int64),
+                ("first_blocked", C.c_int64), ("n_no_candidate", C.c_int64), ("n_dir_changes", C.c_int64), ("max_dir_turn", C.c_int64)]
+
+
 POSE_MAX_BANDS, POSE_COST_MAX = 4, 15
 
 
@@ -245,6 +251,8 @@ SYMBOLS = {
     "wa_grid_pose_weighted_matrix": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, C.POINTER(PoseCosts), _P, _P, _I, _P]),
     "wa_grid_pose_weighted_paths": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, C.POINTER(PoseCosts), _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "wa_grid_pose_shortcut": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, C.POINTER(PoseShortcutSummary)]),
+    "wa_grid_pose_fit_trajectory": (C.c_int, [_V, _V, _I, _F, _I, _I64, _P, _I, C.POINTER(ToolBeads), _P, _P, C.POINTER(_V), C.POINTER(_V), _P, _P,
+                                              C.POINTER(PoseFitSummary)]),
     "wa_traj_axes_smooth": (C.c_int, [_V, _V, _P, C.POINTER(ToolBeads), _P, _I, C.c_double, _I, _P, _P, _P, C.POINTER(AxesSmoothSummary)]),
     "wa_traj_axes_limits": (C.c_int, [_V, _P, C.c_double, C.c_double, C.c_double, _P, _P, C.POINTER(AxesLimitsSummary)]),
     "wa_traj_tick_axes": (C.c_int, [_V, _V, _P, C.POINTER(ToolBeads), _I, C.c_double, C.c_double, C.c_double, _P, _P, C.POINTER(_V), _P,

@@ -941,6 +941,28 @@ class Trajectory:
         summary["final"] = {k: int(getattr(s.final, k)) for k, _ in L.ClearanceSummary._fields_}
         return Bspline.adopt(self.ctx, bh, 3, degree, summary["n_cps"] - 2 * degree), Trajectory(self.ctx, th), levels, summary
 
+    def pose_fit(self, grid, dirs, tool, holds, degree=3, spacing=None, max_level=6, n_samples=6001):
+        """wa_grid_pose_fit_trajectory with this polyline: the loop of fit(), refined until one of the planned directions -- `holds`, one
+        per leg, -1 for none, as pose_shortcut_paths returns them -- is open for `tool` in every voxel each piece of the sampled curve
+        touches.  Returns (Bspline, samples Trajectory, levels int32[n-1], seg_dir int32[n_samples-1]: the direction found for every
+        segment, -1 for none, blocked uint8[n_samples-1], summary dict; summary["final"] is the occupancy clearance summary of the
+        samples, summary["n_blocked"] == 0 the success case)."""
+        spacing = grid.precision if spacing is None else spacing
+        dirs, K, tool = grid._torch_args(dirs, tool)
+        holds = np.ascontiguousarray(holds, np.int32).reshape(-1)
+        if len(holds) != len(self) - 1:
+            raise ValueError("holds needs one entry per leg")
+        levels = np.empty(max(len(self) - 1, 0), np.int32)
+        seg_dir, blocked = np.empty(max(n_samples - 1, 0), np.int32), np.empty(max(n_samples - 1, 0), np.uint8)
+        bh, th, s = C.c_void_p(), C.c_void_p(), L.PoseFitSummary()
+        self.ctx.check(self.ctx.lib.wa_grid_pose_fit_trajectory(grid.h, self.h, degree, C.c_float(spacing), max_level, n_samples, _ptr(dirs), K,
+                                                                C.byref(tool), _ptr(holds), _ptr(levels), C.byref(bh), C.byref(th),
+                                                                _ptr(seg_dir), _ptr(blocked), C.byref(s)))
+        summary = {k: int(getattr(s, k)) for k, _ in L.PoseFitSummary._fields_ if k != "final"}
+        summary["final"] = {k: int(getattr(s.final, k)) for k, _ in L.ClearanceSummary._fields_}
+        return (Bspline.adopt(self.ctx, bh, 3, degree, summary["n_cps"] - 2 * degree), Trajectory(self.ctx, th), levels, seg_dir, blocked,
+                summary)
+
     def retime(self, v_max, acc, dec, tick, a_lat=float("inf"), grid=None, v_near=0.0, near_d2=-1, v_limit=None, ticks=True):
         """wa_traj_retime with these samples: the fastest rest-to-rest speed profile under the caps (v_max, the per-sample v_limit, a_lat
         over the curvature, v_near where `grid`'s distance field is <= near_d2) and the ramps acc / dec, and the positions every `tick`

@@ -1,6 +1,7 @@
 // host_fit.inc -- C ABI: the trajectory fit that refines its control polygon until the sampled curve clears the grid
 // (included by weldacs.hip inside extern "C").  Everything between the arguments and the results stays on the device, on the
 // context's stream; per round the host reads one WaFitRec (the next fit's size, the hit count, whether a level changed).
+// The loop itself is fit_run, which takes the round's segment test as a callable: wa_grid_pose_fit_trajectory (host_pose_fit.inc) runs it too.
 struct FitBuffers {
     DevBuf<int32_t> level, owner, d2;
     DevBuf<uint8_t> mark, hit;
@@ -50,27 +51,37 @@ static hipError_t fit_spline_room(wa_ctx *ctx, FitBuffers &B, int32_t degree, lo
     return e;
 }
 
-int wa_grid_fit_trajectory(const wa_grid *g, const wa_traj *poly, int32_t degree, float spacing, int32_t max_level, int64_t n_samples,
-                           int32_t *leg_level_out, wa_bspline **spline_out, wa_traj **samples_out, wa_fit_summary *sum)
+// the segment test of a round: enqueues on the context's stream what fills B.hit (one byte per segment, non-zero: refine around it) and
+// the record's acc[1] (the first such segment) and acc[2] (their number) from the round's sample voxels B.ids
+using FitSegTest = std::function<hipError_t(const FitBuffers &B, const WaSpline &S, float dt)>;
+
+// the arguments every fit shares, behind the caller's check of g: 0 or WA_ERR_ARG
+static int fit_check(wa_ctx *ctx, const char *fn, const wa_traj *poly, const void *sum, const void *spline_out, int32_t degree, float spacing,
+                     int32_t max_level, int64_t n_samples)
 {
-    WaDevGuard dev_guard_(g ? g->ctx : nullptr);
-    if (!dev_guard_.ok) return WA_ERR_DEVICE;   // the context's device could not be made current
-    if (!g) return WA_ERR_ARG;
+    if (!poly || !sum || !spline_out) return fail(ctx, WA_ERR_ARG, "%s: NULL polyline, summary or spline output", fn);
+    if (poly->ctx != ctx) return fail(ctx, WA_ERR_ARG, "%s: polyline and grid belong to different contexts", fn);
+    if (poly->n < 2) return fail(ctx, WA_ERR_ARG, "%s: a polyline needs at least 2 points", fn);
+    if (degree != 2 && degree != 3) return fail(ctx, WA_ERR_ARG, "%s: degree must be 2 or 3", fn);
+    if (!(spacing > 0.0f) || !isfinite(spacing)) return fail(ctx, WA_ERR_ARG, "%s: spacing must be finite and > 0", fn);
+    if (max_level < 0 || max_level > WA_FIT_MAX_LEVEL) return fail(ctx, WA_ERR_ARG, "%s: max_level must be 0..8", fn);
+    if (n_samples < 2 || n_samples > ((int64_t)1 << 33)) return fail(ctx, WA_ERR_ARG, "%s: n_samples must be 2..2^33", fn);
+    if (poly->n - 1 > WA_FIT_MAX_CPS) return fail(ctx, WA_ERR_ARG, "%s: more than 2^24 control points", fn);
+    return WA_OK;
+}
+
+// The loop both fits run, behind fit_check: control polygon -> fit -> sample -> `test` -> blame -> refine, until the test marks no
+// segment or nothing can be refined.  Leaves the last round's spline and samples in B, its levels in *lv, its record in *rec_out and the
+// summary's fields in *s (n_hit_first and final's segment terms are whatever `test` counted).  Nothing of the caller's is written.
+static int fit_run(const wa_grid *g, const char *fn, const wa_traj *poly, int32_t degree, float spacing, int32_t max_level, int64_t n_samples,
+                   const FitSegTest &test, FitBuffers &B, wa_fit_summary *s_out, WaFitRec *rec_out, std::vector<int32_t> *lv)
+{
     wa_ctx *ctx = g->ctx;
-    if (!poly || !sum || !spline_out) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: NULL polyline, summary or spline output");
-    if (poly->ctx != ctx) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: polyline and grid belong to different contexts");
-    if (poly->n < 2) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: a polyline needs at least 2 points");
-    if (degree != 2 && degree != 3) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: degree must be 2 or 3");
-    if (!(spacing > 0.0f) || !isfinite(spacing)) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: spacing must be finite and > 0");
-    if (max_level < 0 || max_level > WA_FIT_MAX_LEVEL) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: max_level must be 0..8");
-    if (n_samples < 2 || n_samples > ((int64_t)1 << 33)) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: n_samples must be 2..2^33");
     const long long n_legs = poly->n - 1;
-    if (n_legs > WA_FIT_MAX_CPS) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: more than 2^24 control points");
     WaField F;
     int rc = grid_field(g, &F);
     if (rc) return rc;
 
-    FitBuffers B;
     const long long n_seg = n_samples - 1;
     hipError_t e = B.level.alloc((size_t)n_legs);
     e = e ? e : B.mark.alloc((size_t)n_legs);
@@ -80,7 +91,7 @@ int wa_grid_fit_trajectory(const wa_grid *g, const wa_traj *poly, int32_t degree
     e = e ? e : B.ids.alloc((size_t)n_samples);
     e = e ? e : B.d2.alloc((size_t)n_samples);
     e = e ? e : B.hit.alloc((size_t)n_seg);
-    if (e != hipSuccess) return fail(ctx, WA_ERR_ALLOC, "wa_grid_fit_trajectory: device buffers");
+    if (e != hipSuccess) return fail(ctx, WA_ERR_ALLOC, "%s: device buffers", fn);
     wa_traj *samples = nullptr;
     rc = traj_alloc(ctx, n_samples, &samples);
     if (rc) return rc;
@@ -92,8 +103,8 @@ int wa_grid_fit_trajectory(const wa_grid *g, const wa_traj *poly, int32_t degree
     WaFitRec rec;
     e = e ? e : hipMemcpyAsync(&rec, B.rec, sizeof rec, hipMemcpyDeviceToHost, ctx->stream);
     e = e ? e : hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_grid_fit_trajectory: %s", hipGetErrorString(e));
-    if (rec.bad) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: a coordinate of the polyline is not finite");
+    if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(e));
+    if (rec.bad) return fail(ctx, WA_ERR_ARG, "%s: a coordinate of the polyline is not finite", fn);
 
     wa_fit_summary s;
     memset(&s, 0, sizeof s);
@@ -101,9 +112,9 @@ int wa_grid_fit_trajectory(const wa_grid *g, const wa_traj *poly, int32_t degree
     for (int32_t round = 0;; round++) {
         // the control polygon has rec.total + 1 points: two end positions and rec.total - 1 middle points
         const long long n_cps = rec.total - 1 + 2 * degree;
-        if (rec.total > WA_FIT_MAX_CPS || n_cps > WA_FIT_MAX_CPS) return fail(ctx, WA_ERR_ARG, "wa_grid_fit_trajectory: more than 2^24 control points");
+        if (rec.total > WA_FIT_MAX_CPS || n_cps > WA_FIT_MAX_CPS) return fail(ctx, WA_ERR_ARG, "%s: more than 2^24 control points", fn);
         e = fit_spline_room(ctx, B, degree, n_cps);
-        if (e != hipSuccess) return fail(ctx, WA_ERR_ALLOC, "wa_grid_fit_trajectory: spline buffers");
+        if (e != hipSuccess) return fail(ctx, WA_ERR_ALLOC, "%s: spline buffers", fn);
         const WaSpline &S = B.b->S;
         const float fin_time = (float)(S.n_knots - 2 * degree - 1);   // the number of knot spans: the chain's step is exactly 1.0f
         const float dt = fin_time / (float)(n_samples - 1);
@@ -115,7 +126,10 @@ int wa_grid_fit_trajectory(const wa_grid *g, const wa_traj *poly, int32_t degree
         e = e ? e : bspline_launch(B.b.get(), nullptr, 0.0f, dt, n_samples, 0, B.samples->xyz, nullptr);
         if (e == hipSuccess) {
             k_clr_samples<<<(unsigned)((n_samples + 255) / 256), 256, 0, ctx->stream>>>(B.samples->xyz, n_samples, F, B.ids, B.d2, B.rec.p->acc);
-            k_clr_segments<<<(unsigned)((n_seg + 255) / 256), 256, 0, ctx->stream>>>(B.ids, n_samples, g->d, g->occ, B.hit, B.rec.p->acc);
+            e = hipGetLastError();
+        }
+        e = e ? e : test(B, S, dt);
+        if (e == hipSuccess) {
             if (degree == 2) k_fit_blame<2><<<(unsigned)((n_seg + 255) / 256), 256, 0, ctx->stream>>>(S, B.hit, n_seg, dt, B.owner, B.mark);
             else k_fit_blame<3><<<(unsigned)((n_seg + 255) / 256), 256, 0, ctx->stream>>>(S, B.hit, n_seg, dt, B.owner, B.mark);
             k_fit_bump<<<(unsigned)((n_legs + 255) / 256), 256, 0, ctx->stream>>>(B.level, B.mark, n_legs, max_level, last ? 0 : 1, B.rec);
@@ -124,7 +138,7 @@ int wa_grid_fit_trajectory(const wa_grid *g, const wa_traj *poly, int32_t degree
         e = e ? e : fit_pieces(ctx, poly, B, (double)spacing);   // (the next round's, should there be one)
         e = e ? e : hipMemcpyAsync(&rec, B.rec, sizeof rec, hipMemcpyDeviceToHost, ctx->stream);
         e = e ? e : hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_grid_fit_trajectory: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(e));
         const int64_t n_hit = (int64_t)rec.acc[2];
         if (round == 0) s.n_hit_first = n_hit;
         s.rounds = round + 1;
@@ -133,11 +147,36 @@ int wa_grid_fit_trajectory(const wa_grid *g, const wa_traj *poly, int32_t degree
     s.n_legs_at_cap = rec.at_cap;
     s.n_cps = B.b->S.n_cps;
     clr_summary_from(rec.acc, &s.final);
-    std::vector<int32_t> lv((size_t)n_legs);
-    e = hipMemcpy(lv.data(), B.level, sizeof(int32_t) * n_legs, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_grid_fit_trajectory: %s", hipGetErrorString(e));
-    for (int32_t v : lv) s.max_level_used = std::max(s.max_level_used, v);
-    if (leg_level_out) memcpy(leg_level_out, lv.data(), sizeof(int32_t) * n_legs);
+    lv->resize((size_t)n_legs);
+    e = hipMemcpy(lv->data(), B.level, sizeof(int32_t) * n_legs, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(e));
+    for (int32_t v : *lv) s.max_level_used = std::max(s.max_level_used, v);
+    *s_out = s;
+    *rec_out = rec;
+    return WA_OK;
+}
+
+int wa_grid_fit_trajectory(const wa_grid *g, const wa_traj *poly, int32_t degree, float spacing, int32_t max_level, int64_t n_samples,
+                           int32_t *leg_level_out, wa_bspline **spline_out, wa_traj **samples_out, wa_fit_summary *sum)
+{
+    WaDevGuard dev_guard_(g ? g->ctx : nullptr);
+    if (!dev_guard_.ok) return WA_ERR_DEVICE;   // the context's device could not be made current
+    if (!g) return WA_ERR_ARG;
+    wa_ctx *ctx = g->ctx;
+    const char *fn = "wa_grid_fit_trajectory";
+    int rc = fit_check(ctx, fn, poly, sum, spline_out, degree, spacing, max_level, n_samples);
+    if (rc) return rc;
+    FitBuffers B;
+    wa_fit_summary s;
+    WaFitRec rec;
+    std::vector<int32_t> lv;
+    const unsigned seg_blocks = (unsigned)((n_samples - 1 + 255) / 256);
+    rc = fit_run(g, fn, poly, degree, spacing, max_level, n_samples, [&](const FitBuffers &R, const WaSpline &, float) {
+        k_clr_segments<<<seg_blocks, 256, 0, ctx->stream>>>(R.ids, n_samples, g->d, g->occ, R.hit, R.rec.p->acc);
+        return hipGetLastError();
+    }, B, &s, &rec, &lv);
+    if (rc) return rc;
+    if (leg_level_out) memcpy(leg_level_out, lv.data(), sizeof(int32_t) * lv.size());
     B.b->set = true;
     B.b->h_valid = false;
     *spline_out = B.b.release();

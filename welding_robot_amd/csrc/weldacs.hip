@@ -42,6 +42,7 @@
 #include "pose_kernels.hpp"
 #include "pose_weighted_kernels.hpp"
 #include "pose_shortcut_kernels.hpp"
+#include "pose_fit_kernels.hpp"
 #include "ticks_kernels.hpp"
 #include "stl_text.hpp"
 #include "acs_plan.hpp"
@@ -856,6 +857,7 @@ void *wa_ctx_stream(wa_ctx *c) { return c ? (void *)c->stream : nullptr; }
 #include "host_pose.inc"
 #include "host_pose_weighted.inc"
 #include "host_pose_shortcut.inc"
+#include "host_pose_fit.inc"
 #include "host_ticks.inc"
 
 }  // extern "C"
