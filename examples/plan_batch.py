@@ -500,6 +500,60 @@ def tick_pose_stage(ctx, metal, xyz, limits, tick, omega, h, duration_free):
     return info
 
 
+def weld_pass_stage(ctx, metal, segs, rev, weld_speed, t_start, t_end, limits, tick):
+    """Weld passes in the timed trajectory (--seams --weld-passes): the stitched polyline as it stands -- segs alternates seams and the
+    travel between them, each walked in its tour direction -- cut into steps of at most half the grid precision, the sample at both
+    ends of every seam doubled.  The doubled sample at a seam's entry is a stop of t_start seconds (strike the arc), the one at its
+    exit a stop of t_end (crater fill); seam samples are capped at the weld speed and seam segments tagged 1.  wa_traj_retime_stops
+    times it, wa_traj_tick_axes_stops tags every controller tick (the axis is held straight up: the torch stage is not part of this).
+    Returns what goes into the JSON under weld_passes."""
+    v_max, acc, dec, a_lat, v_near, near_d2 = limits
+    cx, cy, cz = metal.coords()
+    step = 0.5 * float(metal.precision)
+
+    def dense(ids):
+        ids = np.asarray(ids, np.int64)
+        p = np.stack([cx[ids % metal.nx], cy[(ids // metal.nx) % metal.ny], cz[ids // (metal.nx * metal.ny)]], 1).astype(np.float64)
+        out = [p[:1]]
+        for a, b in zip(p[:-1], p[1:]):
+            m = max(1, int(np.ceil(np.linalg.norm(b - a) / step)))
+            out.append(a[None, :] + (b - a)[None, :] * (np.arange(1, m + 1, dtype=np.float64) / m)[:, None])
+            out[-1][-1] = b
+        return np.concatenate(out).astype(np.float32)
+
+    parts, dwell, tag, vlim, seam_length = [], [], [], [], 0.0
+    for k, (seg, r) in enumerate(zip(segs, rev)):
+        pts = dense(seg[::-1] if r else seg)
+        if k % 2 == 0:   # a seam: entry doubled, the pass, exit doubled
+            parts += [pts[:1], pts, pts[-1:]]
+            if k:
+                dwell.append(-1.0)   # (from the travel's last sample to the entry: no length when they are one voxel)
+                tag.append(0)
+            dwell += [t_start] + [-1.0] * (len(pts) - 1) + [t_end]
+            tag += [0] + [1] * (len(pts) - 1) + [0]
+            vlim += [weld_speed] * (len(pts) + 2)
+            seam_length += float(np.linalg.norm(np.diff(pts.astype(np.float64), axis=0), axis=1).sum())
+        else:            # travel: the seam before ends with its first sample, the seam behind begins with its last
+            pts = pts[1:-1]
+            if len(pts):
+                parts.append(pts)
+                dwell += [-1.0] * len(pts)
+                tag += [0] * len(pts)
+                vlim += [v_max] * len(pts)
+    xyz = np.concatenate(parts)
+    dwell, tag = np.asarray(dwell, np.float64), np.asarray(tag, np.uint8)
+    curve = api.Trajectory.from_points(ctx, xyz)
+    time_q, w_q, _, ticks, rs, ss = curve.retime_stops(v_max, acc, dec, tick, dwell=dwell, a_lat=a_lat, grid=metal, v_near=v_near,
+                                                       near_d2=int(near_d2), v_limit=np.asarray(vlim, np.float32))
+    q = np.tile(np.array([0, 0, 16384], np.int32), (len(xyz), 1))
+    _, _, _, _, ts = curve.tick_axes_stops(q, time_q, w_q, acc, dec, tick, seg_tag=tag, axes=False, blocked=False)
+    weld_q = int(np.diff(time_q)[tag != 0].sum())
+    return dict(n_stops=ss["n_stops"], dwell_s=ss["dwell_q"] / api.RETIME_Q, weld_s=weld_q / api.RETIME_Q,
+                travel_s=(rs["time_q"] - weld_q - ss["dwell_q"]) / api.RETIME_Q, duration_s=rs["time_q"] / api.RETIME_Q, n_ticks=rs["n_ticks"],
+                weld_ticks=ts["n_tagged"], ticks_clearance=ticks.clearance(metal)[3] if ticks is not None else None,
+                samples=len(xyz), seam_length=seam_length, weld_speed=weld_speed, t_start_s=t_start, t_end_s=t_end, tick_s=tick)
+
+
 def wait_for_device_memory(ctx, want=0.85, timeout_s=30.0):
     """A process that has just exited may still be giving its device memory back; allocations made meanwhile can end up in
     host-visible memory (measured: the whole run 4x slower).  Wait until most of the device memory is free."""
@@ -556,6 +610,10 @@ def main():
     ap.add_argument("--seams", action="store_true",
                     help="points 2k and 2k+1 are the two ends of weld seam k: order AND direction of the seams by wa_gtsp_seam_tour, started from "
                          "the seam-level ACS-TSP tour; the exact tour beside it up to 16 seams")
+    ap.add_argument("--weld-passes", type=float, nargs=3, default=None, metavar=("V", "T_START", "T_END"),
+                    help="--seams: time the stitched polyline with the weld passes in it (wa_traj_retime_stops): the torch stops T_START seconds "
+                         "where it enters a seam, welds at no more than V, stops T_END seconds where it leaves; --retime-limits and "
+                         "--retime-tick apply; reported under weld_passes")
     ap.add_argument("--seam-starts", type=int, default=1024, help="--seams: descents of the local search (start 0 is the ACS-TSP tour)")
     ap.add_argument("--torch", type=int, nargs="?", const=64, default=None, metavar="K",
                     help="after --fit or --retime: the torch axis at every sample of the trajectory, one of K directions (1 .. 256) of a cone "
@@ -645,7 +703,13 @@ def main():
     if args.seams and (args.points % 2 or args.points < 2):
         ap.error("--seams needs an even number of --points (two per seam)")
     if args.seams and (args.fit is not None or args.retime):
-        ap.error("--seams does not go together with --fit / --retime yet")
+        ap.error("--seams does not go together with --fit / --retime yet (--weld-passes times a tour of seams)")
+    if args.weld_passes is not None:
+        if not args.seams:
+            ap.error("--weld-passes needs the seams of --seams")
+        v, ts, te = args.weld_passes
+        if not (np.isfinite([v, ts, te]).all() and v > 0 and ts >= 0 and te >= 0):
+            ap.error("--weld-passes takes a weld speed > 0 and two dwells >= 0")
     rank, local_rank, world = wd.env_rank()
     ctx = api.Context(local_rank)
     comm = None
@@ -824,6 +888,11 @@ def main():
         traj, ok, info = smooth(ctx, grid, segs, wsegs, rev, fit=(metal, args.fit, args.fit_dump) if args.fit is not None else None,
                                 pose_fit=(pose_dirs, pose_tool, seg_list(plan_pose.last_holds)) if args.pose_fit else None)
         out.update(info, t_trajectory_s=time.perf_counter() - t2)
+        if args.weld_passes is not None:
+            t6 = time.perf_counter()
+            out.update(weld_passes=weld_pass_stage(ctx, metal, wsegs if args.shortcut else segs, rev, *args.weld_passes, args.retime_limits,
+                                                   args.retime_tick),
+                       t_weld_passes_s=time.perf_counter() - t6)
         if args.retime:
             # what the controller is sent: the same curve at a fixed period, as fast as the limits allow
             t3 = time.perf_counter()

@@ -752,7 +752,8 @@ int wa_grid_fit_trajectory(const wa_grid *g, const wa_traj *poly, int32_t degree
  *    entry not finite or <= 0, a coordinate that is not finite, tick not finite or tick_q outside 1 .. 2^61, the sum of L, of A, of D or
  *    of T reaching 2^61.  More than 2^31 ticks: WA_ERR_CAPACITY with *sum and the per-sample outputs filled and *ticks_out = NULL.
  * time_q_out, w_q_out, bound_out (n entries each, host) and ticks_out may be NULL.  Same bytes on every call; everything runs on the
- * context's stream; g and t are not modified.  g may be NULL: then there is no clearance cap and n_outside is 0. */
+ * context's stream; g and t are not modified.  g may be NULL: then there is no clearance cap and n_outside is 0.
+ * (Stops inside the motion -- arc start, crater fill, a turn in place: wa_traj_retime_stops, rules 40 - 42 at the end of this header.) */
 typedef struct {
     double v_max;     /* speed cap everywhere, coordinate units per second, > 0, finite */
     double acc, dec;  /* tangential acceleration / deceleration, > 0, finite */
@@ -1204,6 +1205,67 @@ int wa_grid_pose_fit_trajectory(const wa_grid *g, const wa_traj *poly, int32_t d
                                 const float *dirs, int32_t K, const wa_tool_beads *tool, const int32_t *leg_hold, int32_t *leg_level_out,
                                 wa_bspline **spline_out, wa_traj **samples_out, int32_t *seg_dir_out, uint8_t *blocked_out,
                                 wa_pose_fit_summary *sum);
+
+/* ---- weld passes in the timed trajectory: stops, dwells and tick tags (not in the reference) ----
+ *      wa_traj_retime knows one motion, rest to rest.  A job that welds has to stop at a seam's start to strike the arc, wait, weld at
+ *      weld speed, stop for the crater fill and travel on; and a torch that must re-orient between a travel leg and a seam needs a
+ *      place to do it (rule 25's n_jump).  A STOP is a segment without length (L_i = 0) that has a duration.  The three calls below take
+ *      stops into the timing, turn the torch in place while one lasts, tag every tick with what the caller put on its segment, and size
+ *      a dwell from a turn rate.  The rules continue the retime section (its rules 1 - 7 are meant by "retime rule k") and rules
+ *      24 - 26; Q, ds_i, L_i, q, U, D_i and psi_i are theirs.  Integers and individually rounded doubles only.
+ * 40. wa_traj_retime_stops.  dwell: n - 1 doubles on the host, or NULL.  dwell[i] < 0: segment i is an ordinary segment.  dwell[i] >= 0:
+ *     segment i is a stop of that many seconds (0 is legal: come to rest, then go); dq_i = (int64)rint(dwell[i] * Q).  WA_ERR_ARG before
+ *     anything is written: an entry that is not finite, dq_i >= 2^61, a stop on a segment with L_i > 0, a NULL stops.  Retime rule 2
+ *     gains one line: both samples of a stop get a kind-0 cap of 0 (kind 0 is the lowest number, so it is the kind reported, and
+ *     n_bound[0] counts these samples).  Retime rules 3 and 4 apply as they stand: a cap of 0 resets the prefix and the suffix minimum, so
+ *     the profile on either side of a stop is the rest-to-rest profile of that piece alone.  Retime rule 5 (a) becomes: L_i = 0:
+ *     T_i = dq_i on a stop, else 0; the sum of T stays below 2^61.  Retime rule 6 is unchanged, word for word: i is the LARGEST index
+ *     with time_q[i] <= tau, so a tick inside a dwell finds the stop and is p_i by the L_i = 0 clause.  Errors as retime rule 7.
+ *     wa_stops_summary: n_stops = entries >= 0, n_stop_samples = samples at either end of a stop (one between two stops counts once),
+ *     dwell_q = the sum of dq.  With dwell == NULL every output is the bytes of wa_traj_retime and *stops is all zero.
+ * 41. wa_traj_tick_axes_stops.  Rule 26 with two additions.  (a) Dwell: a located segment i with L_i = 0, time_q[i+1] > time_q[i] and
+ *     tau < time_q[i+1] -- this is how the call recognises a dwell; it takes no dwell array.  The position is p_i (retime rule 6); the
+ *     axis is rule 26's formula, all-zero case included, with lambda = (double)(tau - time_q[i]) / (double)(time_q[i+1] - time_q[i]) (each
+ *     conversion rounded to nearest even, one division) clamped into [0, 1]: the torch turns in place, linear in time; the bead check
+ *     runs at the voxel of p_i with that axis.  (b) Tags: seg_tag (n - 1 bytes, host, may be NULL) carries whatever the caller put on
+ *     a segment, arc on or off and a seam number for instance; tag_out[k] = seg_tag[i] for the segment i that retime rule 6 located for
+ *     tick k, the final tick that is p_(i+1) exactly included.  tag_out (n_ticks bytes, host) may be NULL and must be with seg_tag NULL.
+ *     wa_tick_stops_summary: n_dwell_ticks = ticks located in a dwell; n_tagged = ticks whose tag is not 0 (0 without seg_tag);
+ *     max_dwell_turn = the largest U between the axes of tick k - 1 and tick k over the ticks k > 0 located in a dwell.  Without a
+ *     segment of no length and positive duration *axes_out, blocked_out and *sum are the bytes of wa_traj_tick_axes.  Errors as rule
+ *     26, and WA_ERR_ARG for a NULL stops.
+ * 42. wa_traj_axes_dwells gives the dwell a turn needs.  Per segment i, with D_i, psi_i and L_i exactly as in rule 25 and
+ *     given = dwell_in ? dwell_in[i] : -1:  L_i > 0: given must be < 0 (WA_ERR_ARG otherwise), dwell_out[i] = -1.  L_i = 0 and D_i = 0:
+ *     dwell_out[i] = given if given >= 0, else -1.  L_i = 0 and D_i > 0 (rule 25's jump): need = psi_i / omega (one division);
+ *     dwell_out[i] = need if given < need, else given.  WA_ERR_ARG as rule 25 for omega, the axes and the coordinates, and for a
+ *     dwell_in entry that is not finite.  Summary: n, n_jump, n_stops (dwell_out[i] >= 0), n_raised (jumps with given < need), max_need
+ *     (the largest need, 0 without a jump).  dwell_out (n - 1 doubles, host) is ready to be passed to wa_traj_retime_stops as dwell.
+ *     Property: there every jump segment takes T_i >= floor(psi_i / omega * Q) quanta.  As in rule 25 omega bounds the CHORD of the two
+ *     axes: in a wide turn the interpolated axis of rule 41 moves faster in the middle of the dwell than at its ends; max_dwell_turn
+ *     shows by how much, and a caller who minds inserts intermediate samples (more, smaller turns).  n is 1 .. 2^31.
+ * Every WA_ERR_ARG is answered before anything is written.  Same bytes on every call; everything runs on the context's stream; g and
+ * t are not modified.  Not covered: stops on segments that have a length, a jerk limit, angular acceleration, slerp. */
+typedef struct {
+    int64_t n_stops, n_stop_samples, dwell_q;
+} wa_stops_summary;
+typedef struct {
+    int64_t n_dwell_ticks, n_tagged, max_dwell_turn;
+} wa_tick_stops_summary;
+typedef struct {
+    int64_t n, n_jump, n_stops, n_raised;
+    double max_need;
+} wa_axes_dwells_summary;
+int wa_traj_retime_stops(const wa_grid *g, const wa_traj *t, const wa_retime_limits *lim, const float *v_limit,
+                         const double *dwell /* n-1, host, may be NULL */, double tick,
+                         int64_t *time_q_out, int64_t *w_q_out, uint8_t *bound_out, wa_traj **ticks_out,
+                         wa_retime_summary *sum, wa_stops_summary *stops);
+int wa_traj_tick_axes_stops(const wa_grid *g, const wa_traj *t, const int32_t *q, const wa_tool_beads *tool, int32_t near_add,
+                            double acc, double dec, double tick, const int64_t *time_q, const int64_t *w_q,
+                            const uint8_t *seg_tag /* n-1, host, may be NULL */,
+                            wa_traj **axes_out, uint8_t *blocked_out, uint8_t *tag_out /* n_ticks, host, may be NULL */,
+                            wa_tick_axes_summary *sum, wa_tick_stops_summary *stops);
+int wa_traj_axes_dwells(const wa_traj *t, const int32_t *q, double omega, const double *dwell_in /* n-1 or NULL */,
+                        double *dwell_out /* n-1, host */, wa_axes_dwells_summary *sum);
 
 #ifdef __cplusplus
 }

@@ -119,6 +119,18 @@ class TickAxesSummary(C.Structure):
                 ("n_near", C.c_int64), ("max_tick_turn", C.c_int64)]
 
 
+class StopsSummary(C.Structure):
+    _fields_ = [("n_stops", C.c_int64), ("n_stop_samples", C.c_int64), ("dwell_q", C.c_int64)]
+
+
+class TickStopsSummary(C.Structure):
+    _fields_ = [("n_dwell_ticks", C.c_int64), ("n_tagged", C.c_int64), ("max_dwell_turn", C.c_int64)]
+
+
+class AxesDwellsSummary(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_jump", C.c_int64), ("n_stops", C.c_int64), ("n_raised", C.c_int64), ("max_need", C.c_double)]
+
+
 WA_PEN_MAX = 31
 
 # every symbol include/weldacs.h declares: name -> (restype, argtypes)
@@ -257,6 +269,11 @@ SYMBOLS = {
     "wa_traj_axes_limits": (C.c_int, [_V, _P, C.c_double, C.c_double, C.c_double, _P, _P, C.POINTER(AxesLimitsSummary)]),
     "wa_traj_tick_axes": (C.c_int, [_V, _V, _P, C.POINTER(ToolBeads), _I, C.c_double, C.c_double, C.c_double, _P, _P, C.POINTER(_V), _P,
                                     C.POINTER(TickAxesSummary)]),
+    "wa_traj_retime_stops": (C.c_int, [_V, _V, C.POINTER(RetimeLimits), _P, _P, C.c_double, _P, _P, _P, C.POINTER(_V), C.POINTER(RetimeSummary),
+                                       C.POINTER(StopsSummary)]),
+    "wa_traj_tick_axes_stops": (C.c_int, [_V, _V, _P, C.POINTER(ToolBeads), _I, C.c_double, C.c_double, C.c_double, _P, _P, _P, C.POINTER(_V), _P,
+                                          _P, C.POINTER(TickAxesSummary), C.POINTER(TickStopsSummary)]),
+    "wa_traj_axes_dwells": (C.c_int, [_V, _P, C.c_double, _P, _P, C.POINTER(AxesDwellsSummary)]),
 }
 
 _libs = {}

@@ -1089,6 +1089,79 @@ class Trajectory:
         summary = {k: int(getattr(s, k)) for k, _ in L.TickAxesSummary._fields_}
         return Trajectory(self.ctx, th) if th.value else None, out, summary
 
+    def _dwells(self, dwell, what):
+        if dwell is None:
+            return None
+        dwell = np.ascontiguousarray(dwell, np.float64).reshape(-1)
+        if len(dwell) != len(self) - 1:
+            raise ValueError("%s needs one entry per segment" % what)
+        return dwell
+
+    def retime_stops(self, v_max, acc, dec, tick, dwell=None, a_lat=float("inf"), grid=None, v_near=0.0, near_d2=-1, v_limit=None, ticks=True):
+        """wa_traj_retime_stops: retime() with stops inside the motion.  dwell: one entry per segment, < 0 for an ordinary segment, >= 0
+        for a stop of that many seconds on a segment without length (a doubled sample): the torch comes to rest there, waits and goes on.
+        Returns retime()'s tuple and the stops summary: (time_q, w_q, bound, ticks Trajectory or None, summary, stops dict)."""
+        n = len(self)
+        lim = L.RetimeLimits(v_max, acc, dec, a_lat, v_near, near_d2)
+        if v_limit is not None:
+            v_limit = np.ascontiguousarray(v_limit, np.float32).reshape(-1)
+            if len(v_limit) != n:
+                raise ValueError("v_limit needs one entry per sample")
+        dwell = self._dwells(dwell, "dwell")
+        time_q, w_q, bound = np.empty(n, np.int64), np.empty(n, np.int64), np.empty(n, np.uint8)
+        th, s, s2 = C.c_void_p(), L.RetimeSummary(), L.StopsSummary()
+        rc = self.ctx.lib.wa_traj_retime_stops(grid.h if grid is not None else None, self.h, C.byref(lim), _ptr(v_limit), _ptr(dwell),
+                                               C.c_double(tick), _ptr(time_q), _ptr(w_q), _ptr(bound), C.byref(th) if ticks else None,
+                                               C.byref(s), C.byref(s2))
+        if rc != 7:   # WA_ERR_CAPACITY: everything but the ticks is there
+            self.ctx.check(rc)
+        summary = {k: (list(getattr(s, k)) if k == "n_bound" else int(getattr(s, k))) for k, _ in L.RetimeSummary._fields_}
+        return time_q, w_q, bound, Trajectory(self.ctx, th) if th.value else None, summary, {k: int(getattr(s2, k)) for k, _ in L.StopsSummary._fields_}
+
+    def axis_dwells(self, q, omega, dwell=None):
+        """wa_traj_axes_dwells: the dwell every change of direction on a segment without length needs at the turn rate `omega` (chord of
+        the unit axes per second), never below the caller's own `dwell` there.  Returns (float64[n-1] for retime_stops(dwell=...),
+        summary)."""
+        q = self._axes(q)
+        dwell = self._dwells(dwell, "dwell")
+        out = np.empty(max(len(self) - 1, 0), np.float64)
+        s = L.AxesDwellsSummary()
+        self.ctx.check(self.ctx.lib.wa_traj_axes_dwells(self.h, _ptr(q), C.c_double(omega), _ptr(dwell), _ptr(out), C.byref(s)))
+        return out, {k: (float(s.max_need) if k == "max_need" else int(getattr(s, k))) for k, _ in L.AxesDwellsSummary._fields_}
+
+    def tick_axes_stops(self, q, time_q, w_q, acc, dec, tick, seg_tag=None, grid=None, tool=None, near_add=-1, axes=True, blocked=True):
+        """wa_traj_tick_axes_stops: tick_axes() on retime_stops(...)'s result.  During a dwell the torch stays where it is and turns from
+        the stop's first axis to its second, linear in time.  seg_tag: one byte per segment (arc on / off, a seam number, whatever the
+        caller puts there); every tick gets the tag of its segment.  Returns tick_axes()'s tuple, the tags and the stops summary:
+        (Trajectory of n_ticks unit axes or None, blocked uint8[n_ticks] or None, summary, tags uint8[n_ticks] or None, stops dict)."""
+        n = len(self)
+        q = self._axes(q)
+        time_q = np.ascontiguousarray(time_q, np.int64).reshape(-1)
+        w_q = np.ascontiguousarray(w_q, np.int64).reshape(-1)
+        if len(time_q) != n or len(w_q) != n:
+            raise ValueError("time_q and w_q need one entry per sample")
+        if seg_tag is not None:
+            seg_tag = np.ascontiguousarray(seg_tag, np.uint8).reshape(-1)
+            if len(seg_tag) != n - 1:
+                raise ValueError("seg_tag needs one entry per segment")
+        if tool is not None:
+            tool = tool if isinstance(tool, L.ToolBeads) else torch_tool(*tool)
+        n_ticks = 0
+        if n >= 2:
+            tq = int(np.rint(np.float64(tick) * RETIME_Q)) if np.isfinite(tick) else 0
+            n_ticks = int(time_q[-1]) // tq + 1 + (1 if int(time_q[-1]) % tq else 0) if tq >= 1 and time_q[-1] >= 0 else 0
+            n_ticks = n_ticks if n_ticks <= 1 << 31 else 0
+        out = np.empty(n_ticks, np.uint8) if blocked and n >= 2 else None
+        tags = np.empty(n_ticks, np.uint8) if seg_tag is not None else None
+        th, s, s2 = C.c_void_p(), L.TickAxesSummary(), L.TickStopsSummary()
+        self.ctx.check(self.ctx.lib.wa_traj_tick_axes_stops(grid.h if grid is not None else None, self.h, _ptr(q),
+                                                            C.byref(tool) if tool is not None else None, near_add, C.c_double(acc), C.c_double(dec),
+                                                            C.c_double(tick), _ptr(time_q), _ptr(w_q), _ptr(seg_tag), C.byref(th) if axes else None,
+                                                            _ptr(out), _ptr(tags), C.byref(s), C.byref(s2)))
+        summary = {k: int(getattr(s, k)) for k, _ in L.TickAxesSummary._fields_}
+        return (Trajectory(self.ctx, th) if th.value else None, out, summary, tags,
+                {k: int(getattr(s2, k)) for k, _ in L.TickStopsSummary._fields_})
+
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.wa_traj_destroy(self.h)

@@ -1,8 +1,9 @@
-// host_retime.inc -- C ABI: wa_traj_retime, speed caps, ramps and controller ticks along a sampled trajectory (included by weldacs.hip
-// inside extern "C").  Everything between the arguments and the results stays on the device, on the context's stream; the host reads
+// host_retime.inc -- C ABI: wa_traj_retime and wa_traj_retime_stops, speed caps, ramps, stops and controller ticks along a sampled
+// trajectory (included by weldacs.hip inside extern "C").  One driver serves both calls: with dwell == nullptr it launches what
+// wa_traj_retime always launched, with a dwell array the two kernels that know a stop (stops_kernels.hpp) in their place.  Everything between the arguments and the results stays on the device, on the context's stream; the host reads
 // ONE WaRtRec (sums, counters, what was refused), sizes the tick buffer from it and launches the ticks.
 struct RetimeBuffers {
-    DevBuf<long long> A, D, C, F, B, T, time_q;
+    DevBuf<long long> A, D, C, F, B, T, time_q, dq;
     DevBuf<uint8_t> kind, bound;
     DevBuf<float> v_limit;
     DevBuf<RtPair> scratch;
@@ -27,25 +28,42 @@ static bool rt_sum_fits(const unsigned long long w[2], int64_t *out)
 
 static bool rt_pos_finite(double x) { return x > 0.0 && std::isfinite(x); }
 
-int wa_traj_retime(const wa_grid *g, const wa_traj *t, const wa_retime_limits *lim, const float *v_limit, double tick,
-                   int64_t *time_q_out, int64_t *w_q_out, uint8_t *bound_out, wa_traj **ticks_out, wa_retime_summary *sum)
+static int retime_run(const char *who, const wa_grid *g, const wa_traj *t, const wa_retime_limits *lim, const float *v_limit,
+                      const double *dwell, double tick, int64_t *time_q_out, int64_t *w_q_out, uint8_t *bound_out, wa_traj **ticks_out,
+                      wa_retime_summary *sum, wa_stops_summary *stops)
 {
     WaDevGuard dev_guard_(t ? t->ctx : nullptr);
     if (!dev_guard_.ok) return WA_ERR_DEVICE;   // the context's device could not be made current
     if (!t) return WA_ERR_ARG;
     wa_ctx *ctx = t->ctx;
-    if (!lim || !sum) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: NULL limits or summary");
-    if (g && g->ctx != ctx) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: trajectory and grid belong to different contexts");
+    if (!lim || !sum) return fail(ctx, WA_ERR_ARG, "%s: NULL limits or summary", who);
+    if (g && g->ctx != ctx) return fail(ctx, WA_ERR_ARG, "%s: trajectory and grid belong to different contexts", who);
     const int64_t n = t->n;
-    if (n < 2 || n > WA_RT_MAX_N) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: a trajectory needs 2 .. 2^31 samples");
+    if (n < 2 || n > WA_RT_MAX_N) return fail(ctx, WA_ERR_ARG, "%s: a trajectory needs 2 .. 2^31 samples", who);
     if (!rt_pos_finite(lim->v_max) || !rt_pos_finite(lim->acc) || !rt_pos_finite(lim->dec))
-        return fail(ctx, WA_ERR_ARG, "wa_traj_retime: v_max, acc and dec must be finite and > 0");
-    if (!(lim->a_lat >= 0.0)) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: a_lat must be >= 0 (0 or +inf: no curvature cap)");
-    if (g && lim->near_d2 >= 0 && !rt_pos_finite(lim->v_near)) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: v_near must be finite and > 0");
-    if (!std::isfinite(tick)) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: tick must be finite");
+        return fail(ctx, WA_ERR_ARG, "%s: v_max, acc and dec must be finite and > 0", who);
+    if (!(lim->a_lat >= 0.0)) return fail(ctx, WA_ERR_ARG, "%s: a_lat must be >= 0 (0 or +inf: no curvature cap)", who);
+    if (g && lim->near_d2 >= 0 && !rt_pos_finite(lim->v_near)) return fail(ctx, WA_ERR_ARG, "%s: v_near must be finite and > 0", who);
+    if (!std::isfinite(tick)) return fail(ctx, WA_ERR_ARG, "%s: tick must be finite", who);
     const double tq = rint(tick * WA_RT_Q);
-    if (!(tq >= 1.0 && tq <= (double)WA_RT_CAP)) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: tick must be 2^-30 .. 2^31 seconds");
+    if (!(tq >= 1.0 && tq <= (double)WA_RT_CAP)) return fail(ctx, WA_ERR_ARG, "%s: tick must be 2^-30 .. 2^31 seconds", who);
     const long long tick_q = (long long)tq;
+    std::vector<long long> hdq;   // rule 40: the dwells in quanta, -1 where the segment is no stop
+    wa_stops_summary ss;
+    memset(&ss, 0, sizeof ss);
+    if (dwell) {
+        hdq.resize((size_t)n - 1);
+        for (int64_t i = 0; i < n - 1; i++) {
+            if (!std::isfinite(dwell[i])) return fail(ctx, WA_ERR_ARG, "%s: dwell entries must be finite", who);
+            const double dq = dwell[i] < 0.0 ? -1.0 : rint(dwell[i] * WA_RT_Q);
+            if (!(dq < (double)WA_RT_CAP)) return fail(ctx, WA_ERR_ARG, "%s: a dwell reaches 2^61 quanta", who);
+            hdq[(size_t)i] = (long long)dq;
+            if (dq < 0.0) continue;
+            ss.n_stops++;
+            ss.n_stop_samples += (i == 0 || hdq[(size_t)i - 1] < 0) ? 2 : 1;   // (a sample between two stops counts once)
+            ss.dwell_q = ss.dwell_q + (long long)dq < WA_RT_CAP ? ss.dwell_q + (long long)dq : WA_RT_CAP;   // (the device refuses such a sum)
+        }
+    }
     WaField field = {};   // (no grid: all zero)
     if (g) {
         int rc = grid_field(g, &field);
@@ -60,9 +78,11 @@ int wa_traj_retime(const wa_grid *g, const wa_traj *t, const wa_retime_limits *l
     e = e ? e : R.scratch.alloc((size_t)rt_scratch_pairs(n));
     e = e ? e : R.rec.alloc(1);
     if (v_limit) e = e ? e : R.v_limit.alloc((size_t)n);
-    if (e != hipSuccess) return fail(ctx, WA_ERR_ALLOC, "wa_traj_retime: device buffers");
+    if (dwell) e = e ? e : R.dq.alloc((size_t)n - 1);
+    if (e != hipSuccess) return fail(ctx, WA_ERR_ALLOC, "%s: device buffers", who);
     e = hipMemsetAsync(R.rec, 0, sizeof(WaRtRec), ctx->stream);
     if (v_limit) e = e ? e : hipMemcpyAsync(R.v_limit, v_limit, sizeof(float) * n, hipMemcpyHostToDevice, ctx->stream);
+    if (dwell) e = e ? e : hipMemcpyAsync(R.dq, hdq.data(), sizeof(long long) * ((size_t)n - 1), hipMemcpyHostToDevice, ctx->stream);
     const unsigned blocks = (unsigned)((n + 255) / 256);
     WaRtLimits dl;
     dl.v_max = lim->v_max; dl.acc = lim->acc; dl.dec = lim->dec; dl.a_lat = lim->a_lat; dl.v_near = lim->v_near;
@@ -70,29 +90,32 @@ int wa_traj_retime(const wa_grid *g, const wa_traj *t, const wa_retime_limits *l
     dl.curv = std::isfinite(lim->a_lat) && lim->a_lat != 0.0;
     if (e == hipSuccess) {
         k_rt_segments<<<blocks, 256, 0, ctx->stream>>>(t->xyz, n, dl.acc, dl.dec, R.A, R.D, R.rec);
-        k_rt_caps<<<blocks, 256, 0, ctx->stream>>>(t->xyz, n, dl, R.v_limit, field, R.C, R.kind, R.rec);
+        if (dwell) k_st_caps<<<blocks, 256, 0, ctx->stream>>>(t->xyz, n, dl, R.v_limit, field, R.dq, R.C, R.kind, R.rec);
+        else k_rt_caps<<<blocks, 256, 0, ctx->stream>>>(t->xyz, n, dl, R.v_limit, field, R.C, R.kind, R.rec);
         e = hipGetLastError();
     }
     const RtSamples fwd = {R.A, R.C, R.F, n, 0}, bwd = {R.D, R.F, R.B, n, 1}, tim = {R.T, nullptr, R.time_q, n, 0};
     e = e ? e : rt_scan(ctx->stream, fwd, R.scratch);
     e = e ? e : rt_scan(ctx->stream, bwd, R.scratch);
     if (e == hipSuccess) {
-        k_rt_times<<<blocks, 256, 0, ctx->stream>>>(t->xyz, n, dl.acc, dl.dec, R.A, R.D, R.C, R.B, R.kind, R.bound, R.T, R.rec);
+        if (dwell) k_st_times<<<blocks, 256, 0, ctx->stream>>>(t->xyz, n, dl.acc, dl.dec, R.A, R.D, R.C, R.B, R.kind, R.dq, R.bound, R.T, R.rec);
+        else k_rt_times<<<blocks, 256, 0, ctx->stream>>>(t->xyz, n, dl.acc, dl.dec, R.A, R.D, R.C, R.B, R.kind, R.bound, R.T, R.rec);
         e = hipGetLastError();
     }
     e = e ? e : rt_scan(ctx->stream, tim, R.scratch);
     WaRtRec rec;
     e = e ? e : hipMemcpyAsync(&rec, R.rec, sizeof rec, hipMemcpyDeviceToHost, ctx->stream);
     e = e ? e : hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_traj_retime: %s", hipGetErrorString(e));
-    if (rec.bad & 1) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: a coordinate of the trajectory is not finite");
-    if (rec.bad & 4) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: v_limit entries must be finite and > 0");   // (k_rt_caps looked at every entry)
+    if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
+    if (rec.bad & 1) return fail(ctx, WA_ERR_ARG, "%s: a coordinate of the trajectory is not finite", who);
+    if (rec.bad & 4) return fail(ctx, WA_ERR_ARG, "%s: v_limit entries must be finite and > 0", who);   // (k_rt_caps looked at every entry)
+    if (rec.bad & 8) return fail(ctx, WA_ERR_ARG, "%s: a stop sits on a segment that has a length", who);
     wa_retime_summary s;
     memset(&s, 0, sizeof s);
     int64_t sum_a = 0, sum_d = 0;
     if (!rt_sum_fits(rec.sumL, &s.length_q) || !rt_sum_fits(rec.sumA, &sum_a) || !rt_sum_fits(rec.sumD, &sum_d))
-        return fail(ctx, WA_ERR_ARG, "wa_traj_retime: the sum of L, A or D reaches 2^61 quanta");
-    if ((rec.bad & 2) || !rt_sum_fits(rec.sumT, &s.time_q)) return fail(ctx, WA_ERR_ARG, "wa_traj_retime: the duration reaches 2^61 quanta");
+        return fail(ctx, WA_ERR_ARG, "%s: the sum of L, A or D reaches 2^61 quanta", who);
+    if ((rec.bad & 2) || !rt_sum_fits(rec.sumT, &s.time_q)) return fail(ctx, WA_ERR_ARG, "%s: the duration reaches 2^61 quanta", who);
     s.n = n;
     const long long n_full = s.time_q / tick_q + 1;
     s.n_ticks = n_full + (s.time_q % tick_q ? 1 : 0);
@@ -117,9 +140,24 @@ int wa_traj_retime(const wa_grid *g, const wa_traj *t, const wa_retime_limits *l
     if (w_q_out) e = e ? e : hipMemcpyAsync(w_q_out, R.B, sizeof(int64_t) * n, hipMemcpyDeviceToHost, ctx->stream);
     if (bound_out) e = e ? e : hipMemcpyAsync(bound_out, R.bound, (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
     e = e ? e : hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_traj_retime: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
     if (ticks_out) *ticks_out = R.ticks.release();
     *sum = s;
-    if (too_many) return fail(ctx, WA_ERR_CAPACITY, "wa_traj_retime: more than 2^31 ticks");
+    if (stops) *stops = ss;
+    if (too_many) return fail(ctx, WA_ERR_CAPACITY, "%s: more than 2^31 ticks", who);
     return WA_OK;
+}
+
+int wa_traj_retime(const wa_grid *g, const wa_traj *t, const wa_retime_limits *lim, const float *v_limit, double tick,
+                   int64_t *time_q_out, int64_t *w_q_out, uint8_t *bound_out, wa_traj **ticks_out, wa_retime_summary *sum)
+{
+    return retime_run("wa_traj_retime", g, t, lim, v_limit, nullptr, tick, time_q_out, w_q_out, bound_out, ticks_out, sum, nullptr);
+}
+
+int wa_traj_retime_stops(const wa_grid *g, const wa_traj *t, const wa_retime_limits *lim, const float *v_limit, const double *dwell,
+                         double tick, int64_t *time_q_out, int64_t *w_q_out, uint8_t *bound_out, wa_traj **ticks_out,
+                         wa_retime_summary *sum, wa_stops_summary *stops)
+{
+    if (t && !stops) return fail(t->ctx, WA_ERR_ARG, "wa_traj_retime_stops: NULL stops summary");
+    return retime_run("wa_traj_retime_stops", g, t, lim, v_limit, dwell, tick, time_q_out, w_q_out, bound_out, ticks_out, sum, stops);
 }

@@ -201,34 +201,36 @@ int wa_traj_axes_limits(const wa_traj *t, const int32_t *q, double omega, double
     return WA_OK;
 }
 
-int wa_traj_tick_axes(const wa_grid *g, const wa_traj *t, const int32_t *q, const wa_tool_beads *tool, int32_t near_add, double acc, double dec,
-                      double tick, const int64_t *time_q, const int64_t *w_q, wa_traj **axes_out, uint8_t *blocked_out,
-                      wa_tick_axes_summary *sum)
+// One driver for wa_traj_tick_axes and wa_traj_tick_axes_stops (host_stops.inc): stops == nullptr launches k_tk_axes as ever, otherwise
+// k_tk_axes_stops with the segment tags and the second record.
+static int tick_axes_run(const char *who, const wa_grid *g, const wa_traj *t, const int32_t *q, const wa_tool_beads *tool, int32_t near_add,
+                         double acc, double dec, double tick, const int64_t *time_q, const int64_t *w_q, const uint8_t *seg_tag,
+                         wa_traj **axes_out, uint8_t *blocked_out, uint8_t *tag_out, wa_tick_axes_summary *sum, wa_tick_stops_summary *stops)
 {
     WaDevGuard dev_guard_(t ? t->ctx : nullptr);
     if (!dev_guard_.ok) return WA_ERR_DEVICE;   // the context's device could not be made current
     if (!t) return WA_ERR_ARG;
     wa_ctx *ctx = t->ctx;
-    if (!q || !time_q || !w_q || !sum) return fail(ctx, WA_ERR_ARG, "wa_traj_tick_axes: NULL argument");
-    if ((g == nullptr) != (tool == nullptr)) return fail(ctx, WA_ERR_ARG, "wa_traj_tick_axes: a grid and a tool come together or not at all");
-    if (g && g->ctx != ctx) return fail(ctx, WA_ERR_ARG, "wa_traj_tick_axes: trajectory and grid belong to different contexts");
+    if (!q || !time_q || !w_q || !sum) return fail(ctx, WA_ERR_ARG, "%s: NULL argument", who);
+    if ((g == nullptr) != (tool == nullptr)) return fail(ctx, WA_ERR_ARG, "%s: a grid and a tool come together or not at all", who);
+    if (g && g->ctx != ctx) return fail(ctx, WA_ERR_ARG, "%s: trajectory and grid belong to different contexts", who);
     const int64_t n = t->n;
-    if (n < 2 || n > WA_RT_MAX_N) return fail(ctx, WA_ERR_ARG, "wa_traj_tick_axes: a trajectory needs 2 .. 2^31 samples");
-    if (!rt_pos_finite(acc) || !rt_pos_finite(dec)) return fail(ctx, WA_ERR_ARG, "wa_traj_tick_axes: acc and dec must be finite and > 0");
-    if (!std::isfinite(tick)) return fail(ctx, WA_ERR_ARG, "wa_traj_tick_axes: tick must be finite");
+    if (n < 2 || n > WA_RT_MAX_N) return fail(ctx, WA_ERR_ARG, "%s: a trajectory needs 2 .. 2^31 samples", who);
+    if (!rt_pos_finite(acc) || !rt_pos_finite(dec)) return fail(ctx, WA_ERR_ARG, "%s: acc and dec must be finite and > 0", who);
+    if (!std::isfinite(tick)) return fail(ctx, WA_ERR_ARG, "%s: tick must be finite", who);
     const double tq = rint(tick * WA_RT_Q);
-    if (!(tq >= 1.0 && tq <= (double)WA_RT_CAP)) return fail(ctx, WA_ERR_ARG, "wa_traj_tick_axes: tick must be 2^-30 .. 2^31 seconds");
+    if (!(tq >= 1.0 && tq <= (double)WA_RT_CAP)) return fail(ctx, WA_ERR_ARG, "%s: tick must be 2^-30 .. 2^31 seconds", who);
     const long long tick_q = (long long)tq;
-    if (time_q[0] != 0) return fail(ctx, WA_ERR_ARG, "wa_traj_tick_axes: time_q must begin at 0");
+    if (time_q[0] != 0) return fail(ctx, WA_ERR_ARG, "%s: time_q must begin at 0", who);
     for (int64_t i = 0; i < n; i++) {
         if (time_q[i] >= WA_RT_CAP || (i > 0 && time_q[i] < time_q[i - 1]))
-            return fail(ctx, WA_ERR_ARG, "wa_traj_tick_axes: time_q must not decrease and stay below 2^61");
-        if (w_q[i] < 0 || w_q[i] > WA_RT_CAP) return fail(ctx, WA_ERR_ARG, "wa_traj_tick_axes: w_q must be 0 .. 2^61");
+            return fail(ctx, WA_ERR_ARG, "%s: time_q must not decrease and stay below 2^61", who);
+        if (w_q[i] < 0 || w_q[i] > WA_RT_CAP) return fail(ctx, WA_ERR_ARG, "%s: w_q must be 0 .. 2^61", who);
     }
     WaTorchTool dt;
-    if (tool && !torch_tool_dev(tool, near_add, &dt)) return fail(ctx, WA_ERR_ARG, "wa_traj_tick_axes: n_beads, dist16, r2 or near_add out of range");
+    if (tool && !torch_tool_dev(tool, near_add, &dt)) return fail(ctx, WA_ERR_ARG, "%s: n_beads, dist16, r2 or near_add out of range", who);
     std::vector<short4> hq;
-    if (!ax_pack(q, n, &hq)) return fail(ctx, WA_ERR_ARG, "wa_traj_tick_axes: an axis component outside -16384 .. 16384 or an all-zero axis");
+    if (!ax_pack(q, n, &hq)) return fail(ctx, WA_ERR_ARG, "%s: an axis component outside -16384 .. 16384 or an all-zero axis", who);
     WaField F = {};
     if (g) {
         int rc = grid_field(g, &F);
@@ -238,9 +240,10 @@ int wa_traj_tick_axes(const wa_grid *g, const wa_traj *t, const int32_t *q, cons
     const bool too_many = n_ticks > ((int64_t)1 << 31);
     DevBuf<short4> dq;
     DevBuf<long long> dB, dtime, dL;
-    DevBuf<uint8_t> dblocked;
+    DevBuf<uint8_t> dblocked, dseg_tag, dtag;
     DevBuf<WaTorchTool> dtool;
     DevBuf<WaAxRec> drec;
+    DevBuf<WaTkStopsRec> dsrec;
     OwnedHandle<wa_traj> axes;
     hipError_t e = dq.alloc((size_t)n);
     e = e ? e : dB.alloc((size_t)n);
@@ -249,7 +252,10 @@ int wa_traj_tick_axes(const wa_grid *g, const wa_traj *t, const int32_t *q, cons
     e = e ? e : drec.alloc(1);
     if (tool) e = e ? e : dtool.alloc(1);
     if (blocked_out && !too_many) e = e ? e : dblocked.alloc((size_t)n_ticks);
-    if (e != hipSuccess) return fail(ctx, WA_ERR_ALLOC, "wa_traj_tick_axes: device buffers");
+    if (stops) e = e ? e : dsrec.alloc(1);
+    if (seg_tag) e = e ? e : dseg_tag.alloc((size_t)n - 1);
+    if (tag_out && !too_many) e = e ? e : dtag.alloc((size_t)n_ticks);
+    if (e != hipSuccess) return fail(ctx, WA_ERR_ALLOC, "%s: device buffers", who);
     if (axes_out && !too_many) {
         wa_traj *a = nullptr;
         int rc = traj_alloc(ctx, n_ticks, &a);
@@ -263,6 +269,8 @@ int wa_traj_tick_axes(const wa_grid *g, const wa_traj *t, const int32_t *q, cons
     e = e ? e : hipMemcpyAsync(dtime, time_q, sizeof(long long) * (size_t)n, hipMemcpyHostToDevice, st);
     e = e ? e : hipMemcpyAsync(drec, &rec, sizeof rec, hipMemcpyHostToDevice, st);
     if (tool) e = e ? e : hipMemcpyAsync(dtool, &dt, sizeof dt, hipMemcpyHostToDevice, st);
+    if (stops) e = e ? e : hipMemsetAsync(dsrec, 0, sizeof(WaTkStopsRec), st);
+    if (seg_tag) e = e ? e : hipMemcpyAsync(dseg_tag, seg_tag, (size_t)n - 1, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {
         k_ax_lengths<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(t->xyz, n, dL, drec);   // (here for the coordinates that are not finite)
         e = hipGetLastError();
@@ -271,22 +279,31 @@ int wa_traj_tick_axes(const wa_grid *g, const wa_traj *t, const int32_t *q, cons
         WaTkArgs T;
         T.xyz = t->xyz; T.q = dq; T.B = dB; T.time_q = dtime; T.n = n; T.tick_q = tick_q; T.n_full = n_full; T.n_ticks = n_ticks;
         T.acc = acc; T.dec = dec; T.check = g ? 1 : 0; T.axes = axes ? axes->xyz : nullptr; T.blocked = dblocked;
-        k_tk_axes<<<(unsigned)((n_ticks + 255) / 256), 256, 0, st>>>(T, F, dtool, drec);
+        if (stops) {
+            const WaTkStops S = {dseg_tag, dtag, dsrec};
+            k_tk_axes_stops<<<(unsigned)((n_ticks + 255) / 256), 256, 0, st>>>(T, F, dtool, drec, S);
+        } else {
+            k_tk_axes<<<(unsigned)((n_ticks + 255) / 256), 256, 0, st>>>(T, F, dtool, drec);
+        }
         e = hipGetLastError();
     }
+    WaTkStopsRec srec;
+    memset(&srec, 0, sizeof srec);
     e = e ? e : hipMemcpyAsync(&rec, drec, sizeof rec, hipMemcpyDeviceToHost, st);
+    if (stops) e = e ? e : hipMemcpyAsync(&srec, dsrec, sizeof srec, hipMemcpyDeviceToHost, st);
     e = e ? e : hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_traj_tick_axes: %s", hipGetErrorString(e));
-    if (rec.bad & 1) return fail(ctx, WA_ERR_ARG, "wa_traj_tick_axes: a coordinate of the trajectory is not finite");
+    if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
+    if (rec.bad & 1) return fail(ctx, WA_ERR_ARG, "%s: a coordinate of the trajectory is not finite", who);
     // (every WA_ERR_ARG has been answered by now: nothing was written before this line)
     if (too_many) {
         if (axes_out) *axes_out = nullptr;
-        return fail(ctx, WA_ERR_CAPACITY, "wa_traj_tick_axes: more than 2^31 ticks");
+        return fail(ctx, WA_ERR_CAPACITY, "%s: more than 2^31 ticks", who);
     }
-    if (blocked_out) {
-        e = hipMemcpyAsync(blocked_out, dblocked, (size_t)n_ticks, hipMemcpyDeviceToHost, st);
+    if (blocked_out || tag_out) {
+        if (blocked_out) e = hipMemcpyAsync(blocked_out, dblocked, (size_t)n_ticks, hipMemcpyDeviceToHost, st);
+        if (tag_out) e = e ? e : hipMemcpyAsync(tag_out, dtag, (size_t)n_ticks, hipMemcpyDeviceToHost, st);
         e = e ? e : hipStreamSynchronize(st);
-        if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_traj_tick_axes: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
     }
     wa_tick_axes_summary s;
     memset(&s, 0, sizeof s);
@@ -298,7 +315,25 @@ int wa_traj_tick_axes(const wa_grid *g, const wa_traj *t, const int32_t *q, cons
     }
     s.first_blocked = rec.first_blocked == ~0ull ? -1 : (int64_t)rec.first_blocked;
     s.max_tick_turn = (int64_t)rec.max_tick_turn;
+    if (stops) {
+        wa_tick_stops_summary s2;
+        memset(&s2, 0, sizeof s2);
+        for (int k = 0; k < WA_AX_SLOTS; k++) {
+            s2.n_dwell_ticks += (int64_t)srec.slot[k].n_dwell;
+            s2.n_tagged += (int64_t)srec.slot[k].n_tagged;
+        }
+        s2.max_dwell_turn = (int64_t)srec.max_dwell_turn;
+        *stops = s2;
+    }
     if (axes_out) *axes_out = axes.release();
     *sum = s;
     return WA_OK;
+}
+
+int wa_traj_tick_axes(const wa_grid *g, const wa_traj *t, const int32_t *q, const wa_tool_beads *tool, int32_t near_add, double acc, double dec,
+                      double tick, const int64_t *time_q, const int64_t *w_q, wa_traj **axes_out, uint8_t *blocked_out,
+                      wa_tick_axes_summary *sum)
+{
+    return tick_axes_run("wa_traj_tick_axes", g, t, q, tool, near_add, acc, dec, tick, time_q, w_q, nullptr, axes_out, blocked_out, nullptr, sum,
+                         nullptr);
 }

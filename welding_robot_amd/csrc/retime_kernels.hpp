@@ -9,6 +9,7 @@
 //                  aggregates, recursively) - add (block prefixes), with kernel boundaries in between: no workgroup waits for another.
 //   k_rt_times     one lane per sample: bound bits, the segment's time T, the summary's counters
 //   k_rt_ticks     one lane per tick: binary search in time_q, the position on its segment, stores staged through LDS
+// k_rt_caps and k_rt_times are the STOPS == false instantiations of rt_caps / rt_times; stops_kernels.hpp holds the others.
 // Integers and single correctly rounded fp64 operations throughout (the translation unit is built without contraction): every output
 // is bit-exact and independent of scheduling; what is accumulated across lanes is an integer.
 #pragma once
@@ -27,7 +28,8 @@ struct WaRtRec {
     unsigned long long sumL[2], sumA[2], sumD[2], sumT[2];
     unsigned long long n_bound[4], n_on_cap, n_on_ramp, n_triangle, n_outside;
     long long peak;
-    int32_t bad;     // bit 0: a coordinate is not finite; bit 1: a segment time does not fit; bit 2: a v_limit entry is not finite or <= 0
+    int32_t bad;     // bit 0: a coordinate is not finite; bit 1: a segment time does not fit; bit 2: a v_limit entry is not finite or <= 0;
+                     // bit 3: a stop on a segment that has a length
     int32_t pad;
 };
 
@@ -121,9 +123,12 @@ struct WaRtLimits {
 };
 
 // Rule 2.  The voxel of a sample is found by field_voxel, the lookup k_clr_samples runs; a call without a grid passes a zeroed view.
-__global__ __launch_bounds__(256) void k_rt_caps(const float *__restrict__ xyz, long long n, WaRtLimits lim, const float *__restrict__ v_limit,
-                                                 WaField F, long long *__restrict__ C, uint8_t *__restrict__ kind,
-                                                 WaRtRec *__restrict__ rec)
+// STOPS (wa_traj_retime_stops, stops_kernels.hpp): dq holds the dwell of every segment in quanta, -1 where the segment is no stop; both
+// samples of a stop get the kind-0 cap of the end points.
+template <bool STOPS>
+__device__ __forceinline__ void rt_caps(const float *__restrict__ xyz, long long n, const WaRtLimits &lim, const float *__restrict__ v_limit,
+                                        const WaField &F, long long *__restrict__ C, uint8_t *__restrict__ kind, WaRtRec *__restrict__ rec,
+                                        const long long *__restrict__ dq)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long outs = 0;
@@ -159,12 +164,19 @@ __global__ __launch_bounds__(256) void k_rt_caps(const float *__restrict__ xyz, 
             }
         }
         if (i == 0 || i == n - 1) { cap = 0.0; k = 0; }
+        if (STOPS && ((i > 0 && dq[i - 1] >= 0) || (i < n - 1 && dq[i] >= 0))) { cap = 0.0; k = 0; }
         const double q = cap * WA_RT_Q;
         C[i] = !(q < (double)WA_RT_CAP) ? WA_RT_CAP : (long long)floor(q);
         kind[i] = (uint8_t)k;
     }
     outs = rt_wave_sum(outs);
     if ((threadIdx.x & 63) == 0 && outs) atomicAdd(&rec->n_outside, outs);
+}
+__global__ __launch_bounds__(256) void k_rt_caps(const float *__restrict__ xyz, long long n, WaRtLimits lim, const float *__restrict__ v_limit,
+                                                 WaField F, long long *__restrict__ C, uint8_t *__restrict__ kind,
+                                                 WaRtRec *__restrict__ rec)
+{
+    rt_caps<false>(xyz, n, lim, v_limit, F, C, kind, rec, nullptr);
 }
 
 // ---- the scan.  A source hands out element e = 0 .. n - 1 and takes its result: the exclusive prefix and the element itself.
@@ -261,12 +273,14 @@ static hipError_t rt_scan(hipStream_t st, SRC src, RtPair *scratch)
 
 __device__ __forceinline__ double rt_speed(long long b) { return __dsqrt_rn((double)b / WA_RT_Q); }
 
-// Rules 4 and 5 and the summary.  T gets n entries, entry n - 1 is 0.
-__global__ __launch_bounds__(256) void k_rt_times(const float *__restrict__ xyz, long long n, double acc, double dec,
-                                                  const long long *__restrict__ A, const long long *__restrict__ D,
-                                                  const long long *__restrict__ C, const long long *__restrict__ B,
-                                                  const uint8_t *__restrict__ kind, uint8_t *__restrict__ bound, long long *__restrict__ T,
-                                                  WaRtRec *__restrict__ rec)
+// Rules 4 and 5 and the summary.  T gets n entries, entry n - 1 is 0.  STOPS: a stop segment takes its dwell dq_i as T_i; one that has
+// a length is reported in rec->bad.
+template <bool STOPS>
+__device__ __forceinline__ void rt_times(const float *__restrict__ xyz, long long n, double acc, double dec,
+                                         const long long *__restrict__ A, const long long *__restrict__ D,
+                                         const long long *__restrict__ C, const long long *__restrict__ B,
+                                         const uint8_t *__restrict__ kind, uint8_t *__restrict__ bound, long long *__restrict__ T,
+                                         WaRtRec *__restrict__ rec, const long long *__restrict__ dq)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     long long t = 0, b = 0;
@@ -299,6 +313,9 @@ __global__ __launch_bounds__(256) void k_rt_times(const float *__restrict__ xyz,
                 }
                 t = rt_quanta(dt);
                 if (t >= WA_RT_CAP) atomicOr(&rec->bad, 2);
+                if (STOPS && dq[i] >= 0) atomicOr(&rec->bad, 8);
+            } else if (STOPS && dq[i] >= 0) {
+                t = dq[i];
             }
         }
         T[i] = t;
@@ -322,6 +339,14 @@ __global__ __launch_bounds__(256) void k_rt_times(const float *__restrict__ xyz,
         if (mt) atomicAdd(&rec->n_triangle, (unsigned long long)__popcll(mt));
         if (pk > 0) atomicMax(&rec->peak, pk);
     }
+}
+__global__ __launch_bounds__(256) void k_rt_times(const float *__restrict__ xyz, long long n, double acc, double dec,
+                                                  const long long *__restrict__ A, const long long *__restrict__ D,
+                                                  const long long *__restrict__ C, const long long *__restrict__ B,
+                                                  const uint8_t *__restrict__ kind, uint8_t *__restrict__ bound, long long *__restrict__ T,
+                                                  WaRtRec *__restrict__ rec)
+{
+    rt_times<false>(xyz, n, acc, dec, A, D, C, B, kind, bound, T, rec, nullptr);
 }
 
 // Rule 6 for one tau: the segment i (the largest index in [lo, hi] with time_q[i] <= tau; the caller brackets it, [0, n - 2] always

@@ -9,6 +9,7 @@
 //   k_ax_limits    rule 25, one lane per sample
 //   k_tk_axes      rule 26, one lane per tick: where the tick lies (rt_tick_locate, rule 6), the interpolated axis, rule 2 at the tick's
 //                  voxel, stores staged through LDS
+//                  (the STOPS == false instantiation of tk_axes; stops_kernels.hpp holds the other)
 // Integers and single correctly rounded fp64 operations throughout (the translation unit is built without contraction): every output
 // is bit-exact and independent of scheduling; what is accumulated across lanes is an integer.
 #pragma once
@@ -474,31 +475,70 @@ __device__ __forceinline__ short4 tk_axis(const short4 *__restrict__ q, const Rt
 // of it a second time for max_tick_turn (the other lanes get their neighbour's by a shuffle): nothing is read that another
 // workgroup writes.  The block's 256 axes go through LDS so that consecutive lanes store consecutive floats; its counters are added
 // up in LDS and leave as one atomic each (WaAxSlot).
-__global__ __launch_bounds__(256) void k_tk_axes(WaTkArgs T, WaField F, const WaTorchTool *__restrict__ tool, WaAxRec *__restrict__ rec)
+// STOPS (wa_traj_tick_axes_stops, rule 41): the same kernel with a dwell's turn in place, a tag per tick and three more counters; what it
+// adds is compiled in only there.
+struct WaTkStopsSlot {
+    unsigned long long n_dwell, n_tagged, pad[6];   // one 64-byte line, as WaAxSlot
+};
+struct WaTkStopsRec {
+    WaTkStopsSlot slot[WA_AX_SLOTS];
+    unsigned long long max_dwell_turn;
+};
+struct WaTkStops {
+    const uint8_t *seg_tag;   // n - 1 or nullptr
+    uint8_t *tag;             // n_ticks or nullptr
+    WaTkStopsRec *rec;
+};
+
+// Rule 6 for one tau, and in a dwell (a located segment without length whose time goes on, tau before its end) the lambda of rule 41 for
+// the AXIS: the position of such a tick stays p_i (exact == 2 keeps rt_tick_pos off lam).
+template <bool STOPS>
+__device__ __forceinline__ RtTick tk_locate(const WaTkArgs &T, long long tau, long long lo, long long hi, bool *dwell)
+{
+    RtTick r = rt_tick_locate(T.xyz, T.acc, T.dec, T.B, T.time_q, tau, lo, hi);
+    *dwell = false;
+    if (STOPS && r.exact == 2) {
+        const long long t0 = T.time_q[r.i], t1 = T.time_q[r.i + 1];
+        if (t1 > t0) {
+            *dwell = true;
+            const double lam = __ddiv_rn((double)(tau - t0), (double)(t1 - t0));
+            r.lam = lam < 0.0 ? 0.0 : (lam > 1.0 ? 1.0 : lam);
+        }
+    }
+    return r;
+}
+
+template <bool STOPS>
+__device__ __forceinline__ void tk_axes(const WaTkArgs &T, const WaField &F, const WaTorchTool *__restrict__ tool, WaAxRec *__restrict__ rec,
+                                        const WaTkStops &S)
 {
     __shared__ float stage[256 * 3];
     __shared__ int32_t tl[192];
     __shared__ unsigned int cnt[3], blk_turn;   // the workgroup's ticks outside / blocked / near, its largest turn
     __shared__ unsigned long long blk_first;    // its first blocked tick
+    __shared__ unsigned int st_cnt[2], st_turn; // STOPS: its ticks in a dwell / with a tag, its largest turn at a dwell tick
+    __shared__ uint32_t st_tag[64];             // STOPS: its 256 tags, so that a lane stores four of them as one word
     if (T.check) ax_stage_tool(tool, tl);
     if (threadIdx.x < 3) cnt[threadIdx.x] = 0;
     if (threadIdx.x == 0) {
         blk_turn = 0;
         blk_first = ~0ull;
+        if (STOPS) st_cnt[0] = st_cnt[1] = st_turn = 0;
     }
     __syncthreads();
     const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const long long k_first = k - lane;   // (wave-uniform)
-    bool outside = false, blocked = false, near = false;
+    bool outside = false, blocked = false, near = false, dwell = false, front_dwell;
     unsigned long long turn = 0;
     long long mine = 0;
+    uint8_t tag = 0;
     bool live = k < T.n_ticks;
     if (k_first < T.n_ticks) {
         const long long total = T.time_q[T.n - 1];
         // the segment of tick k_first - 1 (always a full tick), or of tick 0
         const long long tau_front = k_first > 0 ? (k_first - 1) * T.tick_q : 0;
-        const RtTick front = rt_tick_locate(T.xyz, T.acc, T.dec, T.B, T.time_q, tau_front, 0, T.n - 2);
+        const RtTick front = tk_locate<STOPS>(T, tau_front, 0, T.n - 2, &front_dwell);
         if (live) {
             const long long tau = k < T.n_full ? k * T.tick_q : total;
             long long lo = front.i, hi = T.n - 2, step = 1;
@@ -507,9 +547,10 @@ __global__ __launch_bounds__(256) void k_tk_axes(WaTkArgs T, WaField F, const Wa
                 step <<= 1;
             }
             hi = lo + step - 1 < hi ? lo + step - 1 : hi;
-            const RtTick r = rt_tick_locate(T.xyz, T.acc, T.dec, T.B, T.time_q, tau, lo, hi);
+            const RtTick r = tk_locate<STOPS>(T, tau, lo, hi, &dwell);
             const short4 qt = tk_axis(T.q, r);
             mine = tk_pack(qt);
+            if (STOPS && S.seg_tag) tag = S.seg_tag[r.i];
             for (int c = 0; c < 3; c++) stage[3 * threadIdx.x + c] = (float)((double)(c == 0 ? qt.x : (c == 1 ? qt.y : qt.z)) / 16384.0);
             if (T.check) {
                 int64_t id;
@@ -525,6 +566,20 @@ __global__ __launch_bounds__(256) void k_tk_axes(WaTkArgs T, WaField F, const Wa
         if (live && k > 0) turn = ax_chord2(tk_unpack(before), tk_unpack(mine)) >> 10;
     }
     const unsigned long long mo = __ballot(outside), mb = __ballot(blocked), mn = __ballot(near);
+    if (STOPS) {
+        ((uint8_t *)st_tag)[threadIdx.x] = tag;   // (0 past the last tick)
+        const unsigned long long md = __ballot(dwell), mg = __ballot(tag != 0);
+        unsigned long long dturn = dwell ? turn : 0;
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long t2 = __shfl_down(dturn, o, 64);
+            dturn = t2 > dturn ? t2 : dturn;
+        }
+        if (lane == 0) {   // (LDS atomics)
+            if (md) atomicAdd(&st_cnt[0], (unsigned int)__popcll(md));
+            if (mg) atomicAdd(&st_cnt[1], (unsigned int)__popcll(mg));
+            if (dturn) atomicMax(&st_turn, (unsigned int)dturn);
+        }
+    }
     for (int o = 32; o > 0; o >>= 1) {
         const unsigned long long t2 = __shfl_down(turn, o, 64);
         turn = t2 > turn ? t2 : turn;
@@ -548,10 +603,31 @@ __global__ __launch_bounds__(256) void k_tk_axes(WaTkArgs T, WaField F, const Wa
         if (blk_first < __hip_atomic_load(&rec->first_blocked, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&rec->first_blocked, blk_first);
         if (blk_turn > __hip_atomic_load(&rec->max_tick_turn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
             atomicMax(&rec->max_tick_turn, (unsigned long long)blk_turn);
+        if (STOPS) {
+            WaTkStopsSlot *s2 = &S.rec->slot[blockIdx.x & (WA_AX_SLOTS - 1)];
+            if (st_cnt[0]) atomicAdd(&s2->n_dwell, (unsigned long long)st_cnt[0]);
+            if (st_cnt[1]) atomicAdd(&s2->n_tagged, (unsigned long long)st_cnt[1]);
+            if (st_turn > __hip_atomic_load(&S.rec->max_dwell_turn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                atomicMax(&S.rec->max_dwell_turn, (unsigned long long)st_turn);
+        }
     }
     if (T.axes) {
         const long long first = (long long)blockIdx.x * blockDim.x * 3, end = T.n_ticks * 3;
         for (int e = threadIdx.x; e < 256 * 3; e += 256)
             if (first + e < end) T.axes[first + e] = stage[e];
     }
+    if (STOPS && S.tag && threadIdx.x < 64) {   // (the block's first tick is a multiple of 256: the words are aligned)
+        const long long first = (long long)blockIdx.x * blockDim.x + 4 * threadIdx.x;
+        if (first + 4 <= T.n_ticks) {
+            *(uint32_t *)(S.tag + first) = st_tag[threadIdx.x];
+        } else {
+            for (int b = 0; b < 4; b++)
+                if (first + b < T.n_ticks) S.tag[first + b] = ((const uint8_t *)st_tag)[4 * threadIdx.x + b];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_tk_axes(WaTkArgs T, WaField F, const WaTorchTool *__restrict__ tool, WaAxRec *__restrict__ rec)
+{
+    tk_axes<false>(T, F, tool, rec, WaTkStops{});
 }

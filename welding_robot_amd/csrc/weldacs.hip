@@ -44,6 +44,7 @@
 #include "pose_shortcut_kernels.hpp"
 #include "pose_fit_kernels.hpp"
 #include "ticks_kernels.hpp"
+#include "stops_kernels.hpp"
 #include "stl_text.hpp"
 #include "acs_plan.hpp"
 
@@ -859,5 +860,6 @@ void *wa_ctx_stream(wa_ctx *c) { return c ? (void *)c->stream : nullptr; }
 #include "host_pose_shortcut.inc"
 #include "host_pose_fit.inc"
 #include "host_ticks.inc"
+#include "host_stops.inc"
 
 }  // extern "C"
