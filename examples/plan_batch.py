@@ -124,7 +124,24 @@ def turn_totals(dirs, ids_all, ks_all):
     return dict(hops=hops, direction_changes=changes, turn_sum=turn)
 
 
-def plan_pose(grid, point_ids, dirs, tool, max_turn, rank=0, world=1, shortcut=0, pose_shortcut=False, costs=None):
+def pose_path_totals(grid, dirs, tool, max_turn, ids_all, ks_all, shortcut, pose_shortcut):
+    """of a batch of (voxel, direction) paths (empty arrays for pairs without one): the nodes, the moves by class, the length of the
+    lattice paths, and with a shortcut span the shortened length (wa_grid_pose_shortcut's with pose_shortcut, else the plain one's)"""
+    nx, nxy = grid.nx, grid.nx * grid.ny
+    by_class = np.zeros(4, np.int64)
+    for p in ids_all:
+        a, b = p[:-1], p[1:]
+        by_class += np.bincount((a % nx != b % nx).astype(np.int64) + ((a // nx) % grid.ny != (b // nx) % grid.ny) + (a // nxy != b // nxy), minlength=4)
+    q = dict(nodes_total=int(sum(len(p) for p in ids_all)), moves_by_class=[int(v) for v in by_class[1:]],
+             length_total=float(api.shortcut_paths(grid, ids_all, 1)[1].sum()))
+    if shortcut and pose_shortcut:
+        q.update(shortened_length_total=float(api.pose_shortcut_paths(grid, dirs, tool, max_turn, ids_all, ks_all, shortcut)[3].sum()))
+    elif shortcut:
+        q.update(shortened_length_total=float(api.shortcut_paths(grid, ids_all, shortcut)[1].sum()))
+    return q
+
+
+def plan_pose(grid, point_ids, dirs, tool, max_turn, rank=0, world=1, shortcut=0, pose_shortcut=False, costs=None, diag=None):
     """--pose-paths MAX_TURN: the pair paths from the exact search over (voxel, torch direction) (wa_grid_pose_paths): every node has a
     direction in which the torch body clears the metal, and from node to node the torch turns by at most MAX_TURN.  Costs and return
     values as plan_exact; the directions per node are left in plan_pose.last_dirs.  A path shortened by line of sight (shortcut alone,
@@ -135,7 +152,10 @@ def plan_pose(grid, point_ids, dirs, tool, max_turn, rank=0, world=1, shortcut=0
     pairs) are left in plan_pose.last_pose_shortcut, the hold of every shortened segment in plan_pose.last_holds (what --pose-fit fits with).
     costs (--pose-turn-costs, an api.pose_costs): the pair paths come from wa_grid_pose_weighted_paths instead, which charges every
     step its turn and the voxel it enters; the pair costs stay lengths.  plan_pose.last_totals holds turn_totals per planner (this
-    rank's pairs): of wa_grid_pose_paths always, of the weighted planner beside it when it is used."""
+    rank's pairs): of wa_grid_pose_paths always, of the weighted planner beside it when it is used.
+    diag (--pose-diagonal, an api.pose_diag_costs): the pair paths come from wa_grid_pose_diag_paths instead, which moves on the
+    26-neighbour lattice and keeps the direction on a diagonal move; wa_grid_pose_diag_matrix gives the same pairs' costs, and every
+    path must cost what the matrix says.  The planner it replaces has run above: plan_pose.last_diagonal holds both planners' totals."""
     P = len(point_ids)
     pairs = [(i, j) for i in range(P) for j in range(i + 1, P)]
     mine = [k for k in range(len(pairs)) if k % world == rank]
@@ -149,11 +169,28 @@ def plan_pose(grid, point_ids, dirs, tool, max_turn, rank=0, world=1, shortcut=0
         plan_pose.last_totals.update(pose_weighted_paths=dict(turn_totals(dirs, ids_all, ks_all), t_s=time.perf_counter() - t0,
                                                               cost_total=int(hops[hops >= 0].sum())))
     ids_all = [np.zeros(0, np.int64) if p is None else p for p in ids_all]
+    ks_some = [np.zeros(0, np.int32) if k is None else k for k in ks_all]
+    plan_pose.last_diagonal = None
+    if diag is not None:
+        stairs = dict(pose_path_totals(grid, dirs, tool, max_turn, ids_all, ks_some, shortcut, pose_shortcut),
+                      planner="wa_grid_pose_weighted_paths" if costs is not None else "wa_grid_pose_paths", pairs_reached=int((hops >= 0).sum()))
+        t0 = time.perf_counter()
+        matrix = grid.pose_diag_matrix(dirs, tool, max_turn, diag, point_ids)
+        t1 = time.perf_counter()
+        hops, ids_all, ks_all = grid.pose_diag_paths(dirs, tool, max_turn, diag, starts, ends)
+        t2 = time.perf_counter()
+        if [int(matrix[pairs[k]]) for k in mine] != hops.tolist():
+            raise SystemExit("wa_grid_pose_diag_paths and wa_grid_pose_diag_matrix disagree on a pair's cost")
+        ids_all = [np.zeros(0, np.int64) if p is None else p for p in ids_all]
+        ks_some = [np.zeros(0, np.int32) if k is None else k for k in ks_all]
+        plan_pose.last_totals.update(pose_diag_paths=dict(turn_totals(dirs, ids_all, ks_all), t_s=t2 - t1, cost_total=int(hops[hops >= 0].sum())))
+        plan_pose.last_diagonal = dict(pose_path_totals(grid, dirs, tool, max_turn, ids_all, ks_some, shortcut, pose_shortcut),
+                                       step=[int(v) for v in diag.c.step], t_matrix_s=t1 - t0, t_paths_s=t2 - t1,
+                                       pairs_reached=int((hops >= 0).sum()), cost_total=int(hops[hops >= 0].sum()), staircase=stairs)
     wps, lengths = api.shortcut_paths(grid, ids_all, shortcut or 1)
     plan_pose.last_pose_shortcut, holds = None, None
     if pose_shortcut:
         plain_total = float(lengths.sum())
-        ks_some = [np.zeros(0, np.int32) if k is None else k for k in ks_all]
         wps, _, holds, lengths, summary = api.pose_shortcut_paths(grid, dirs, tool, max_turn, ids_all, ks_some, shortcut)
         plan_pose.last_pose_shortcut = dict({k: summary[k] for k in ("n_waypoints", "n_held_start", "n_held_end", "n_unheld", "max_hold_turn")},
                                             length_total=float(lengths.sum()), plain_length_total=plain_total)
@@ -642,6 +679,12 @@ def main():
                          "15); the pair costs stay what they are.  With it --safe-paths G may be combined with --pose-paths: entering a "
                          "voxel then adds min(15, its clearance cost - 1) with bands at 1^2 .. G^2.  pose_paths.planners reports hops, "
                          "direction changes and the sum of U per planner")
+    ap.add_argument("--pose-diagonal", type=int, nargs="*", default=None, metavar="STEP",
+                    help="needs --pose-paths: the pair paths come from wa_grid_pose_diag_paths, which moves on the 26-neighbour lattice -- "
+                         "a face, edge and corner move cost F E C (three integers 1 .. 16, default 3 4 5), a diagonal move keeps the torch "
+                         "direction and needs it open in every voxel of the box it spans.  With --pose-turn-costs HOP must equal F, and the "
+                         "bands and costs apply to face moves.  pose_diagonal reports times, nodes, moves by class and lengths beside the "
+                         "totals of the staircase planner it replaces")
     ap.add_argument("--pose-shortcut", action="store_true",
                     help="needs --pose-paths and --shortcut: the waypoints and costs of the pair paths come from wa_grid_pose_shortcut, which "
                          "straightens a stretch only where a planned direction stays open along the whole segment and keeps MAX_TURN at the "
@@ -678,6 +721,17 @@ def main():
             ap.error("--pose-turn-costs takes HOP and U1=C1[,U2=C2...] in integers")
         if len(bands) > 4:
             ap.error("--pose-turn-costs takes at most 4 bands")
+    pose_diagonal = None
+    if args.pose_diagonal is not None:
+        if args.pose_paths is None:
+            ap.error("--pose-diagonal needs --pose-paths")
+        if len(args.pose_diagonal) not in (0, 3) or not all(1 <= v <= 16 for v in args.pose_diagonal):
+            ap.error("--pose-diagonal takes no values (3 4 5) or the three steps F E C, each 1 .. 16")
+        pose_diagonal = list(args.pose_diagonal) or [3, 4, 5]
+        if pose_turn_costs is not None and pose_turn_costs[0] != pose_diagonal[0]:
+            ap.error("--pose-diagonal with --pose-turn-costs: HOP (%d) must equal the face step F (%d)" % (pose_turn_costs[0], pose_diagonal[0]))
+        if pose_turn_costs is not None and not 1 <= pose_turn_costs[0] <= 8:
+            ap.error("--pose-turn-costs takes a HOP of 1 .. 8")
     if args.pose_shortcut and (args.pose_paths is None or not args.shortcut):
         ap.error("--pose-shortcut needs --pose-paths and --shortcut")
     if args.pose_fit and (not args.pose_shortcut or args.fit is None):
@@ -773,14 +827,18 @@ def main():
     t0 = time.perf_counter()
     if args.pose_paths is not None:
         pose_tool, pose_dirs, _ = torch_tool_and_cone(metal, args.torch)
-        pose_costs = None
+        pose_costs, pose_diag = None, None
         if pose_turn_costs is not None:
             pen = None
             if args.safe_paths:
                 pen = np.clip(grid.clearance_costs([k * k for k in range(1, args.safe_paths + 1)]).astype(np.int32) - 1, 0, 15).astype(np.uint8)
             pose_costs = api.pose_costs(*pose_turn_costs, pen)
+            if pose_diagonal is not None:
+                pose_diag = api.pose_diag_costs(pose_diagonal, pose_turn_costs[1], pose_turn_costs[2], pen)
+        elif pose_diagonal is not None:
+            pose_diag = api.pose_diag_costs(pose_diagonal, [], [0])
         cost, paths, n_mine = plan_pose(grid, pts, pose_dirs, pose_tool, args.pose_paths, rank, world, shortcut=args.max_span if args.shortcut else 0,
-                                        pose_shortcut=args.pose_shortcut, costs=pose_costs)
+                                        pose_shortcut=args.pose_shortcut, costs=pose_costs, diag=pose_diag)
     elif both:
         cost, paths, n_mine = plan_safe_diagonal(grid, pts, args.safe_paths, args.diagonal_paths, args.safe_gain, rank, world,
                                                  shortcut=args.max_span if args.shortcut else 0, extra_pen=extra_pen)
@@ -830,6 +888,8 @@ def main():
                                                      safe_paths=args.safe_paths or 0))
         if plan_pose.last_pose_shortcut is not None:
             out["pose_paths"].update(shortcut=plan_pose.last_pose_shortcut)
+        if plan_pose.last_diagonal is not None:
+            out.update(pose_diagonal=plan_pose.last_diagonal)
     if torch_grid is not None and rank == 0:
         out.update(torch_grid=dict(torch_grid, paths=torch_grid_report(base, count, paths, paths_without, args.max_span if args.shortcut else 0)))
     if rank == 0 and args.geodesic:

@@ -1267,6 +1267,60 @@ int wa_traj_tick_axes_stops(const wa_grid *g, const wa_traj *t, const int32_t *q
 int wa_traj_axes_dwells(const wa_traj *t, const int32_t *q, double omega, const double *dwell_in /* n-1 or NULL */,
                         double *dwell_out /* n-1, host */, wa_axes_dwells_summary *sum);
 
+/* ---- diagonal pose paths: 26-neighbour moves over the states (voxel, direction) (not in the reference) ----
+ *      wa_grid_pose_* and wa_grid_pose_weighted_* move along the six axes only, so a path for which a sequence of open directions is
+ *      known to exist is a Manhattan staircase; wa_grid_chamfer_* moves diagonally but knows nothing of the torch.  Here the states and
+ *      the face steps are those of the turn-cost pose paths, and a diagonal move is added that keeps the direction.  The rules continue
+ *      the numbering of the torch section.  States, open(v, k), adj(k, k'), seeds, pins and keys are those of rules 17 - 19, unchanged;
+ *      the turn classes are rule 31's; U(a, b) is rule 2's.  Integers only.
+ * 43. The cost description wa_pose_diag_costs.  step[0 .. 2]: the face, edge and corner move, each 1 .. 16.  n_bands, turn_band,
+ *     turn_cost and pen exactly as in rule 30.
+ *     A move changes each coordinate by -1, 0 or +1; its class c = 1 .. 3 is the number of coordinates that change.
+ *     c = 1: the step (v, k) -> (v', k') of rule 18 (adj(k, k') and open(v', k')); it costs step[0] + turn_cost[class(k, k')] + pen[v'].
+ *     c = 2 or 3: (v, k) -> (v', k), the SAME direction; it exists iff all 2^c voxels of the box that v and v' span are inside the grid
+ *     and have k open (the box rule of wa_grid_chamfer_*, on open(., k) in place of free); it costs step[c - 1] + pen[v'].
+ *     The torch does not turn during a diagonal move, nor in place.  The rule is symmetric: the reverse of a move is a move.
+ * 44. dist(s; v, k), cost(s; v), the pinned minimum cost(s; t, pin), WA_DIST_NONE and the end state of a pair are rules 32 and 33's with
+ *     the moves of rule 43.  Walking back from (v, k) at dist L > 0 the predecessors are tried in this order: first the six faces in
+ *     the order -x, +x, -y, +y, -z, +z, of the first such voxel inside the grid that has some k' with adj(k', k) and
+ *     dist(k') + step[0] + turn_cost[class(k', k)] + pen[v] == L the lowest such k' (rule 33); then the 12 edge offsets, then the 8
+ *     corner offsets, each group sorted by (dz, dy, dx) ascending (the order of wa_grid_chamfer_paths): the first offset o for which the
+ *     move (v + o, k) -> (v, k) exists and dist(s; v + o, k) == L - step[c - 1] - pen[v].  The path is returned start first.
+ * 45. wa_grid_pose_diag_fields, _matrix and _paths take the arguments of wa_grid_pose_weighted_fields, _matrix and _paths with a
+ *     wa_pose_diag_costs, and return what rule 34 says with these distances and paths (len_out REQUIRED, the capacity protocol unchanged).
+ *     Identities.  (1) With step = {h, 2h, 3h}, h = 1 .. 5, and no pen, all three calls return the bytes of wa_grid_pose_weighted_* with
+ *     hop_cost = h and the same bands and turn costs: a diagonal exists only where its face detour with the direction kept exists at the
+ *     same price, and faces are asked first; with h = 1 and zero turn costs these are the bytes of wa_grid_pose_*.  (2) With K = 1 the
+ *     bytes are those of wa_grid_chamfer_weighted_* with the same step and pen on the grid wa_grid_tool_fit gives for min_dirs = 1 and
+ *     no keep ids, every direction index 0.  (3) With max_turn = 0, pairwise distinct q and no pins, dist(s; ., k) is the
+ *     wa_grid_chamfer_weighted_fields distance from s on the grid whose free voxels are {v : open(v, k)}, all WA_DIST_NONE where
+ *     open(s, k) does not hold.  (4) Multiplying every step, turn cost and pen byte by one factor multiplies every distance by it and
+ *     keeps every path.  (5) Without pen and with the same pins on both sides the matrix is symmetric; with pen and no pins
+ *     d(i, j) - pen[j] == d(j, i) - pen[i].
+ * 46. Errors.  Rules 23 and 35 apply, with a step[i] outside 1 .. 16 in the place of hop_cost.  WA_ERR_STATE past
+ *     (R - 1) * (K * n_free - 1) + R + 1 levels (capped at 2^31 - 33), R as in rule 47.
+ * 47. Memory.  R = max(step[0] + max turn_cost, step[1], step[2]) + P + 1 settled sets per source, P = the largest pen byte present on a
+ *     free voxel; a source costs (R + 1) * W * 8 * n bytes of bitmaps plus the fields of rule 36; chunks as in rule 36.
+ * Same bytes on every call; everything runs on the context's stream; g is not modified.  The masks, the step matrices and the device
+ * copy of pen are rebuilt by every call; nothing is cached with the grid.  Not covered: turns during a diagonal move, turns in place,
+ * per-edge costs. */
+typedef struct {
+    int32_t step[3];                           /* face, edge, corner move: each 1 .. 16 */
+    int32_t n_bands;                           /* as wa_pose_costs */
+    int32_t turn_band[WA_POSE_MAX_BANDS];
+    int32_t turn_cost[WA_POSE_MAX_BANDS + 1];
+    const uint8_t *pen;                        /* as wa_pose_costs: 0 .. WA_POSE_COST_MAX on free voxels, NULL = zero */
+} wa_pose_diag_costs;
+int wa_grid_pose_diag_fields(const wa_grid *g, const float *dirs, int32_t K, const wa_tool_beads *tool, int32_t max_turn,
+                             const wa_pose_diag_costs *costs, const int64_t *src_ids, const int32_t *src_pin, int32_t n_src, int32_t *cost_out,
+                             int32_t *state_out);
+int wa_grid_pose_diag_matrix(const wa_grid *g, const float *dirs, int32_t K, const wa_tool_beads *tool, int32_t max_turn,
+                             const wa_pose_diag_costs *costs, const int64_t *point_ids, const int32_t *point_pin, int32_t n_pts, int32_t *cost_out);
+int wa_grid_pose_diag_paths(const wa_grid *g, const float *dirs, int32_t K, const wa_tool_beads *tool, int32_t max_turn,
+                            const wa_pose_diag_costs *costs, const int64_t *start_ids, const int64_t *end_ids, const int32_t *pin_start,
+                            const int32_t *pin_end, int32_t n_pairs, const int64_t *off, int64_t *ids_out, int32_t *dir_out,
+                            int32_t *cost_out, int32_t *len_out);
+
 #ifdef __cplusplus
 }
 #endif

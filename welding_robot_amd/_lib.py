@@ -114,6 +114,11 @@ class PoseCosts(C.Structure):
                 ("turn_cost", C.c_int32 * (POSE_MAX_BANDS + 1)), ("pen", C.c_void_p)]
 
 
+class PoseDiagCosts(C.Structure):
+    _fields_ = [("step", C.c_int32 * 3), ("n_bands", C.c_int32), ("turn_band", C.c_int32 * POSE_MAX_BANDS),
+                ("turn_cost", C.c_int32 * (POSE_MAX_BANDS + 1)), ("pen", C.c_void_p)]
+
+
 class TickAxesSummary(C.Structure):
     _fields_ = [("n_ticks", C.c_int64), ("n_outside", C.c_int64), ("n_blocked", C.c_int64), ("first_blocked", C.c_int64),
                 ("n_near", C.c_int64), ("max_tick_turn", C.c_int64)]
@@ -262,6 +267,9 @@ SYMBOLS = {
     "wa_grid_pose_weighted_fields": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, C.POINTER(PoseCosts), _P, _P, _I, _P, _P]),
     "wa_grid_pose_weighted_matrix": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, C.POINTER(PoseCosts), _P, _P, _I, _P]),
     "wa_grid_pose_weighted_paths": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, C.POINTER(PoseCosts), _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "wa_grid_pose_diag_fields": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, C.POINTER(PoseDiagCosts), _P, _P, _I, _P, _P]),
+    "wa_grid_pose_diag_matrix": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, C.POINTER(PoseDiagCosts), _P, _P, _I, _P]),
+    "wa_grid_pose_diag_paths": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, C.POINTER(PoseDiagCosts), _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "wa_grid_pose_shortcut": (C.c_int, [_V, _P, _I, C.POINTER(ToolBeads), _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, C.POINTER(PoseShortcutSummary)]),
     "wa_grid_pose_fit_trajectory": (C.c_int, [_V, _V, _I, _F, _I, _I64, _P, _I, C.POINTER(ToolBeads), _P, _P, C.POINTER(_V), C.POINTER(_V), _P, _P,
                                               C.POINTER(PoseFitSummary)]),

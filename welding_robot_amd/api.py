@@ -333,6 +333,11 @@ class Grid:
         per node]); None in both lists where the cost is WA_DIST_NONE.  The lists feed pose_shortcut_paths as those of pose_paths do.  Two
         calls: the first, with empty ranges, returns the costs and node counts (WA_ERR_CAPACITY is its expected status when any pair is
         reachable), the second writes the paths into ranges of those counts."""
+        return self._pose_cost_paths(self.ctx.lib.wa_grid_pose_weighted_paths, self._pose_costs(costs), dirs, tool, max_turn, starts, ends,
+                                     pin_start, pin_end)
+
+    def _pose_cost_paths(self, fn, cs, dirs, tool, max_turn, starts, ends, pin_start, pin_end):
+        """the two calls of pose_weighted_paths and pose_diag_paths: fn is the library's _paths call, cs its cost description by reference"""
         dirs, K, tool = self._torch_args(dirs, tool)
         starts = np.ascontiguousarray(starts, np.int64).reshape(-1)
         ends = np.ascontiguousarray(ends, np.int64).reshape(-1)
@@ -342,13 +347,11 @@ class Grid:
         cost, lens = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
         off = np.zeros(n + 1, np.int64)
         pad = np.zeros(1, np.int64)
-        cs = self._pose_costs(costs)
 
         def call(ids, ks):
-            return self.ctx.lib.wa_grid_pose_weighted_paths(self.h, _ptr(dirs), K, C.byref(tool), int(max_turn), cs, _ptr(starts if n else pad),
-                                                            _ptr(ends if n else pad), _ptr(ps) if ps is not None and n else None,
-                                                            _ptr(pe) if pe is not None and n else None, n, _ptr(off), _ptr(ids), _ptr(ks), _ptr(cost),
-                                                            _ptr(lens))
+            return fn(self.h, _ptr(dirs), K, C.byref(tool), int(max_turn), cs, _ptr(starts if n else pad), _ptr(ends if n else pad),
+                      _ptr(ps) if ps is not None and n else None, _ptr(pe) if pe is not None and n else None, n, _ptr(off), _ptr(ids),
+                      _ptr(ks), _ptr(cost), _ptr(lens))
         rc = call(pad, np.zeros(1, np.int32))
         if rc not in (0, 7):
             self.ctx.check(rc)
@@ -359,6 +362,48 @@ class Grid:
         cost = cost[:n]
         return (cost, [ids[off[k]:off[k + 1]].copy() if cost[k] >= 0 else None for k in range(n)],
                 [ks[off[k]:off[k + 1]].copy() if cost[k] >= 0 else None for k in range(n)])
+
+    def _pose_diag_costs(self, costs):
+        assert isinstance(costs, PoseDiagCosts), "costs come from api.pose_diag_costs"
+        assert costs.pen is None or costs.pen.size == self.n, "a penalty array holds one byte per voxel"
+        return C.byref(costs.c)
+
+    def pose_diag_fields(self, dirs, tool, max_turn, costs, ids, pins=None, states=False):
+        """wa_grid_pose_diag_fields: pose_weighted_fields on the 26-neighbour lattice -- `costs` (api.pose_diag_costs) charges a face move
+        step[0] plus the turn cost of its change of direction, an edge or corner move step[1] or step[2]; a diagonal move keeps the
+        direction and needs it open in every voxel of the box it spans; every move pays the penalty of the voxel it enters.  Returns
+        int32 cost [len(ids), n] (WA_DIST_NONE (-1) where no state is reached), and with states=True also int32 [len(ids), K, n], the
+        distance of every state."""
+        dirs, K, tool = self._torch_args(dirs, tool)
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        pins = self._pins(pins, len(ids), "source")
+        cost = np.empty((len(ids), self.n), np.int32)
+        state = np.empty((len(ids), K, self.n), np.int32) if states else None
+        pad = np.zeros(1, np.int32)
+        self.ctx.check(self.ctx.lib.wa_grid_pose_diag_fields(self.h, _ptr(dirs), K, C.byref(tool), int(max_turn), self._pose_diag_costs(costs),
+                                                             _ptr(ids if len(ids) else np.zeros(1, np.int64)),
+                                                             _ptr(pins) if pins is not None and len(ids) else None, len(ids),
+                                                             _ptr(cost if cost.size else pad), (_ptr(state if state.size else pad)) if states else None))
+        return (cost, state) if states else cost
+
+    def pose_diag_matrix(self, dirs, tool, max_turn, costs, ids, pins=None):
+        """wa_grid_pose_diag_matrix: int32 [P, P] of those costs between the points, pins as for pose_matrix (symmetric when `costs` has
+        no penalties and both sides carry the same pins; WA_DIST_NONE (-1) where two points are not connected)"""
+        dirs, K, tool = self._torch_args(dirs, tool)
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        pins = self._pins(pins, len(ids), "point")
+        out = np.empty((len(ids), len(ids)), np.int32)
+        self.ctx.check(self.ctx.lib.wa_grid_pose_diag_matrix(self.h, _ptr(dirs), K, C.byref(tool), int(max_turn), self._pose_diag_costs(costs),
+                                                             _ptr(ids if len(ids) else np.zeros(1, np.int64)),
+                                                             _ptr(pins) if pins is not None and len(ids) else None, len(ids),
+                                                             _ptr(out if out.size else np.zeros(1, np.int32))))
+        return out
+
+    def pose_diag_paths(self, dirs, tool, max_turn, costs, starts, ends, pin_start=None, pin_end=None):
+        """wa_grid_pose_diag_paths of a batch of pairs, returned as pose_weighted_paths returns its paths (and by the same two calls):
+        consecutive nodes are 26-neighbours, and the direction index changes on face moves only.  The lists feed pose_shortcut_paths."""
+        return self._pose_cost_paths(self.ctx.lib.wa_grid_pose_diag_paths, self._pose_diag_costs(costs), dirs, tool, max_turn, starts, ends,
+                                     pin_start, pin_end)
 
     def clearance_radius(self, metres):
         """a clearance in metres as a radius in voxels (exact up to the hi-side seam of the wall, see include/weldacs.h)"""
@@ -1340,6 +1385,40 @@ def pose_costs(hop, bands, turn_costs, pen=None):
         pen = np.ascontiguousarray(pen, np.uint8).reshape(-1)
         c.pen = pen.ctypes.data
     return PoseCosts(c, pen)
+
+
+class PoseDiagCosts:
+    """a wa_pose_diag_costs (`c`) together with the penalty array it points to (`pen`, None for none)"""
+
+    def __init__(self, c, pen):
+        self.c, self.pen = c, pen
+
+
+def pose_diag_costs(step, bands, turn_costs, pen=None):
+    """the cost description of Grid.pose_diag_*: `step` = the cost of a face, an edge and a corner move (each 1 .. 16; 3, 4, 5 is the
+    usual chamfer); bands, turn_costs and pen as for pose_costs, the turn costs charged on face moves (a diagonal move keeps the
+    direction).  The ranges are checked by the library."""
+    step = np.asarray(step, np.int64).reshape(-1)
+    bands = np.asarray(bands, np.int64).reshape(-1)
+    turn_costs = np.asarray(turn_costs, np.int64).reshape(-1)
+    if len(step) != 3:
+        raise ValueError("step holds three costs: face, edge, corner")
+    if len(bands) > L.POSE_MAX_BANDS or len(turn_costs) != len(bands) + 1:
+        raise ValueError("at most %d bands, and one turn cost more than bands" % L.POSE_MAX_BANDS)
+    if max(np.abs(step).max(), np.abs(bands).max(initial=0), np.abs(turn_costs).max()) >= 2 ** 31:
+        raise ValueError("step, bands and turn_costs are int32")
+    c = L.PoseDiagCosts()
+    c.n_bands = len(bands)
+    for i in range(3):
+        c.step[i] = int(step[i])
+    for b in range(len(bands)):
+        c.turn_band[b] = int(bands[b])
+    for b in range(len(turn_costs)):
+        c.turn_cost[b] = int(turn_costs[b])
+    if pen is not None:
+        pen = np.ascontiguousarray(pen, np.uint8).reshape(-1)
+        c.pen = pen.ctypes.data
+    return PoseDiagCosts(c, pen)
 
 
 def quantise_axes(dirs):

@@ -8,50 +8,57 @@ struct PosewSetup {
     WaPosewCosts c;
     DevBuf<unsigned long long> adjw;
     DevBuf<uint8_t> pen;
-    int32_t top = 0;   // hop_cost + max turn_cost + P: the largest step
+    int32_t top = 0;   // hop_cost + max turn_cost + P: the largest step (R - 1)
 };
 
-// rule 30's ranges, and the turn classes dealt over the distinct step weights (classes of equal cost share a matrix); no device work
-static int posew_check(wa_ctx *ctx, const char *who, const wa_pose_costs *costs, WaPosewCosts *c)
+// rule 30's ranges of the bands and turn costs, and the turn classes dealt over the distinct step weights hop + turn_cost[b] (classes of
+// equal cost share a matrix); no device work.  hop is the caller's, already checked (host_pose_diag.inc passes its face step).
+static int posew_check_turns(wa_ctx *ctx, const char *who, int32_t hop, int32_t B, const int32_t *turn_band, const int32_t *turn_cost, WaPosewCosts *c)
 {
-    if (!costs) return fail(ctx, WA_ERR_ARG, "%s: costs is NULL", who);
-    if (costs->hop_cost < 1 || costs->hop_cost > 8) return fail(ctx, WA_ERR_ARG, "%s: hop_cost must be 1 .. 8", who);
-    const int32_t B = costs->n_bands;
     if (B < 0 || B > WA_POSE_MAX_BANDS) return fail(ctx, WA_ERR_ARG, "%s: n_bands must be 0 .. 4", who);
     for (int32_t b = 0; b < B; b++) {
-        if (costs->turn_band[b] < 0 || costs->turn_band[b] > 3 * (1 << 20)) return fail(ctx, WA_ERR_ARG, "%s: a turn band outside 0 .. 3 * 2^20", who);
-        if (b && costs->turn_band[b] <= costs->turn_band[b - 1]) return fail(ctx, WA_ERR_ARG, "%s: the turn bands must ascend strictly", who);
+        if (turn_band[b] < 0 || turn_band[b] > 3 * (1 << 20)) return fail(ctx, WA_ERR_ARG, "%s: a turn band outside 0 .. 3 * 2^20", who);
+        if (b && turn_band[b] <= turn_band[b - 1]) return fail(ctx, WA_ERR_ARG, "%s: the turn bands must ascend strictly", who);
     }
-    if (costs->turn_cost[0] != 0) return fail(ctx, WA_ERR_ARG, "%s: turn_cost[0] must be 0", who);
+    if (turn_cost[0] != 0) return fail(ctx, WA_ERR_ARG, "%s: turn_cost[0] must be 0", who);
     for (int32_t b = 1; b <= B; b++) {
-        if (costs->turn_cost[b] > WA_POSE_COST_MAX) return fail(ctx, WA_ERR_ARG, "%s: a turn cost above 15", who);
-        if (costs->turn_cost[b] < costs->turn_cost[b - 1]) return fail(ctx, WA_ERR_ARG, "%s: the turn costs must not decrease", who);
+        if (turn_cost[b] > WA_POSE_COST_MAX) return fail(ctx, WA_ERR_ARG, "%s: a turn cost above 15", who);
+        if (turn_cost[b] < turn_cost[b - 1]) return fail(ctx, WA_ERR_ARG, "%s: the turn costs must not decrease", who);
     }
     memset(c, 0, sizeof *c);
     c->n_bands = B;
-    for (int32_t b = 0; b < B; b++) c->band[b] = costs->turn_band[b];
+    for (int32_t b = 0; b < B; b++) c->band[b] = turn_band[b];
     for (int32_t b = 0; b <= B; b++) {
-        const int32_t w = costs->hop_cost + costs->turn_cost[b];
+        const int32_t w = hop + turn_cost[b];
         if (c->n_w == 0 || c->weight[c->n_w - 1] != w) c->weight[c->n_w++] = w;   // (non-decreasing: equal costs are neighbours)
         c->group[b] = c->n_w - 1;
     }
     return WA_OK;
 }
 
+// rule 30's ranges; no device work
+static int posew_check(wa_ctx *ctx, const char *who, const wa_pose_costs *costs, WaPosewCosts *c)
+{
+    if (!costs) return fail(ctx, WA_ERR_ARG, "%s: costs is NULL", who);
+    if (costs->hop_cost < 1 || costs->hop_cost > 8) return fail(ctx, WA_ERR_ARG, "%s: hop_cost must be 1 .. 8", who);
+    return posew_check_turns(ctx, who, costs->hop_cost, costs->n_bands, costs->turn_band, costs->turn_cost, c);
+}
+
 // uploads pen and finds P (WA_ERR_ARG for a byte above 15 on a free voxel), then the step matrices; needs pose_prepare's q on the
-// stream.  Nothing has been written to the caller's arrays when this fails.
-static int posew_prepare(const wa_grid *g, const char *who, const wa_pose_costs *costs, const PoseSetup &P, PosewSetup &S)
+// stream.  Nothing has been written to the caller's arrays when this fails.  pen: the caller's bytes (host) or NULL; other_step: the
+// largest step that is not a face weight (host_pose_diag.inc's diagonals), which the ring has to hold too.
+static int posew_prepare(const wa_grid *g, const char *who, const uint8_t *pen, const PoseSetup &P, PosewSetup &S, int32_t other_step = 0)
 {
     wa_ctx *ctx = g->ctx;
     const int64_t n = g->d.n;
     int32_t top_pen = 0;
-    if (costs->pen) {
+    if (pen) {
         DevBuf<int32_t> d_info;
         int32_t info[WA_POSEW_PEN_MAX + 2];
         hipError_t e = S.pen.alloc((size_t)n);
         e = e ? e : d_info.alloc((size_t)(WA_POSEW_PEN_MAX + 2));
         if (e != hipSuccess) { (void)hipGetLastError(); hipStreamSynchronize(ctx->stream); return fail(ctx, WA_ERR_ALLOC, "%s: the penalty array does not fit the device", who); }
-        e = hipMemcpyAsync(S.pen, costs->pen, (size_t)n, hipMemcpyHostToDevice, ctx->stream);
+        e = hipMemcpyAsync(S.pen, pen, (size_t)n, hipMemcpyHostToDevice, ctx->stream);
         e = e ? e : hipMemsetAsync(d_info, 0, sizeof info, ctx->stream);
         if (e == hipSuccess) {
             k_posew_pen_info<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(g->occ, S.pen, n, d_info);
@@ -65,7 +72,7 @@ static int posew_prepare(const wa_grid *g, const char *who, const wa_pose_costs 
         for (int32_t q = 1; q <= WA_POSEW_PEN_MAX; q++)
             if (info[q]) top_pen = q;
     }
-    S.top = S.c.weight[S.c.n_w - 1] + top_pen;
+    S.top = std::max(S.c.weight[S.c.n_w - 1], other_step) + top_pen;
     S.c.R = S.top + 1;
     const int32_t cells = S.c.n_w * P.K * P.W;
     if (S.adjw.alloc((size_t)cells) != hipSuccess) {
@@ -133,7 +140,7 @@ int wa_grid_pose_weighted_fields(const wa_grid *g, const float *dirs, int32_t K,
     if (rc || n_src == 0) return rc;
     PoseSetup P(ctx);
     rc = pose_prepare(g, fn, hq, dt, max_turn, P);
-    rc = rc ? rc : posew_prepare(g, fn, costs, P, S);
+    rc = rc ? rc : posew_prepare(g, fn, costs->pen, P, S);
     if (rc) return rc;
     const std::vector<int64_t> keys = pose_keys(src_ids, src_pin, n_src);
     const SearchKind k = posew_kind(g, P, S, state_out != nullptr, fn);
@@ -173,7 +180,7 @@ int wa_grid_pose_weighted_matrix(const wa_grid *g, const float *dirs, int32_t K,
     if (rc || n_pts == 0) return rc;
     PoseSetup P(ctx);
     rc = pose_prepare(g, fn, hq, dt, max_turn, P);
-    rc = rc ? rc : posew_prepare(g, fn, costs, P, S);
+    rc = rc ? rc : posew_prepare(g, fn, costs->pen, P, S);
     if (rc) return rc;
     const std::vector<int64_t> keys = pose_keys(point_ids, point_pin, n_pts);
     return search_rows(g, d, posew_kind(g, P, S, false, fn), keys.data(), n_pts, true, cost_out);
@@ -203,7 +210,7 @@ int wa_grid_pose_weighted_paths(const wa_grid *g, const float *dirs, int32_t K, 
     if (rc || n_pairs == 0) return rc;
     PoseSetup P(ctx);
     rc = pose_prepare(g, fn, hq, dt, max_turn, P);
-    rc = rc ? rc : posew_prepare(g, fn, costs, P, S);
+    rc = rc ? rc : posew_prepare(g, fn, costs->pen, P, S);
     if (rc) return rc;
     const std::vector<int64_t> starts = pose_keys(start_ids, pin_start, n_pairs), ends = pose_keys(end_ids, pin_end, n_pairs);
     const SearchKind k = posew_kind(g, P, S, true, fn);
