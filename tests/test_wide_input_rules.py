@@ -3,7 +3,8 @@ direction count selects, how many trips the matrix's target lookup takes, how ma
 the source chunks split.  tests/test_gpu_pose_planes.py, tests/test_gpu_wide_matrices.py and tests/test_gpu_seamtour_wide.py take their
 sizes and scenes from this file.  If a constant moves in the source, this test fails, and the GPU cases must be moved with it.
 
-  posew_pick      host_pose_weighted.inc: K <= 64 -> k_posew_level<1>, K <= 128 -> <2>, else <WA_POSE_MAX_W>
+  posew_pick      host_pose_weighted.inc: K <= 64 -> k_posew_level<1>, K <= 128 -> <2>, else <WA_POSE_MAX_W>.  k_posew_level<WMAX> holds
+                  the level kernel of both lattices and this is the only pick, so the rule covers the wa_grid_pose_diag_* calls too
   pose_max_w      WA_POSE_MAX_W: planes of 64 directions a state has at most
   max_dirs        WA_TORCH_MAX_DIRS
   pose_stride     pose_lookup_targets: the targets a thread of the source's first block takes lie 256 apart

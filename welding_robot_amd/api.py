@@ -233,112 +233,31 @@ class Grid:
         assert len(pins) == count, "one pin per " + what
         return pins
 
-    def pose_fields(self, dirs, tool, max_turn, ids, pins=None, states=False):
-        """wa_grid_pose_fields: exact hop counts over the states (voxel, direction) -- a step moves to a 6-neighbour voxel and turns the
-        torch by at most `max_turn` (the measure U of torch_axes; -1: no limit), and every state on the way has the direction open.
-        `pins`: per source a direction index the search starts with, or -1 for every open one.  Returns int32 hops [len(ids), n], the
-        least level over the directions (WA_HOPS_NONE (-1) where no state is reached), and with states=True also int32
-        [len(ids), K, n], the level of every state."""
-        dirs, K, tool = self._torch_args(dirs, tool)
+    def _pose_fields(self, fn, lead, ids, pins, states):
+        """the marshalling of the three pose _fields calls: fn(grid, *lead, ids, pins, len(ids), out, state), out int32 [len(ids), n],
+        state int32 [len(ids), K, n] or NULL; lead = (dirs, K, tool, max_turn[, costs]); empty arrays as in _search_rows"""
+        K = lead[1]
         ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
         pins = self._pins(pins, len(ids), "source")
-        hops = np.empty((len(ids), self.n), np.int32)
+        out = np.empty((len(ids), self.n), np.int32)
         state = np.empty((len(ids), K, self.n), np.int32) if states else None
         pad = np.zeros(1, np.int32)
-        self.ctx.check(self.ctx.lib.wa_grid_pose_fields(self.h, _ptr(dirs), K, C.byref(tool), int(max_turn), _ptr(ids if len(ids) else np.zeros(1, np.int64)),
-                                                        _ptr(pins) if pins is not None and len(ids) else None, len(ids),
-                                                        _ptr(hops if hops.size else pad), (_ptr(state if state.size else pad)) if states else None))
-        return (hops, state) if states else hops
+        self.ctx.check(fn(self.h, *lead, _ptr(ids if len(ids) else np.zeros(1, np.int64)), _ptr(pins) if pins is not None and len(ids) else None,
+                          len(ids), _ptr(out if out.size else pad), (_ptr(state if state.size else pad)) if states else None))
+        return (out, state) if states else out
 
-    def pose_matrix(self, dirs, tool, max_turn, ids, pins=None):
-        """wa_grid_pose_matrix: int32 [P, P] of those hop counts between the points; a point's pin restricts both the directions it starts
-        with as a source and the direction it must be reached with as a target (symmetric; WA_HOPS_NONE (-1) where two points are not
-        connected, on the diagonal too when the point has no open direction its pin allows)"""
-        dirs, K, tool = self._torch_args(dirs, tool)
+    def _pose_matrix(self, fn, lead, ids, pins):
+        """the marshalling of the three pose _matrix calls: fn(grid, *lead, ids, pins, len(ids), out), out int32 [len(ids), len(ids)]"""
         ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
         pins = self._pins(pins, len(ids), "point")
         out = np.empty((len(ids), len(ids)), np.int32)
-        self.ctx.check(self.ctx.lib.wa_grid_pose_matrix(self.h, _ptr(dirs), K, C.byref(tool), int(max_turn), _ptr(ids if len(ids) else np.zeros(1, np.int64)),
-                                                        _ptr(pins) if pins is not None and len(ids) else None, len(ids),
-                                                        _ptr(out if out.size else np.zeros(1, np.int32))))
+        self.ctx.check(fn(self.h, *lead, _ptr(ids if len(ids) else np.zeros(1, np.int64)), _ptr(pins) if pins is not None and len(ids) else None,
+                          len(ids), _ptr(out if out.size else np.zeros(1, np.int32))))
         return out
 
-    def pose_paths(self, dirs, tool, max_turn, starts, ends, pin_start=None, pin_end=None):
-        """wa_grid_pose_paths of a batch of pairs: (int32 hops, [node-id array per pair, start first], [int32 direction index per node]);
-        None in both lists where hops is WA_HOPS_NONE.  Two calls: the first, with empty ranges, returns the counts (WA_ERR_CAPACITY is
-        its expected status when any pair is reachable), the second writes the paths into ranges of hops + 1."""
-        dirs, K, tool = self._torch_args(dirs, tool)
-        starts = np.ascontiguousarray(starts, np.int64).reshape(-1)
-        ends = np.ascontiguousarray(ends, np.int64).reshape(-1)
-        assert len(starts) == len(ends)
-        n = len(starts)
-        ps, pe = self._pins(pin_start, n, "pair"), self._pins(pin_end, n, "pair")
-        hops, lens = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
-        off = np.zeros(n + 1, np.int64)
-        pad = np.zeros(1, np.int64)
-
-        def call(ids, ks):
-            return self.ctx.lib.wa_grid_pose_paths(self.h, _ptr(dirs), K, C.byref(tool), int(max_turn), _ptr(starts if n else pad),
-                                                   _ptr(ends if n else pad), _ptr(ps) if ps is not None and n else None,
-                                                   _ptr(pe) if pe is not None and n else None, n, _ptr(off), _ptr(ids), _ptr(ks), _ptr(hops),
-                                                   _ptr(lens))
-        rc = call(pad, np.zeros(1, np.int32))
-        if rc not in (0, 7):
-            self.ctx.check(rc)
-        off[1:] = np.cumsum(np.maximum(hops[:n].astype(np.int64) + 1, 0))
-        ids, ks = np.empty(max(int(off[-1]), 1), np.int64), np.empty(max(int(off[-1]), 1), np.int32)
-        if rc == 7:
-            self.ctx.check(call(ids, ks))
-        hops = hops[:n]
-        return (hops, [ids[off[k]:off[k + 1]].copy() if hops[k] >= 0 else None for k in range(n)],
-                [ks[off[k]:off[k + 1]].copy() if hops[k] >= 0 else None for k in range(n)])
-
-    def _pose_costs(self, costs):
-        assert isinstance(costs, PoseCosts), "costs come from api.pose_costs"
-        assert costs.pen is None or costs.pen.size == self.n, "a penalty array holds one byte per voxel"
-        return C.byref(costs.c)
-
-    def pose_weighted_fields(self, dirs, tool, max_turn, costs, ids, pins=None, states=False):
-        """wa_grid_pose_weighted_fields: pose_fields with a price on every step -- `costs` (api.pose_costs) charges a step its hop cost,
-        the turn cost of the class its change of direction falls in and the penalty of the voxel it enters.  Returns int32 cost
-        [len(ids), n], the least distance over the directions (WA_DIST_NONE (-1) where no state is reached), and with states=True also
-        int32 [len(ids), K, n], the distance of every state."""
-        dirs, K, tool = self._torch_args(dirs, tool)
-        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
-        pins = self._pins(pins, len(ids), "source")
-        cost = np.empty((len(ids), self.n), np.int32)
-        state = np.empty((len(ids), K, self.n), np.int32) if states else None
-        pad = np.zeros(1, np.int32)
-        self.ctx.check(self.ctx.lib.wa_grid_pose_weighted_fields(self.h, _ptr(dirs), K, C.byref(tool), int(max_turn), self._pose_costs(costs),
-                                                                 _ptr(ids if len(ids) else np.zeros(1, np.int64)),
-                                                                 _ptr(pins) if pins is not None and len(ids) else None, len(ids),
-                                                                 _ptr(cost if cost.size else pad), (_ptr(state if state.size else pad)) if states else None))
-        return (cost, state) if states else cost
-
-    def pose_weighted_matrix(self, dirs, tool, max_turn, costs, ids, pins=None):
-        """wa_grid_pose_weighted_matrix: int32 [P, P] of those costs between the points, pins as for pose_matrix (symmetric when `costs`
-        has no penalties and both sides carry the same pins; WA_DIST_NONE (-1) where two points are not connected)"""
-        dirs, K, tool = self._torch_args(dirs, tool)
-        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
-        pins = self._pins(pins, len(ids), "point")
-        out = np.empty((len(ids), len(ids)), np.int32)
-        self.ctx.check(self.ctx.lib.wa_grid_pose_weighted_matrix(self.h, _ptr(dirs), K, C.byref(tool), int(max_turn), self._pose_costs(costs),
-                                                                 _ptr(ids if len(ids) else np.zeros(1, np.int64)),
-                                                                 _ptr(pins) if pins is not None and len(ids) else None, len(ids),
-                                                                 _ptr(out if out.size else np.zeros(1, np.int32))))
-        return out
-
-    def pose_weighted_paths(self, dirs, tool, max_turn, costs, starts, ends, pin_start=None, pin_end=None):
-        """wa_grid_pose_weighted_paths of a batch of pairs: (int32 cost, [node-id array per pair, start first], [int32 direction index
-        per node]); None in both lists where the cost is WA_DIST_NONE.  The lists feed pose_shortcut_paths as those of pose_paths do.  Two
-        calls: the first, with empty ranges, returns the costs and node counts (WA_ERR_CAPACITY is its expected status when any pair is
-        reachable), the second writes the paths into ranges of those counts."""
-        return self._pose_cost_paths(self.ctx.lib.wa_grid_pose_weighted_paths, self._pose_costs(costs), dirs, tool, max_turn, starts, ends,
-                                     pin_start, pin_end)
-
-    def _pose_cost_paths(self, fn, cs, dirs, tool, max_turn, starts, ends, pin_start, pin_end):
-        """the two calls of pose_weighted_paths and pose_diag_paths: fn is the library's _paths call, cs its cost description by reference"""
-        dirs, K, tool = self._torch_args(dirs, tool)
+    def _pose_paths(self, fn, lead, starts, ends, pin_start, pin_end):
+        """the two calls of the three pose _paths calls: fn is the library's _paths call, lead as for _pose_fields.  The first call, with
+        empty ranges, returns the distances and node counts, the second writes the paths into ranges of those counts."""
         starts = np.ascontiguousarray(starts, np.int64).reshape(-1)
         ends = np.ascontiguousarray(ends, np.int64).reshape(-1)
         assert len(starts) == len(ends)
@@ -349,9 +268,8 @@ class Grid:
         pad = np.zeros(1, np.int64)
 
         def call(ids, ks):
-            return fn(self.h, _ptr(dirs), K, C.byref(tool), int(max_turn), cs, _ptr(starts if n else pad), _ptr(ends if n else pad),
-                      _ptr(ps) if ps is not None and n else None, _ptr(pe) if pe is not None and n else None, n, _ptr(off), _ptr(ids),
-                      _ptr(ks), _ptr(cost), _ptr(lens))
+            return fn(self.h, *lead, _ptr(starts if n else pad), _ptr(ends if n else pad), _ptr(ps) if ps is not None and n else None,
+                      _ptr(pe) if pe is not None and n else None, n, _ptr(off), _ptr(ids), _ptr(ks), _ptr(cost), _ptr(lens))
         rc = call(pad, np.zeros(1, np.int32))
         if rc not in (0, 7):
             self.ctx.check(rc)
@@ -363,10 +281,62 @@ class Grid:
         return (cost, [ids[off[k]:off[k + 1]].copy() if cost[k] >= 0 else None for k in range(n)],
                 [ks[off[k]:off[k + 1]].copy() if cost[k] >= 0 else None for k in range(n)])
 
-    def _pose_diag_costs(self, costs):
-        assert isinstance(costs, PoseDiagCosts), "costs come from api.pose_diag_costs"
+    def _pose_costs(self, costs, cls, factory):
+        """the cost description of a pose call by reference: `costs` is an instance of `cls`, which api.`factory` returns"""
+        assert isinstance(costs, cls), "costs come from api." + factory
         assert costs.pen is None or costs.pen.size == self.n, "a penalty array holds one byte per voxel"
         return C.byref(costs.c)
+
+    def pose_fields(self, dirs, tool, max_turn, ids, pins=None, states=False):
+        """wa_grid_pose_fields: exact hop counts over the states (voxel, direction) -- a step moves to a 6-neighbour voxel and turns the
+        torch by at most `max_turn` (the measure U of torch_axes; -1: no limit), and every state on the way has the direction open.
+        `pins`: per source a direction index the search starts with, or -1 for every open one.  Returns int32 hops [len(ids), n], the
+        least level over the directions (WA_HOPS_NONE (-1) where no state is reached), and with states=True also int32
+        [len(ids), K, n], the level of every state."""
+        dirs, K, tool = self._torch_args(dirs, tool)
+        lead = (_ptr(dirs), K, C.byref(tool), int(max_turn))
+        return self._pose_fields(self.ctx.lib.wa_grid_pose_fields, lead, ids, pins, states)
+
+    def pose_matrix(self, dirs, tool, max_turn, ids, pins=None):
+        """wa_grid_pose_matrix: int32 [P, P] of those hop counts between the points; a point's pin restricts both the directions it starts
+        with as a source and the direction it must be reached with as a target (symmetric; WA_HOPS_NONE (-1) where two points are not
+        connected, on the diagonal too when the point has no open direction its pin allows)"""
+        dirs, K, tool = self._torch_args(dirs, tool)
+        lead = (_ptr(dirs), K, C.byref(tool), int(max_turn))
+        return self._pose_matrix(self.ctx.lib.wa_grid_pose_matrix, lead, ids, pins)
+
+    def pose_paths(self, dirs, tool, max_turn, starts, ends, pin_start=None, pin_end=None):
+        """wa_grid_pose_paths of a batch of pairs: (int32 hops, [node-id array per pair, start first], [int32 direction index per node]);
+        None in both lists where hops is WA_HOPS_NONE.  Two calls: the first, with empty ranges, returns the counts (WA_ERR_CAPACITY is
+        its expected status when any pair is reachable), the second writes the paths into ranges of hops + 1."""
+        dirs, K, tool = self._torch_args(dirs, tool)
+        lead = (_ptr(dirs), K, C.byref(tool), int(max_turn))
+        return self._pose_paths(self.ctx.lib.wa_grid_pose_paths, lead, starts, ends, pin_start, pin_end)
+
+    def pose_weighted_fields(self, dirs, tool, max_turn, costs, ids, pins=None, states=False):
+        """wa_grid_pose_weighted_fields: pose_fields with a price on every step -- `costs` (api.pose_costs) charges a step its hop cost,
+        the turn cost of the class its change of direction falls in and the penalty of the voxel it enters.  Returns int32 cost
+        [len(ids), n], the least distance over the directions (WA_DIST_NONE (-1) where no state is reached), and with states=True also
+        int32 [len(ids), K, n], the distance of every state."""
+        dirs, K, tool = self._torch_args(dirs, tool)
+        lead = (_ptr(dirs), K, C.byref(tool), int(max_turn), self._pose_costs(costs, PoseCosts, "pose_costs"))
+        return self._pose_fields(self.ctx.lib.wa_grid_pose_weighted_fields, lead, ids, pins, states)
+
+    def pose_weighted_matrix(self, dirs, tool, max_turn, costs, ids, pins=None):
+        """wa_grid_pose_weighted_matrix: int32 [P, P] of those costs between the points, pins as for pose_matrix (symmetric when `costs`
+        has no penalties and both sides carry the same pins; WA_DIST_NONE (-1) where two points are not connected)"""
+        dirs, K, tool = self._torch_args(dirs, tool)
+        lead = (_ptr(dirs), K, C.byref(tool), int(max_turn), self._pose_costs(costs, PoseCosts, "pose_costs"))
+        return self._pose_matrix(self.ctx.lib.wa_grid_pose_weighted_matrix, lead, ids, pins)
+
+    def pose_weighted_paths(self, dirs, tool, max_turn, costs, starts, ends, pin_start=None, pin_end=None):
+        """wa_grid_pose_weighted_paths of a batch of pairs: (int32 cost, [node-id array per pair, start first], [int32 direction index
+        per node]); None in both lists where the cost is WA_DIST_NONE.  The lists feed pose_shortcut_paths as those of pose_paths do.  Two
+        calls: the first, with empty ranges, returns the costs and node counts (WA_ERR_CAPACITY is its expected status when any pair is
+        reachable), the second writes the paths into ranges of those counts."""
+        dirs, K, tool = self._torch_args(dirs, tool)
+        lead = (_ptr(dirs), K, C.byref(tool), int(max_turn), self._pose_costs(costs, PoseCosts, "pose_costs"))
+        return self._pose_paths(self.ctx.lib.wa_grid_pose_weighted_paths, lead, starts, ends, pin_start, pin_end)
 
     def pose_diag_fields(self, dirs, tool, max_turn, costs, ids, pins=None, states=False):
         """wa_grid_pose_diag_fields: pose_weighted_fields on the 26-neighbour lattice -- `costs` (api.pose_diag_costs) charges a face move
@@ -375,35 +345,22 @@ class Grid:
         int32 cost [len(ids), n] (WA_DIST_NONE (-1) where no state is reached), and with states=True also int32 [len(ids), K, n], the
         distance of every state."""
         dirs, K, tool = self._torch_args(dirs, tool)
-        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
-        pins = self._pins(pins, len(ids), "source")
-        cost = np.empty((len(ids), self.n), np.int32)
-        state = np.empty((len(ids), K, self.n), np.int32) if states else None
-        pad = np.zeros(1, np.int32)
-        self.ctx.check(self.ctx.lib.wa_grid_pose_diag_fields(self.h, _ptr(dirs), K, C.byref(tool), int(max_turn), self._pose_diag_costs(costs),
-                                                             _ptr(ids if len(ids) else np.zeros(1, np.int64)),
-                                                             _ptr(pins) if pins is not None and len(ids) else None, len(ids),
-                                                             _ptr(cost if cost.size else pad), (_ptr(state if state.size else pad)) if states else None))
-        return (cost, state) if states else cost
+        lead = (_ptr(dirs), K, C.byref(tool), int(max_turn), self._pose_costs(costs, PoseDiagCosts, "pose_diag_costs"))
+        return self._pose_fields(self.ctx.lib.wa_grid_pose_diag_fields, lead, ids, pins, states)
 
     def pose_diag_matrix(self, dirs, tool, max_turn, costs, ids, pins=None):
         """wa_grid_pose_diag_matrix: int32 [P, P] of those costs between the points, pins as for pose_matrix (symmetric when `costs` has
         no penalties and both sides carry the same pins; WA_DIST_NONE (-1) where two points are not connected)"""
         dirs, K, tool = self._torch_args(dirs, tool)
-        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
-        pins = self._pins(pins, len(ids), "point")
-        out = np.empty((len(ids), len(ids)), np.int32)
-        self.ctx.check(self.ctx.lib.wa_grid_pose_diag_matrix(self.h, _ptr(dirs), K, C.byref(tool), int(max_turn), self._pose_diag_costs(costs),
-                                                             _ptr(ids if len(ids) else np.zeros(1, np.int64)),
-                                                             _ptr(pins) if pins is not None and len(ids) else None, len(ids),
-                                                             _ptr(out if out.size else np.zeros(1, np.int32))))
-        return out
+        lead = (_ptr(dirs), K, C.byref(tool), int(max_turn), self._pose_costs(costs, PoseDiagCosts, "pose_diag_costs"))
+        return self._pose_matrix(self.ctx.lib.wa_grid_pose_diag_matrix, lead, ids, pins)
 
     def pose_diag_paths(self, dirs, tool, max_turn, costs, starts, ends, pin_start=None, pin_end=None):
         """wa_grid_pose_diag_paths of a batch of pairs, returned as pose_weighted_paths returns its paths (and by the same two calls):
         consecutive nodes are 26-neighbours, and the direction index changes on face moves only.  The lists feed pose_shortcut_paths."""
-        return self._pose_cost_paths(self.ctx.lib.wa_grid_pose_diag_paths, self._pose_diag_costs(costs), dirs, tool, max_turn, starts, ends,
-                                     pin_start, pin_end)
+        dirs, K, tool = self._torch_args(dirs, tool)
+        lead = (_ptr(dirs), K, C.byref(tool), int(max_turn), self._pose_costs(costs, PoseDiagCosts, "pose_diag_costs"))
+        return self._pose_paths(self.ctx.lib.wa_grid_pose_diag_paths, lead, starts, ends, pin_start, pin_end)
 
     def clearance_radius(self, metres):
         """a clearance in metres as a radius in voxels (exact up to the hi-side seam of the wall, see include/weldacs.h)"""

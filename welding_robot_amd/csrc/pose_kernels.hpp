@@ -6,10 +6,10 @@
 // no word.  Every kernel of one search runs on one stream: a level reads what the launch before it wrote, nothing inside a launch reads
 // what the same launch writes.
 //   k_pose_adj        the K x W adjacency bit matrix from q and max_turn
-//   k_pose_seed       level 0 of every source of a chunk
 //   k_pose_level      one level for every source of a chunk (pull form)
 //   k_pose_pair_hops  hop count and end direction per pair
 //   k_pose_walkback   the path of a pair, one wavefront each
+// Level 0 is k_posew_seed's (pose_weighted_kernels.hpp) with a ring of one set: the first frontier.
 #pragma once
 #include "reach_kernels.hpp"
 
@@ -39,35 +39,6 @@ __global__ __launch_bounds__(256) void k_pose_adj(const short4 *__restrict__ q, 
         if (max_turn < 0 || U <= max_turn) bits |= 1ull << b;
     }
     adj[i] = bits;
-}
-
-// level 0 of every source of a chunk: the open directions of its voxel (all of them, or the pinned one) in `seen` and in the first
-// frontier (both zeroed before), level 0 in its hop field and its state field, last[s] = 0, stop[s] = 0.  An empty seed writes nothing:
-// the first level finds no frontier and the search ends there.
-__global__ __launch_bounds__(256) void k_pose_seed(const long long *__restrict__ src, int32_t n_src, const unsigned long long *__restrict__ open,
-                                                   int64_t n, int32_t K, int64_t words, int64_t ints, unsigned long long *__restrict__ seen,
-                                                   unsigned long long *__restrict__ frontier, int32_t *__restrict__ field, int32_t keep_states,
-                                                   int32_t *__restrict__ last, int32_t *__restrict__ stop)
-{
-    const int32_t s = (int32_t)(blockIdx.x * 256 + threadIdx.x);
-    if (s >= n_src) return;
-    const long long v = pose_key_id(src[s]);
-    const int32_t pin = pose_key_pin(src[s]);
-    const int32_t W = (K + 63) >> 6;
-    bool any = false;
-    for (int32_t w = 0; w < W; w++) {
-        unsigned long long b = open[(int64_t)w * n + v];
-        if (pin >= 0) b = (pin >> 6) == w ? b & (1ull << (pin & 63)) : 0ull;
-        if (!b) continue;
-        any = true;
-        seen[(int64_t)s * words + (int64_t)w * n + v] = b;
-        frontier[(int64_t)s * words + (int64_t)w * n + v] = b;
-        if (field && keep_states)
-            for (unsigned long long r = b; r; r &= r - 1) field[(int64_t)s * ints + n + (int64_t)(w * 64 + __builtin_ctzll(r)) * n + v] = 0;
-    }
-    if (any && field) field[(int64_t)s * ints + v] = 0;
-    last[s] = 0;
-    stop[s] = 0;
 }
 
 // The matrix's targets, by all 256 threads of the first block of a source: `value` goes to row_out[t] for every target t that has no

@@ -41,7 +41,6 @@
 #include "reach_kernels.hpp"
 #include "pose_kernels.hpp"
 #include "pose_weighted_kernels.hpp"
-#include "pose_diag_kernels.hpp"
 #include "pose_shortcut_kernels.hpp"
 #include "pose_fit_kernels.hpp"
 #include "ticks_kernels.hpp"
@@ -858,7 +857,6 @@ void *wa_ctx_stream(wa_ctx *c) { return c ? (void *)c->stream : nullptr; }
 #include "host_reach.inc"
 #include "host_pose.inc"
 #include "host_pose_weighted.inc"
-#include "host_pose_diag.inc"
 #include "host_pose_shortcut.inc"
 #include "host_pose_fit.inc"
 #include "host_ticks.inc"
