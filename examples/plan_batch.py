@@ -439,7 +439,7 @@ def smooth(ctx, grid, segs, wsegs, rev, fit=None, pose_fit=None):
     return traj, ok, info
 
 
-def seam_stage(ctx, cost, seed, n_starts):
+def seam_stage(ctx, cost, seed, n_starts, rules=None):
     """Order and direction of the seams (points 2k, 2k+1 = seam k) from the endpoint costs.  Start 0 of the search is today's order
     stage one level up: ACS-TSP on D[s][t] = the cheapest of the four end combinations, every seam left at the end nearer to its
     successor.  Returns (what goes into the JSON, order, directions)."""
@@ -458,7 +458,57 @@ def seam_stage(ctx, cost, seed, n_starts):
     if m <= 16:
         ex = api.seam_tour_exact(ctx, cost, closed=True)
         info["seams"].update(exact=dict(order=ex["order"].tolist(), dir=ex["dir"].tolist(), cost=ex["cost"]))
-    return info, r["order"].tolist(), r["dir"].tolist()
+    if rules is None:
+        return info, r["order"].tolist(), r["dir"].tolist()
+    # job rules (--seam-before / --seam-fixed): what the free tour above breaks, then the tour that keeps them (wa_gtsp_seam_tour_rules,
+    # started from the repaired identity: the ACS-TSP tour knows no rules) and the exact one beside it; the job is stitched from this tour
+    before, after, fixed = rules
+    bad_p, bad_d = api.seam_rules_check(r["order"], r["dir"], before, after, fixed, closed=True, ctx=ctx)
+    rr = api.seam_tour_rules(ctx, cost, before, after, fixed, closed=True, or_len=3, n_starts=n_starts, seed=seed)
+    s = rr["summary"]
+    assert api.seam_rules_check(rr["order"], rr["dir"], before, after, fixed, closed=True, ctx=ctx) == (0, 0)
+    info["seam_rules"] = dict(before=[int(x) for x in before], after=[int(x) for x in after], fixed=[int(x) for x in fixed],
+                              n_prec=s["n_prec"], n_fixed=s["n_fixed"],
+                              unconstrained_breaks=dict(precedences=bad_p, directions=bad_d, cost=r["cost"]),
+                              searched=dict(order=rr["order"].tolist(), dir=rr["dir"].tolist(), cost=rr["cost"], best_start=s["best_start"],
+                                            n_starts=s["n_starts"], passes_total=s["passes_total"], n_capped=s["n_capped"]))
+    if m <= 16:
+        ex = api.seam_tour_rules_exact(ctx, cost, before, after, fixed, closed=True)
+        info["seam_rules"].update(exact=dict(order=ex["order"].tolist(), dir=ex["dir"].tolist(), cost=ex["cost"]))
+    return info, rr["order"].tolist(), rr["dir"].tolist()
+
+
+def parse_seam_rules(ap, args):
+    """--seam-before A:B[,A:B...] and --seam-fixed S:D[,...] as (before, after, fixed bytes), or None when neither is given"""
+    if args.seam_before is None and args.seam_fixed is None:
+        return None
+    if not args.seams:
+        ap.error("--seam-before / --seam-fixed need the seams of --seams")
+    m = args.points // 2
+
+    def pairs(text, what):
+        out = []
+        for item in (text or "").split(","):
+            if not item:
+                continue
+            try:
+                a, b = (int(x) for x in item.split(":"))
+            except ValueError:
+                ap.error("%s takes N:N[,N:N...], not %r" % (what, item))
+            out.append((a, b))
+        return out
+
+    before, after, fixed = [], [], [0] * m
+    for a, b in pairs(args.seam_before, "--seam-before"):
+        if not (0 <= a < m and 0 <= b < m) or a == b or b == 0:
+            ap.error("--seam-before %d:%d: two different seams of 0 .. %d, and nothing goes before seam 0 (the tour starts there)" % (a, b, m - 1))
+        before.append(a)
+        after.append(b)
+    for s, d in pairs(args.seam_fixed, "--seam-fixed"):
+        if not 0 <= s < m or d not in (0, 1):
+            ap.error("--seam-fixed %d:%d: a seam of 0 .. %d and the direction 0 (enter at the even point) or 1" % (s, d, m - 1))
+        fixed[s] = d + 1
+    return before, after, fixed
 
 
 def torch_tool_and_cone(metal, K):
@@ -651,6 +701,11 @@ def main():
                     help="--seams: time the stitched polyline with the weld passes in it (wa_traj_retime_stops): the torch stops T_START seconds "
                          "where it enters a seam, welds at no more than V, stops T_END seconds where it leaves; --retime-limits and "
                          "--retime-tick apply; reported under weld_passes")
+    ap.add_argument("--seam-before", metavar="A:B[,A:B...]",
+                    help="--seams: seam A is welded before seam B (a tack before its seam, a root pass before its fill); the tour then comes "
+                         "from wa_gtsp_seam_tour_rules and the JSON gains seam_rules (what the free tour breaks, both costs)")
+    ap.add_argument("--seam-fixed", metavar="S:D[,S:D...]",
+                    help="--seams: seam S is welded one way only, D = 0 from its even point, D = 1 from its odd point")
     ap.add_argument("--seam-starts", type=int, default=1024, help="--seams: descents of the local search (start 0 is the ACS-TSP tour)")
     ap.add_argument("--torch", type=int, nargs="?", const=64, default=None, metavar="K",
                     help="after --fit or --retime: the torch axis at every sample of the trajectory, one of K directions (1 .. 256) of a cone "
@@ -758,6 +813,7 @@ def main():
         ap.error("--seams needs an even number of --points (two per seam)")
     if args.seams and (args.fit is not None or args.retime):
         ap.error("--seams does not go together with --fit / --retime yet (--weld-passes times a tour of seams)")
+    seam_rules = parse_seam_rules(ap, args)
     if args.weld_passes is not None:
         if not args.seams:
             ap.error("--weld-passes needs the seams of --seams")
@@ -911,7 +967,7 @@ def main():
     if rank == 0 and finite:
         t1 = time.perf_counter()
         if args.seams:
-            info, order, dirs = seam_stage(ctx, cost, args.seed, args.seam_starts)
+            info, order, dirs = seam_stage(ctx, cost, args.seed, args.seam_starts, seam_rules)
             out.update(info, t_seams_s=time.perf_counter() - t1, pair_generations_per_s=out["pairs"] * args.generations / t_pairs)
             # every seam is a two-node segment walked in its chosen direction; between two seams the pair path from where the torch
             # leaves one to where it enters the next (the way back to the first seam is not stitched, as without --seams)

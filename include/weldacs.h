@@ -817,6 +817,46 @@ int wa_gtsp_seam_tour(wa_ctx *ctx, const double *dist, int32_t m, const wa_seam_
                  int32_t *order_out, uint8_t *dir_out, int64_t *start_cost_q_out, int32_t *start_passes_out, wa_seam_summary *sum);
 int wa_gtsp_seam_tour_exact(wa_ctx *ctx, const double *dist, int32_t m, int32_t closed, int32_t *order_out, uint8_t *dir_out, int64_t *cost_q);
 
+/* ---- seam tours under job rules: precedences between seams and one-way seams (DESIGN 4aa holds the full text) ----
+ * Costs, closed, the dummy seam of an open tour, the state and the cost are rules 1 - 3 above.  Two more inputs: before[k] / after[k],
+ * k < n_prec (0 .. 65 536; duplicates allowed): seam before[k] is welded earlier in the tour than seam after[k]; and fixed[s], m bytes
+ * (NULL: all 0): 0 free, 1 the seam is entered at its even endpoint (d = 0), 2 at its odd endpoint (d = 1).
+ *  7. Anchor.  A tour is read from its anchor seam: the dummy when the tour is open, seam 0 when it is closed.  The anchor stands at
+ *     position 0 of every state and never leaves it.  (A caller who wants a home position makes it a degenerate seam 0.)
+ *  8. Admissible state.  The anchor stands at position 0, pos(before[k]) < pos(after[k]) for every pair, every fixed seam has its d.
+ *  9. Moves.  Rule 4's moves with rule 4's numbers, but i >= 1 (the one exception is Reverse(0, 0), which flips the anchor seam alone),
+ *     and a move counts only if the state it produces is admissible.  A pass takes the smallest cost change among the admissible moves,
+ *     the lowest number among equals, and applies it if it is negative; ends and max_passes as in rule 4.
+ * 10. Starts.  Rule 5's draw, then a repair: the anchor goes first; then, step by step, the seam that stands earliest in the drawn order
+ *     among the seams whose `before` seams have all been placed; the drawn d stays unless fixed forces the other.  Start 0 is order0 /
+ *     dir0 as given: they must be admissible and a closed order0[0] must be 0.  A NULL order0 is the repair of the identity, a NULL dir0
+ *     is 0 where a seam is free.
+ * 11. wa_gtsp_seam_tour_rules_exact: rule 6's subset programme with the anchor first, M <= 16.  A subset carries a value only if it is
+ *     closed under `before`, and an entry only where fixed permits it.  Closed: one table per permitted d of seam 0, the d = 0 table
+ *     wins on equal cost; open: one table.  Backtracking takes the lowest endpoint at every step.
+ * 12. wa_gtsp_seam_rules_check (host only: nothing runs on the device, and ctx may be NULL -- like every wa_gtsp_ call it takes the context
+ *     first, here only so that wa_last_error can say what was refused): order / dir hold a tour of m seams as the calls return it; it is read from
+ *     seam 0 when closed, from its first entry when open.  n_bad_prec_out counts the given pairs (a duplicate as often as it is given)
+ *     whose `before` seam does not come first, n_bad_dir_out the fixed seams entered at the wrong end.
+ * WA_ERR_ARG, before anything is written: everything the calls above refuse; n_prec outside 0 .. 65 536 or NULL before / after with
+ * n_prec > 0; a seam index outside 0 .. m-1; before[k] == after[k]; a cycle; after[k] == 0 on a closed tour; a fixed byte above 2;
+ * an order0 / dir0 that is not admissible.  wa_seam_rules_summary is wa_seam_summary, then the number of distinct pairs and of fixed
+ * seams. */
+typedef struct {
+    int32_t m, M, n_starts, best_start, n_capped;
+    int64_t cost_q;
+    int64_t start0_cost_q_in, start0_cost_q_out;
+    int64_t passes_total;
+    int32_t n_prec, n_fixed;                       /* distinct pairs, seams with fixed != 0 */
+} wa_seam_rules_summary;
+int wa_gtsp_seam_tour_rules(wa_ctx *ctx, const double *dist, int32_t m, const wa_seam_params *params, const int32_t *before, const int32_t *after,
+                            int32_t n_prec, const uint8_t *fixed, const int32_t *order0, const uint8_t *dir0, int32_t *order_out, uint8_t *dir_out,
+                            int64_t *start_cost_q_out, int32_t *start_passes_out, wa_seam_rules_summary *sum);
+int wa_gtsp_seam_tour_rules_exact(wa_ctx *ctx, const double *dist, int32_t m, int32_t closed, const int32_t *before, const int32_t *after, int32_t n_prec,
+                                  const uint8_t *fixed, int32_t *order_out, uint8_t *dir_out, int64_t *cost_q);
+int wa_gtsp_seam_rules_check(wa_ctx *ctx, int32_t m, int32_t closed, const int32_t *before, const int32_t *after, int32_t n_prec, const uint8_t *fixed,
+                             const int32_t *order, const uint8_t *dir, int64_t *n_bad_prec_out, int64_t *n_bad_dir_out);
+
 /* ---- torch axis along a trajectory: which way the torch body may point, sample by sample (not in the reference: Usr_SendToSimulation
  *      holds alpha, beta, gamma at constants, main.cpp:393-405) ----
  * t holds n samples, the torch TIP.  The call picks, for every sample, one of K given directions for the torch body so that the body

@@ -64,6 +64,10 @@ class SeamSummary(C.Structure):
                 ("cost_q", C.c_int64), ("start0_cost_q_in", C.c_int64), ("start0_cost_q_out", C.c_int64), ("passes_total", C.c_int64)]
 
 
+class SeamRulesSummary(C.Structure):
+    _fields_ = SeamSummary._fields_ + [("n_prec", C.c_int32), ("n_fixed", C.c_int32)]
+
+
 TORCH_MAX_DIRS, TORCH_MAX_BEADS, TORCH_INF = 256, 64, 1 << 62
 
 
@@ -255,6 +259,9 @@ SYMBOLS = {
     "wa_traj_retime": (C.c_int, [_V, _V, C.POINTER(RetimeLimits), _P, C.c_double, _P, _P, _P, C.POINTER(_V), C.POINTER(RetimeSummary)]),
     "wa_gtsp_seam_tour": (C.c_int, [_V, _P, _I, C.POINTER(SeamParams), _P, _P, _P, _P, _P, _P, C.POINTER(SeamSummary)]),
     "wa_gtsp_seam_tour_exact": (C.c_int, [_V, _P, _I, _I, _P, _P, _P]),
+    "wa_gtsp_seam_tour_rules": (C.c_int, [_V, _P, _I, C.POINTER(SeamParams), _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(SeamRulesSummary)]),
+    "wa_gtsp_seam_tour_rules_exact": (C.c_int, [_V, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
+    "wa_gtsp_seam_rules_check": (C.c_int, [_V, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
     "wa_traj_tool_axes": (C.c_int, [_V, _V, _P, _I, C.POINTER(ToolBeads), C.POINTER(ToolWeights), _P, _P, _I, _P, _P, _P, _P, _P,
                                     C.POINTER(ToolSummary)]),
     "wa_traj_tool_check": (C.c_int, [_V, _V, _P, C.POINTER(ToolBeads), _I, _P, _P, C.POINTER(ToolSummary)]),

@@ -1296,6 +1296,67 @@ def seam_tour_exact(ctx, dist, closed=True):
     return dict(order=order, dir=dirs, cost_q=int(cost.value), cost=cost.value / SEAM_Q)
 
 
+def _seam_rules(m, before, after, fixed):
+    """the rule arrays of the seam-tour calls as the library reads them: (before, after, n_prec, fixed)"""
+    before = np.ascontiguousarray([] if before is None else before, np.int32).reshape(-1)
+    after = np.ascontiguousarray([] if after is None else after, np.int32).reshape(-1)
+    assert before.shape == after.shape, "one `after` seam per `before` seam"
+    fixed = None if fixed is None else np.ascontiguousarray(fixed, np.uint8)
+    assert fixed is None or fixed.shape == (m,), "fixed holds m bytes"
+    return (before if len(before) else None), (after if len(after) else None), len(before), fixed
+
+
+def seam_tour_rules(ctx, dist, before=None, after=None, fixed=None, closed=True, or_len=3, n_starts=64, max_passes=1 << 20, seed=1,
+                    order0=None, dir0=None):
+    """wa_gtsp_seam_tour_rules: seam_tour under job rules.  Seam before[k] is welded earlier than seam after[k]; fixed[s] = 1 / 2 enters
+    seam s at its even / odd endpoint only.  The tour is read from seam 0 when closed (nothing may go before it) and from its first
+    seam when open; a given order0 / dir0 must keep the rules."""
+    dist = np.ascontiguousarray(dist, np.float64)
+    m = dist.shape[0] // 2
+    assert dist.shape == (2 * m, 2 * m), "dist is 2m x 2m"
+    before, after, n_prec, fixed = _seam_rules(m, before, after, fixed)
+    p = L.SeamParams(1 if closed else 0, or_len, n_starts, max_passes, seed)
+    order0 = None if order0 is None else np.ascontiguousarray(order0, np.int32)
+    dir0 = None if dir0 is None else np.ascontiguousarray(dir0, np.uint8)
+    assert (order0 is None or order0.shape == (m,)) and (dir0 is None or dir0.shape == (m,)), "order0 / dir0 hold m entries"
+    order, dirs = np.zeros(m, np.int32), np.zeros(m, np.uint8)
+    n = max(int(n_starts), 0)
+    costs, passes = np.zeros(n, np.int64), np.zeros(n, np.int32)
+    s = L.SeamRulesSummary()
+    ctx.check(ctx.lib.wa_gtsp_seam_tour_rules(ctx.h, _ptr(dist), m, C.byref(p), _ptr(before), _ptr(after), n_prec, _ptr(fixed), _ptr(order0),
+                                              _ptr(dir0), _ptr(order), _ptr(dirs), _ptr(costs), _ptr(passes), C.byref(s)))
+    summary = {k: int(getattr(s, k)) for k, _ in L.SeamRulesSummary._fields_}
+    return dict(order=order, dir=dirs, cost_q=summary["cost_q"], cost=summary["cost_q"] / SEAM_Q, start_cost_q=costs, start_passes=passes,
+                summary=summary)
+
+
+def seam_tour_rules_exact(ctx, dist, before=None, after=None, fixed=None, closed=True):
+    """wa_gtsp_seam_tour_rules_exact: the optimal admissible order and directions, up to 16 seams (15 when open)"""
+    dist = np.ascontiguousarray(dist, np.float64)
+    m = dist.shape[0] // 2
+    assert dist.shape == (2 * m, 2 * m), "dist is 2m x 2m"
+    before, after, n_prec, fixed = _seam_rules(m, before, after, fixed)
+    order, dirs, cost = np.zeros(m, np.int32), np.zeros(m, np.uint8), C.c_int64(0)
+    ctx.check(ctx.lib.wa_gtsp_seam_tour_rules_exact(ctx.h, _ptr(dist), m, 1 if closed else 0, _ptr(before), _ptr(after), n_prec, _ptr(fixed),
+                                                    _ptr(order), _ptr(dirs), C.byref(cost)))
+    return dict(order=order, dir=dirs, cost_q=int(cost.value), cost=cost.value / SEAM_Q)
+
+
+def seam_rules_check(order, dirs, before=None, after=None, fixed=None, closed=True, ctx=None):
+    """wa_gtsp_seam_rules_check (host only, a context is optional): (given pairs out of order, one-way seams entered at the wrong end) of a
+    tour"""
+    order, dirs = np.ascontiguousarray(order, np.int32), np.ascontiguousarray(dirs, np.uint8)
+    m = len(order)
+    assert order.shape == (m,) and dirs.shape == (m,), "order / dir hold m entries"
+    before, after, n_prec, fixed = _seam_rules(m, before, after, fixed)
+    bad_p, bad_d = C.c_int64(0), C.c_int64(0)
+    rc = (ctx.lib if ctx is not None else L.load()).wa_gtsp_seam_rules_check(ctx.h if ctx is not None else None, m, 1 if closed else 0, _ptr(before), _ptr(after), n_prec, _ptr(fixed), _ptr(order), _ptr(dirs),
+                                                    C.byref(bad_p), C.byref(bad_d))
+    if rc:
+        raise ValueError("wa_gtsp_seam_rules_check: the rules or the tour are not well-formed (status %d)" % rc)
+    return int(bad_p.value), int(bad_d.value)
+
+
 TORCH_INF = L.TORCH_INF   # leg cost of a one-sample leg whose two pins differ (wa_traj_tool_axes, rule 5)
 
 

@@ -37,6 +37,7 @@
 #include "fit_kernels.hpp"
 #include "retime_kernels.hpp"
 #include "seamtour_kernels.hpp"
+#include "seamrules_kernels.hpp"
 #include "torch_kernels.hpp"
 #include "reach_kernels.hpp"
 #include "pose_kernels.hpp"
@@ -853,6 +854,7 @@ void *wa_ctx_stream(wa_ctx *c) { return c ? (void *)c->stream : nullptr; }
 #include "host_fit.inc"
 #include "host_retime.inc"
 #include "host_seamtour.inc"
+#include "host_seamrules.inc"
 #include "host_torch.inc"
 #include "host_reach.inc"
 #include "host_pose.inc"
