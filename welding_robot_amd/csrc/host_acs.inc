@@ -186,6 +186,7 @@ static int acs_create_once(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, in
     s->conv_wait_us = env_int("WA_CONVERGED_WAIT_US", 200000);
     s->conv_spec = env_int("WA_CONVERGED_SPECULATE", 1) != 0;
     s->conv_owed = env_int("WA_CONVERGED_OWED", 1) != 0;
+    s->prof_dispatch = env_int("WA_PROF_DISPATCH", 1) != 0;
     s->conv_enqueued.assign((size_t)n_slots, 0);
     {   // sweep grid: measured on MI355X -- 100 MB fields (128^3 x 6) peak at 4096 blocks (6.0 TB/s; 2048: 5.5, 8192: 5.8),
         // 436 MB fields (128^3 x 26) want 2-3 float4 per thread (49152 blocks: 6.1 TB/s; 32768: 5.9; 4096: 4.6)
@@ -374,6 +375,7 @@ void wa_acs_destroy(wa_acs *s)
     if (s->d_hashlog) hipFree(s->d_hashlog);
 #endif
     for (auto &p : s->ev) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
+    for (auto &p : s->ev_pool) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto st : s->gstream) { hipStreamSynchronize(st); hipStreamDestroy(st); }
     for (auto ev : s->gjoin) hipEventDestroy(ev);
     if (s->gfork) hipEventDestroy(s->gfork);
@@ -590,13 +592,25 @@ int wa_acs_begin(wa_acs *s, const wa_acs_params *p, int32_t n_problems, const in
     return WA_OK;
 }
 
+// A pair of events for one stamp: from the solver's pool (pairs wa_acs_sync has harvested), created only when the pool is empty -- a stamped
+// generation of a loop that is read now and then makes no runtime call but its launches.  false: no pair to be had, the launch goes out unstamped
+static bool prof_take(wa_acs *s, EvPair &p, int cls)
+{
+    if (!s->ev_pool.empty()) {
+        p = s->ev_pool.back();
+        s->ev_pool.pop_back();
+    } else {
+        if (hipEventCreate(&p.a) != hipSuccess) return false;
+        if (hipEventCreate(&p.b) != hipSuccess) { hipEventDestroy(p.a); return false; }
+    }
+    p.cls = cls;
+    return true;
+}
 static EvPair *prof_open(wa_acs *s, hipStream_t st, int cls, bool sampled)
 {
     if (!sampled) return nullptr;
     EvPair p;
-    p.cls = cls;
-    if (hipEventCreate(&p.a) != hipSuccess) return nullptr;
-    if (hipEventCreate(&p.b) != hipSuccess) { hipEventDestroy(p.a); return nullptr; }
+    if (!prof_take(s, p, cls)) return nullptr;
     hipEventRecord(p.a, st);
     s->ev.push_back(p);
     return &s->ev.back();
@@ -638,14 +652,10 @@ static void launch_evaporate(wa_acs *s, hipStream_t st, const float *src, float 
     float *dp = dst + (int64_t)slot0 * s->D.pher_stride;
     if (timed) {
         EvPair p;
-        p.cls = WA_K_EVAPORATE;
-        if (hipEventCreate(&p.a) == hipSuccess) {
-            if (hipEventCreate(&p.b) == hipSuccess) {
-                hipExtLaunchKernelGGL(k_evaporate, grid, dim3(256), 0, st, p.a, p.b, 0, sp, dp, s->D.pher_stride, (int64_t)s->nb * s->D.d.n, rho, nt);
-                s->ev.push_back(p);
-                return;
-            }
-            hipEventDestroy(p.a);
+        if (prof_take(s, p, WA_K_EVAPORATE)) {
+            hipExtLaunchKernelGGL(k_evaporate, grid, dim3(256), 0, st, p.a, p.b, 0, sp, dp, s->D.pher_stride, (int64_t)s->nb * s->D.d.n, rho, nt);
+            s->ev.push_back(p);
+            return;
         }
     }
     k_evaporate<<<grid, 256, 0, st>>>(sp, dp, s->D.pher_stride, (int64_t)s->nb * s->D.d.n, rho, nt);
@@ -719,9 +729,7 @@ static void prof_pair_marker(wa_acs *s, hipStream_t st)
 {
     if (!s->prof_paired) return;
     EvPair p;
-    p.cls = -1;   // (not a launch class: acs_collect_events drops it)
-    if (hipEventCreate(&p.a) != hipSuccess) return;
-    if (hipEventCreate(&p.b) != hipSuccess) { hipEventDestroy(p.a); return; }
+    if (!prof_take(s, p, -1)) return;   // (-1 is not a launch class: wa_acs_sync drops the pair's time)
     hipExtLaunchKernelGGL(k_prof_noop, dim3(1), dim3(64), 0, st, p.a, p.b, 0, (int32_t *)nullptr);
     s->ev.push_back(p);
 }
@@ -745,15 +753,11 @@ static void launch_fused(wa_acs *s, WaGroupRun &G, const float *src, float *dst,
         dim3 lgrid((unsigned)(E + MB), (unsigned)P);
         if (timed) {
             EvPair p;
-            p.cls = WA_K_EVAPORATE;
-            if (hipEventCreate(&p.a) == hipSuccess) {
-                if (hipEventCreate(&p.b) == hipSuccess) {
-                    if (s->nb == 26) hipExtLaunchKernelGGL((k_evap_rank_mark<true, 26>), lgrid, dim3(256), rank_lds, G.st, p.a, p.b, 0, G.V, s->R, src, dst, E, gen, MB, SL, LP, 0, RC);
-                    else hipExtLaunchKernelGGL((k_evap_rank_mark<true, 6>), lgrid, dim3(256), rank_lds, G.st, p.a, p.b, 0, G.V, s->R, src, dst, E, gen, MB, SL, LP, 0, RC);
-                    s->ev.push_back(p);
-                    return;
-                }
-                hipEventDestroy(p.a);
+            if (prof_take(s, p, WA_K_EVAPORATE)) {
+                if (s->nb == 26) hipExtLaunchKernelGGL((k_evap_rank_mark<true, 26>), lgrid, dim3(256), rank_lds, G.st, p.a, p.b, 0, G.V, s->R, src, dst, E, gen, MB, SL, LP, 0, RC);
+                else hipExtLaunchKernelGGL((k_evap_rank_mark<true, 6>), lgrid, dim3(256), rank_lds, G.st, p.a, p.b, 0, G.V, s->R, src, dst, E, gen, MB, SL, LP, 0, RC);
+                s->ev.push_back(p);
+                return;
             }
         }
 #ifdef WA_TEST_KNOBS
@@ -767,12 +771,7 @@ static void launch_fused(wa_acs *s, WaGroupRun &G, const float *src, float *dst,
     }
     dim3 grid((unsigned)(s->evap_blocks + MB), (unsigned)P);
     EvPair p;
-    p.cls = WA_K_EVAPORATE;
-    bool ev = false;
-    if (timed && hipEventCreate(&p.a) == hipSuccess) {
-        if (hipEventCreate(&p.b) == hipSuccess) ev = true;
-        else hipEventDestroy(p.a);
-    }
+    const bool ev = timed && prof_take(s, p, WA_K_EVAPORATE);
     if (ev) {   // per-dispatch start/stop events: they stamp the kernel itself, not the stream gaps
         if (s->nb == 26) hipExtLaunchKernelGGL((k_evap_rank_mark<false, 26>), grid, dim3(256), rank_lds, G.st, p.a, p.b, 0, G.V, s->R, src, dst, s->evap_blocks, gen, MB, SL, LP, G.sweep_nt, RC);
         else hipExtLaunchKernelGGL((k_evap_rank_mark<false, 6>), grid, dim3(256), rank_lds, G.st, p.a, p.b, 0, G.V, s->R, src, dst, s->evap_blocks, gen, MB, SL, LP, G.sweep_nt, RC);
@@ -809,7 +808,13 @@ static void enqueue_generation(wa_acs *s, WaGroupRun &G, int32_t gen, bool last_
         G.V.paths = s->paths_arr[gen & 1] + poff;
         G.V.prev_paths = s->paths_arr[(gen + 1) & 1] + poff;
     }
-    EvPair *e = prof_open(s, st, WA_K_WALK, sampled);
+    // Stamps of the fused DEV path: the walk launch and apply + table are one dispatch each and carry their start/stop events themselves, as the
+    // sweep-carrying launch always has (launch_fused): no hipEventRecord in the loop, and the times are the kernels', not kernel plus stream gap.
+    // Classes of several launches (the REF-mode walk, the plain path) keep the recorded pairs, and so does WA_PROF_DISPATCH=0
+    const bool disp = sampled && s->prof_dispatch && fused && s->R.rng_mode == WA_RNG_DEV && s->colony_bound > 0;
+    EvPair wp;
+    const bool wev = disp && prof_take(s, wp, WA_K_WALK);
+    EvPair *e = prof_open(s, st, WA_K_WALK, sampled && !disp);
     // stragglers (DESIGN 4e): WA_RESUME_MAX resume blocks per search behind the ants' blocks, only where the apply + table launch follows
     // (it resets the arrival list and the pool) and only while a search explores (its first WA_STRAGGLER_GENS generations: once
     // converged every ant replays the best path, nothing is handed over, and empty resume blocks at the tail of every walk
@@ -825,7 +830,11 @@ static void enqueue_generation(wa_acs *s, WaGroupRun &G, int32_t gen, bool last_
             if (s->colony_bound > 0)
             {
                 dim3 wg26((unsigned)(strag ? s->D.max_colony + WA_RESUME_MAX : s->colony_bound), (unsigned)P);
-                if (s->lazy) k_walk_dev26<true><<<wg26, 64, shmem, st>>>(G.V, s->R, s->hash_log2, gen, 0);
+                if (wev) {
+                    if (s->lazy) hipExtLaunchKernelGGL(k_walk_dev26<true>, wg26, dim3(64), shmem, st, wp.a, wp.b, 0, G.V, s->R, s->hash_log2, gen, 0);
+                    else hipExtLaunchKernelGGL(k_walk_dev26<false>, wg26, dim3(64), shmem, st, wp.a, wp.b, 0, G.V, s->R, s->hash_log2, gen, hand_over ? 32 : 0);
+                }
+                else if (s->lazy) k_walk_dev26<true><<<wg26, 64, shmem, st>>>(G.V, s->R, s->hash_log2, gen, 0);
                 else k_walk_dev26<false><<<wg26, 64, shmem, st>>>(G.V, s->R, s->hash_log2, gen, hand_over ? 32 : 0);
             }
         } else {
@@ -851,8 +860,10 @@ static void enqueue_generation(wa_acs *s, WaGroupRun &G, int32_t gen, bool last_
                 t16 = s->tab16_env == 1 || (s->tab16_env < 0 && s->id_bits <= 21 && (int64_t)wg.x * P_all > per_cu * ctx->prop.multiProcessorCount);
             }
             const size_t shmem16 = ((size_t)2 << s->hash_log2) + WA_WALK_LDS_EXTRA + (size_t)s->lds_pad;
-#define WA_LAUNCH_WALK16(SP, RJ) k_walk_dev<true, SP, false, RJ, false, true><<<wg, 64, shmem16, st>>>(G.V, s->R, s->hash_log2, gen, walk_flags)
-#define WA_LAUNCH_WALK(A1, SP, WM, RJ, DR) k_walk_dev<A1, SP, WM, RJ, DR><<<wg, 64, shmem, st>>>(G.V, s->R, s->hash_log2, gen, walk_flags)
+#define WA_LAUNCH_WALK16(SP, RJ) do { if (wev) hipExtLaunchKernelGGL((k_walk_dev<true, SP, false, RJ, false, true>), wg, dim3(64), shmem16, st, wp.a, wp.b, 0, G.V, s->R, s->hash_log2, gen, walk_flags); \
+        else k_walk_dev<true, SP, false, RJ, false, true><<<wg, 64, shmem16, st>>>(G.V, s->R, s->hash_log2, gen, walk_flags); } while (0)
+#define WA_LAUNCH_WALK(A1, SP, WM, RJ, DR) do { if (wev) hipExtLaunchKernelGGL((k_walk_dev<A1, SP, WM, RJ, DR>), wg, dim3(64), shmem, st, wp.a, wp.b, 0, G.V, s->R, s->hash_log2, gen, walk_flags); \
+        else k_walk_dev<A1, SP, WM, RJ, DR><<<wg, 64, shmem, st>>>(G.V, s->R, s->hash_log2, gen, walk_flags); } while (0)
             s->last_walk[0] = s->hash_log2; s->last_walk[1] = t16 ? 1 : 0; s->last_walk[2] = (int32_t)(t16 ? shmem16 : shmem); s->last_walk[3] = warm ? 1 : 0;
             if (t16) {
                 if (s->lazy) { if (rej) WA_LAUNCH_WALK16(true, true); else WA_LAUNCH_WALK16(true, false); }
@@ -884,6 +895,7 @@ static void enqueue_generation(wa_acs *s, WaGroupRun &G, int32_t gen, bool last_
         k_walk_ref<<<dim3(1, 1), 64, shmem, st>>>(G.V, s->R, s->hash_log2, gen, (s->walk_flags & 1) | (spec ? 2 : 0));
     }
     prof_close(st, e);
+    if (wev) s->ev.push_back(wp);
 #ifdef WA_STATE_HASH
 #define WA_HASH_GENS 256
 #define WA_HASH_AT(phase) do { if (s->d_hashlog && gen < WA_HASH_GENS) k_state_hash<<<dim3(96, (unsigned)P), 256, 0, st>>>(G.V, s->R, s->d_hashlog + (((int64_t)gen * 3 + (phase)) * s->n_slots + G.slot0) * 8, (phase)); } while (0)
@@ -900,8 +912,16 @@ static void enqueue_generation(wa_acs *s, WaGroupRun &G, int32_t gen, bool last_
         if (!s->lazy) G.cur ^= 1;
         G.V.pher = dst;
         WA_HASH_AT(1);
-        e = prof_open(s, st, WA_K_DEPOSIT, sampled);
-        if (s->nb == 26) k_apply_table26<<<dim3((unsigned)(1 + WA_TABLE26_BLOCKS + mark_blocks(s)), (unsigned)P), 256, 0, st>>>(G.V, s->R);
+        EvPair dp;
+        const bool dev = disp && prof_take(s, dp, WA_K_DEPOSIT);
+        e = prof_open(s, st, WA_K_DEPOSIT, sampled && !disp);
+        if (dev) {   // (the launches below with their events in the dispatch; the shape of k_apply_table's grid is stated there)
+            const int32_t SLd = G.P >= 32 ? 1 : 2, TBd = G.P >= 32 ? 32 : WA_TABLE_BLOCKS_MAX;
+            if (s->nb == 26) hipExtLaunchKernelGGL(k_apply_table26, dim3((unsigned)(1 + WA_TABLE26_BLOCKS + mark_blocks(s)), (unsigned)P), dim3(256), 0, st, dp.a, dp.b, 0, G.V, s->R);
+            else hipExtLaunchKernelGGL(k_apply_table, dim3((unsigned)(TBd + ((mark_blocks(s) >> 3) << SLd)), (unsigned)P), dim3(256), 0, st, dp.a, dp.b, 0, G.V, s->R, SLd, TBd, owed ? gen | WA_GEN_OWED : gen);
+            s->ev.push_back(dp);
+        }
+        else if (s->nb == 26) k_apply_table26<<<dim3((unsigned)(1 + WA_TABLE26_BLOCKS + mark_blocks(s)), (unsigned)P), 256, 0, st>>>(G.V, s->R);
         else { const int32_t SL = P >= 32 ? 1 : 2, TB = P >= 32 ? 32 : WA_TABLE_BLOCKS_MAX; k_apply_table<<<dim3((unsigned)(TB + ((mark_blocks(s) >> 3) << SL)), (unsigned)P), 256, 0, st>>>(G.V, s->R, SL, TB, owed ? gen | WA_GEN_OWED : gen); }
         prof_close(st, e);
         WA_DBG_SYNC("apply+table");
@@ -1345,8 +1365,7 @@ int wa_acs_sync(wa_acs *s)
     for (auto &p : s->ev) {
         float ms = 0;
         if (p.cls >= 0 && hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) { s->prof_ms[p.cls] += ms; s->prof_n[p.cls]++; }   // (cls -1: the marker of a paired stamp)
-        hipEventDestroy(p.a);
-        hipEventDestroy(p.b);
+        s->ev_pool.push_back(p);   // harvested, and the stream is idle: the pair stamps again
     }
     s->ev.clear();
     if (s->begun && s->n_active > 0) {

@@ -169,6 +169,8 @@ struct wa_acs {
     bool prof_paired = false;    // a stamped no-op dispatch in front of every timed sweep-carrying launch (prof_pair_marker)
     int32_t prof_every = 1;
     std::vector<EvPair> ev;
+    std::vector<EvPair> ev_pool;         // event pairs whose times have been harvested (wa_acs_sync), ready for the next stamp: the loop creates none while the pool lasts
+    bool prof_dispatch = true;           // WA_PROF_DISPATCH: the walk and apply + table launches of the fused DEV path carry their start/stop events themselves
     double prof_ms[WA_K_COUNT] = {};
     int64_t prof_n[WA_K_COUNT] = {};
     // pipelined groups (wa_acs_run): the active slots split into groups, each with a stream of its own, so that one group's HBM-bound
