@@ -68,6 +68,12 @@ int wa_ctx_trim(wa_ctx *ctx);
  * handled by releasing kept memory, [6] milliseconds spent building arena blocks, [7] 1 when the arena is in use, 2 when it is but its
  * address window is used up (blocks kept so far go on serving, new shapes come as whole allocations) */
 int wa_ctx_cache_stats(wa_ctx *ctx, int64_t out[8]);
+/* Debug read-out of WA_DEV_POISON=1 (read at wa_ctx_create): every device block the library allocates for a call on such a context is
+ * filled with WA_DEV_POISON_BYTE (0 .. 255, default 255) before it is used, so that a kernel which reads a word nobody wrote reads that
+ * pattern and not the zeros of fresh device memory.  [0] blocks and [1] bytes filled through the context's allocator (the solvers'
+ * memory), [2] blocks and [3] bytes filled through the plain one (grids, trajectories, every planning call's scratch).  All 0 without
+ * the knob. */
+int wa_ctx_poison_stats(wa_ctx *ctx, int64_t out[4]);
 /* Every call on a context (and on anything created from it) runs on that context's device regardless of the calling
  * thread's current HIP device, and restores the caller's current device before returning. */
 int wa_ctx_create(int device_ordinal, wa_ctx **out);

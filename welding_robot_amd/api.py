@@ -92,6 +92,12 @@ class Context:
         d["kept_bytes"] = self.cached_bytes()
         return d
 
+    def poison_stats(self):
+        """wa_ctx_poison_stats as a dict: blocks / bytes that WA_DEV_POISON=1 filled, per allocator (all 0 without the knob)"""
+        v = (C.c_int64 * 4)()
+        self.check(self.lib.wa_ctx_poison_stats(self.h, v))
+        return {k: int(x) for k, x in zip(("ctx_blocks", "ctx_bytes", "plain_blocks", "plain_bytes"), v)}
+
     def sync(self):
         self.check(self.lib.wa_ctx_sync(self.h))
 

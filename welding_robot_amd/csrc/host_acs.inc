@@ -1211,7 +1211,7 @@ int wa_acs_run(wa_acs *s, int32_t n_generations)
 #ifdef WA_STATE_HASH
     if (n_generations > 0 && s->gens_enqueued == 0) {
         const size_t bytes = sizeof(unsigned long long) * 256 * 3 * (size_t)s->n_slots * 8;
-        if (!s->d_hashlog) HIPC(ctx, hipMalloc((void **)&s->d_hashlog, bytes));
+        if (!s->d_hashlog) HIPC(ctx, dev_malloc((void **)&s->d_hashlog, bytes));
         HIPC(ctx, hipMemsetAsync(s->d_hashlog, 0, bytes, ctx->stream));
     }
 #endif

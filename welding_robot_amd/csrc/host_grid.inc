@@ -72,7 +72,7 @@ static int grid_count_free(wa_grid *g)
 {
     wa_ctx *ctx = g->ctx;
     unsigned long long *d_cnt = nullptr, h = 0;
-    hipError_t e = hipMalloc((void **)&d_cnt, 8);
+    hipError_t e = dalloc(&d_cnt, 1);
     e = e ? e : hipMemsetAsync(d_cnt, 0, 8, ctx->stream);
     if (e == hipSuccess) {
         k_count_free<<<1024, 256, 0, ctx->stream>>>(g->occ, g->d.n, d_cnt);

@@ -15,6 +15,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <functional>
 #include <memory>
@@ -67,6 +68,8 @@ struct wa_ctx {
     std::unordered_map<void *, size_t> live;   // blocks handed out by ctx_alloc from hipMalloc and not yet returned
     size_t cache_bytes = 0;                    // kept bytes: cached whole blocks + pooled chunks
     bool cache_on = true, poison = false;      // WA_DEV_CACHE=0 / WA_DEV_POISON=1, read at wa_ctx_create
+    int poison_byte = 0xff;                    // WA_DEV_POISON_BYTE (0 .. 255), read at wa_ctx_create: what a poisoned block is filled with
+    mutable std::atomic<int64_t> poison_stat[4] = {};   // wa_ctx_poison_stats: blocks / bytes filled by ctx_alloc, blocks / bytes filled by dev_malloc
     // the arena (round 5): physical chunks of two sizes, created once and mapped into whatever virtual range the next block needs
     bool arena_on = false;                     // the device supports virtual memory management and WA_DEV_ARENA != 0
     bool arena_strict = false;       // kept blocks are only reused for requests of exactly their size (the retry of a solver that did not fit)
@@ -231,19 +234,31 @@ static int fail(wa_ctx *c, int code, const char *fmt, const char *a = "", const 
 
 // Every entry point runs on the device of its context, whatever device the calling thread had current (another
 // context on another GPU, torch.cuda.set_device ...), and leaves the caller's current device as it found it.
+// ... and names the context to dev_malloc for as long as the call runs when it was created with WA_DEV_POISON=1 (null otherwise, also
+// for a call on a context without the knob made from inside a poisoned call): every plain device block the calling thread allocates
+// meanwhile is filled with that context's poison byte (poison_fill below).  One thread-local pointer saved, set and put back per call.
+static thread_local const wa_ctx *g_poison_ctx = nullptr;
 struct WaDevGuard {
     int prev = -1;
-    bool switched = false, ok = true;
+    bool switched = false, ok = true, named = false;
+    const wa_ctx *prev_poison = nullptr;
     explicit WaDevGuard(const wa_ctx *c)
     {
         if (!c) return;
+        prev_poison = g_poison_ctx;   // (entry points call each other: restored on the way out)
+        g_poison_ctx = c->poison ? c : nullptr;
+        named = true;
         if (hipGetDevice(&prev) != hipSuccess) prev = -1;
         if (prev != c->device) {
             ok = hipSetDevice(c->device) == hipSuccess;
             switched = ok && prev >= 0;
         }
     }
-    ~WaDevGuard() { if (switched) hipSetDevice(prev); }
+    ~WaDevGuard()
+    {
+        if (named) g_poison_ctx = prev_poison;
+        if (switched) hipSetDevice(prev);
+    }
     WaDevGuard(const WaDevGuard &) = delete;
     WaDevGuard &operator=(const WaDevGuard &) = delete;
 };
@@ -289,7 +304,9 @@ static int env_int(const char *name, int def)
 // as is needed, not all.  Blocks below WA_ARENA_MIN (and every block where the arena is off: WA_DEV_ARENA=0 or no VMM support) keep
 // round 4's exact-fit cache of whole hipMalloc blocks, now bounded: least recently used blocks are released beyond
 // WA_DEV_SMALL_CACHE_MB (2 048; without the arena WA_DEV_KEEP_PCT).  Nothing is assumed about a block's contents, fresh or reused
-// (WA_DEV_POISON=1 fills every block with 0xff bytes before it is handed out: the GPU suite passes that way).  Kept bytes count as free
+// (WA_DEV_POISON=1 fills every block with WA_DEV_POISON_BYTE -- 0xff unless set -- before it is handed out, the plain blocks of
+// dev_malloc / dalloc / DevBuf included: tests/test_gpu_cache.py and test_gpu_arena.py run the solver that way, tests/test_gpu_poisoned_scratch.py
+// the planning calls, under 0xff and 0x55; wa_ctx_poison_stats counts what was filled).  Kept bytes count as free
 // in wa_ctx_memory_info; wa_ctx_trim releases them, WA_DEV_CACHE=0 switches everything off.  wa_ctx_cache_stats reports what was served
 // from kept memory and what had to be created.
 static std::mutex g_cache_mu;
@@ -409,35 +426,56 @@ static size_t cache_release_device(int device, size_t need = 0)
 // plain hipMalloc for everything that does not go through a context's cache (grids, traces, staging, the communicator's scratch): when
 // the device is out of memory the kept memory of the contexts on it is released -- as much as is needed -- and the call retried while
 // the driver's wipe proceeds, for a few seconds at most
-static hipError_t dev_malloc(void **out, size_t bytes)
+//
+// WA_DEV_POISON=1: a block allocated inside a call on such a context (g_poison_ctx, set by the call's WaDevGuard) is filled with the
+// context's poison byte before it is handed out.  The fill is enqueued on the context's stream, in front of the call's own work there --
+// and then WAITED FOR: some blocks are first used on another stream (the communicator's, the solver's group streams), which the
+// context's stream does not order.  Poison mode is a test mode; the wait keeps the rule simple.  Without the knob g_poison_ctx is null:
+// nothing is enqueued, locked or waited for.  fill = false: the caller (ctx_alloc_bytes) fills and counts the block itself.
+// tests/test_alloc_rules.py: the runtime's device allocators are called between the two marker lines below and nowhere else in csrc.
+// ---- device allocation: begin
+static hipError_t poison_fill(const wa_ctx *c, void *p, size_t bytes, bool plain)
+{
+    hipError_t e = hipMemsetAsync(p, c->poison_byte, bytes, c->stream);
+    if (e != hipSuccess) return e;   // (nothing was filled: nothing is counted)
+    c->poison_stat[plain ? 2 : 0] += 1;
+    c->poison_stat[plain ? 3 : 1] += (int64_t)bytes;
+    return plain ? hipStreamSynchronize(c->stream) : hipSuccess;
+}
+static hipError_t dev_malloc(void **out, size_t bytes, bool fill = true)
 {
     if (bytes < 16) bytes = 16;
     hipError_t e = hipMalloc(out, bytes);
-    if (e != hipErrorOutOfMemory) return e;
-    (void)hipGetLastError();
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return e;
-    // rounds: what is needed (+ slack), twice that, four times, everything.  After each release the call is retried while the driver
-    // wipes what it got back (memory in that state is neither free nor allocatable: hipMalloc fails rather than waits), 2 s at most
-    // per round; a device with nothing kept on it gives up after 0.3 s
-    size_t need = bytes + ((size_t)64 << 20);
-    for (int round = 0; round < 4; round++) {
-        const size_t freed = cache_release_device(dev, round < 3 ? need : 0);
-        const auto t0 = std::chrono::steady_clock::now();
-        const double limit = freed ? 2.0 : 0.3;
-        for (;;) {
-            e = hipMalloc(out, bytes);
-            if (e != hipErrorOutOfMemory) break;
-            (void)hipGetLastError();
-            if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > limit) break;
-            std::this_thread::sleep_for(std::chrono::milliseconds(10));
+    if (e == hipErrorOutOfMemory && ((void)hipGetLastError(), hipGetDevice(&dev)) == hipSuccess) {
+        // rounds: what is needed (+ slack), twice that, four times, everything.  After each release the call is retried while the driver
+        // wipes what it got back (memory in that state is neither free nor allocatable: hipMalloc fails rather than waits), 2 s at most
+        // per round; a device with nothing kept on it gives up after 0.3 s
+        size_t need = bytes + ((size_t)64 << 20);
+        for (int round = 0; round < 4; round++) {
+            const size_t freed = cache_release_device(dev, round < 3 ? need : 0);
+            const auto t0 = std::chrono::steady_clock::now();
+            const double limit = freed ? 2.0 : 0.3;
+            for (;;) {
+                e = hipMalloc(out, bytes);
+                if (e != hipErrorOutOfMemory) break;
+                (void)hipGetLastError();
+                if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > limit) break;
+                std::this_thread::sleep_for(std::chrono::milliseconds(10));
+            }
+            if (e != hipErrorOutOfMemory || freed == 0) break;
+            need *= 2;
         }
-        if (e != hipErrorOutOfMemory || freed == 0) break;
-        need *= 2;
+        if (e != hipSuccess) *out = nullptr;
     }
-    if (e != hipSuccess) *out = nullptr;
+    if (e == hipSuccess && fill)
+        if (const wa_ctx *pc = g_poison_ctx) {
+            e = poison_fill(pc, *out, bytes, true);
+            if (e != hipSuccess) { hipFree(*out); *out = nullptr; }
+        }
     return e;
 }
+// ---- device allocation: end (hipMalloc)
 template <class T>
 static hipError_t dalloc(T **p, size_t count)
 {
@@ -468,6 +506,7 @@ using OwnedHandle = std::unique_ptr<H, WaHandleDel>;
 
 // one chunk of class k for a block under construction: from the pool; else from a kept block that nobody asked for (harvested, least
 // recently used first); else created -- pooled chunks of the other classes and cached whole blocks make room when the device is full
+// ---- device allocation: begin
 static hipError_t arena_chunk(wa_ctx *c, int k, hipMemGenericAllocationHandle_t *h, bool *kept)
 {
     const size_t sz = WA_ARENA_SZ[k];
@@ -512,6 +551,7 @@ static hipError_t arena_chunk(wa_ctx *c, int k, hipMemGenericAllocationHandle_t 
     }
     return e;
 }
+// ---- device allocation: end (hipMemCreate)
 static void arena_return_chunks(wa_ctx *c, WaArenaBlock &b)
 {
     for (int k = 0; k < 3; k++) {
@@ -633,7 +673,7 @@ static hipError_t ctx_alloc_bytes(wa_ctx *c, void **out, size_t bytes)
             const hipError_t e = arena_alloc_locked(c, out, bytes);
             c->stat[WA_ST_WAIT_MS] += (int64_t)(1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
             if (e == hipSuccess) {
-                if (c->poison) return hipMemsetAsync(*out, 0xff, bytes, c->stream);
+                if (c->poison) return poison_fill(c, *out, bytes, false);
                 return hipSuccess;
             }
             *out = nullptr;   // (no chunk, or no fresh address range left: a whole hipMalloc block below, if the device has one)
@@ -653,7 +693,7 @@ static hipError_t ctx_alloc_bytes(wa_ctx *c, void **out, size_t bytes)
         }
     }
     if (!*out) {
-        const hipError_t e = dev_malloc(out, bytes);   // (releases kept memory and retries when the device is full)
+        const hipError_t e = dev_malloc(out, bytes, false);   // (releases kept memory and retries when the device is full; filled below)
         if (e != hipSuccess) { *out = nullptr; return e; }
         if (big) {
             std::lock_guard<std::mutex> lk(g_cache_mu);
@@ -661,7 +701,7 @@ static hipError_t ctx_alloc_bytes(wa_ctx *c, void **out, size_t bytes)
             c->stat[WA_ST_MISS_BYTES] += (int64_t)bytes;
         }
     }
-    if (c->poison) return hipMemsetAsync(*out, 0xff, bytes, c->stream);
+    if (c->poison) return poison_fill(c, *out, bytes, false);
     return hipSuccess;
 }
 template <class T>
@@ -746,6 +786,7 @@ int wa_ctx_create(int device_ordinal, wa_ctx **out)
     }
     c->cache_on = env_int("WA_DEV_CACHE", 1) != 0;
     c->poison = env_int("WA_DEV_POISON", 0) != 0;
+    c->poison_byte = env_int("WA_DEV_POISON_BYTE", 255) & 255;
     {   // the arena needs virtual memory management; how much the context may keep is a share of the device's memory
         int vmm = 0;
         if (hipDeviceGetAttribute(&vmm, hipDeviceAttributeVirtualMemoryManagementSupported, device_ordinal) != hipSuccess) { vmm = 0; (void)hipGetLastError(); }
@@ -802,6 +843,12 @@ int wa_ctx_cache_stats(wa_ctx *c, int64_t out[8])
     std::lock_guard<std::mutex> lk(g_cache_mu);
     for (int i = 0; i < 7; i++) out[i] = c->stat[i];
     out[7] = c->arena_on ? (g_va_exhausted ? 2 : 1) : 0;   // 2: in use, but its address window is used up -- new shapes come as whole blocks
+    return WA_OK;
+}
+int wa_ctx_poison_stats(wa_ctx *c, int64_t out[4])
+{
+    if (!c || !out) return WA_ERR_ARG;
+    for (int i = 0; i < 4; i++) out[i] = c->poison_stat[i].load();
     return WA_OK;
 }
 int wa_ctx_trim(wa_ctx *c)
