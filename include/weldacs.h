@@ -74,6 +74,20 @@ int wa_ctx_cache_stats(wa_ctx *ctx, int64_t out[8]);
  * memory), [2] blocks and [3] bytes filled through the plain one (grids, trajectories, every planning call's scratch).  All 0 without
  * the knob. */
 int wa_ctx_poison_stats(wa_ctx *ctx, int64_t out[4]);
+/* Debug read-out of WA_DEV_GUARD=1 (read at wa_ctx_create): every plain device block the library allocates for a call on such a context
+ * (grids, trajectories, splines, every planning call's scratch, the whole blocks of the context's allocator; not the blocks the arena
+ * builds from chunks) stands between two red zones of 4096 bytes filled with WA_DEV_GUARD_BYTE (0 .. 255, default 0xa5).  The back zone
+ * starts behind the bytes that were asked for.  When the block is given back the device is waited for and both zones are compared byte
+ * by byte.  [0] blocks handed out with zones, [1] blocks freed and checked, [2] blocks live now, [3] requested bytes live now, [4] blocks
+ * freed with a damaged front zone, [5] with a damaged back zone, [6] requested size of the first damaged block (-1: none), [7] distance
+ * in bytes of its first damaged byte from the block: >= 0 behind its end, < 0 in front of its start.  All 0 / -1 without the knob.
+ * WA_ERR_ARG for a NULL argument. */
+int wa_ctx_guard_stats(wa_ctx *ctx, int64_t out[8]);
+/* The proof that the check above fires, on a block of the library's own: allocates a guarded block of `bytes`, writes one byte (the
+ * complement of the guard byte) at `offset` from the block's start with hipMemsetAsync on the context's stream, and frees the block.
+ * No kernel is launched.  WA_ERR_ARG for bytes < 0 or an offset outside [-4096, bytes + 4096): the write never leaves the allocation.
+ * WA_ERR_STATE on a context created without WA_DEV_GUARD=1. */
+int wa_ctx_guard_selftest(wa_ctx *ctx, int64_t bytes, int64_t offset);
 /* Every call on a context (and on anything created from it) runs on that context's device regardless of the calling
  * thread's current HIP device, and restores the caller's current device before returning. */
 int wa_ctx_create(int device_ordinal, wa_ctx **out);

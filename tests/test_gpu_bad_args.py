@@ -96,3 +96,5 @@ def test_valid_handles_and_nothing_else_never_crash():
             if name == n:
                 assert v != "0", (name, tag)
     assert status[("wa_acs_run", "dense")] != "0" and status[("wa_acs_result", "dense")] != "0"
+    # the red zones' read-out refuses a NULL array (WA_ERR_ARG); their self-test has no guarded block to damage on a plain context (WA_ERR_STATE)
+    assert status[("wa_ctx_guard_stats", "-")] == "1" and status[("wa_ctx_guard_selftest", "-")] == "8"

@@ -152,6 +152,8 @@ SYMBOLS = {
     "wa_ctx_trim": (C.c_int, [_V]),
     "wa_ctx_cache_stats": (C.c_int, [_V, _P]),
     "wa_ctx_poison_stats": (C.c_int, [_V, _P]),
+    "wa_ctx_guard_stats": (C.c_int, [_V, _P]),
+    "wa_ctx_guard_selftest": (C.c_int, [_V, _I64, _I64]),
     "wa_ctx_create": (C.c_int, [C.c_int, C.POINTER(_V)]),
     "wa_ctx_destroy": (None, [_V]),
     "wa_last_error": (C.c_char_p, [_V]),

@@ -98,6 +98,20 @@ class Context:
         self.check(self.lib.wa_ctx_poison_stats(self.h, v))
         return {k: int(x) for k, x in zip(("ctx_blocks", "ctx_bytes", "plain_blocks", "plain_bytes"), v)}
 
+    GUARD_KEYS = ("handed_out", "checked", "live_blocks", "live_bytes", "front_damaged", "back_damaged", "first_bytes", "first_distance")
+
+    def guard_stats(self):
+        """wa_ctx_guard_stats as a dict: the red zones of WA_DEV_GUARD=1 -- blocks handed out, freed and checked, live (with their
+        requested bytes), freed with a damaged front / back zone, and the first damaged block's size and the distance of its first
+        damaged byte (>= 0 behind the block, < 0 in front of it).  All 0, first_bytes -1, without the knob."""
+        v = (C.c_int64 * 8)()
+        self.check(self.lib.wa_ctx_guard_stats(self.h, v))
+        return {k: int(x) for k, x in zip(self.GUARD_KEYS, v)}
+
+    def guard_selftest(self, n_bytes, offset):
+        """wa_ctx_guard_selftest: one byte written at `offset` of a guarded block of `n_bytes` that the library allocates and frees"""
+        self.check(self.lib.wa_ctx_guard_selftest(self.h, int(n_bytes), int(offset)))
+
     def sync(self):
         self.check(self.lib.wa_ctx_sync(self.h))
 

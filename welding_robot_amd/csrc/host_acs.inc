@@ -356,7 +356,7 @@ int wa_acs_create_lazy_nb(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, int
 
 static void free_trace(wa_acs *s)
 {
-    hipFree(s->D.trBest); hipFree(s->D.trIter); hipFree(s->D.trColony); hipFree(s->D.trFinite); hipFree(s->D.trSteps);
+    dev_free(s->D.trBest); dev_free(s->D.trIter); dev_free(s->D.trColony); dev_free(s->D.trFinite); dev_free(s->D.trSteps);
     s->D.trBest = s->D.trIter = nullptr;
     s->D.trColony = s->D.trFinite = nullptr;
     s->D.trSteps = nullptr;
@@ -368,11 +368,11 @@ void wa_acs_destroy(wa_acs *s)
     WaDevGuard dev_guard_(s ? s->ctx : nullptr);
     if (!s) return;
     hipStreamSynchronize(s->ctx->stream);
-    if (s->d_stage) hipFree(s->d_stage);
+    if (s->d_stage) dev_free(s->d_stage);
     if (s->d_conv) ctx_free(s->ctx, s->d_conv);
     if (s->h_verdict) hipHostFree(s->h_verdict);
 #ifdef WA_STATE_HASH
-    if (s->d_hashlog) hipFree(s->d_hashlog);
+    if (s->d_hashlog) dev_free(s->d_hashlog);
 #endif
     for (auto &p : s->ev) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto &p : s->ev_pool) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
@@ -1420,7 +1420,7 @@ static int acs_fetch_results(wa_acs *s)
         // context's arena, a virtual range backed by several physical chunks, and the runtime's 2-D copy refuses a rectangle that leaves the
         // first chunk: "invalid argument", measured in round 5.)
         if (s->stage_words < words) {
-            if (s->d_stage) hipFree(s->d_stage);
+            if (s->d_stage) dev_free(s->d_stage);
             s->d_stage = nullptr; s->stage_words = 0;
             if (dalloc(&s->d_stage, words + words / 2) != hipSuccess) return fail(ctx, WA_ERR_ALLOC, "wa_acs_result: staging");
             s->stage_words = words + words / 2;
@@ -1545,7 +1545,7 @@ int wa_acs_read_pheromone(wa_acs *s, int32_t slot, float *out)
         hipError_t h = hipGetLastError();
         h = h ? h : hipMemcpyAsync(out, d_out, sizeof(float) * m, hipMemcpyDeviceToHost, ctx->stream);   // same stream as the kernel
         h = h ? h : hipStreamSynchronize(ctx->stream);
-        hipFree(d_out);
+        dev_free(d_out);
         if (h != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_acs_read_pheromone: %s", hipGetErrorString(h));
         return WA_OK;
     }

@@ -167,10 +167,10 @@ void wa_comm_destroy(wa_comm *c)
     if (c->nccl) ncclCommDestroy(c->nccl);
     if (c->ready) hipEventDestroy(c->ready);
     if (c->stream) hipStreamDestroy(c->stream);
-    hipFree(c->gkey);
-    hipFree(c->d_tmp);
-    hipFree(c->scratch);
-    hipFree(c->hdr);
+    dev_free(c->gkey);
+    dev_free(c->d_tmp);
+    dev_free(c->scratch);
+    dev_free(c->hdr);
     delete c;
 }
 
@@ -223,7 +223,7 @@ int wa_acs_allreduce_best(wa_acs *s, wa_comm *c, int32_t gen0, int32_t count)
         while (cap < end) cap *= 2;
         unsigned long long *fresh = nullptr;
         if (dalloc(&fresh, (size_t)cap)) return fail(ctx, WA_ERR_ALLOC, "wa_acs_allreduce_best: history");
-        if (c->gkey) { HIPC(ctx, hipMemcpy(fresh, c->gkey, sizeof(unsigned long long) * c->gcap, hipMemcpyDeviceToDevice)); hipFree(c->gkey); }
+        if (c->gkey) { HIPC(ctx, hipMemcpy(fresh, c->gkey, sizeof(unsigned long long) * c->gcap, hipMemcpyDeviceToDevice)); dev_free(c->gkey); }
         c->gkey = fresh;
         c->gcap = (int32_t)cap;
     }
@@ -287,7 +287,7 @@ static int comm_scratch(wa_comm *c, size_t bytes, void **out)
     if (c->fail_scratch_in > 0 && --c->fail_scratch_in == 0) return fail(c->ctx, WA_ERR_ALLOC, "wa_comm: staging (forced failure: wa_test_comm_fail_scratch)");
 #endif
     if (bytes > c->scratch_bytes) {
-        hipFree(c->scratch);
+        dev_free(c->scratch);
         c->scratch = nullptr; c->scratch_bytes = 0;
         const size_t want = bytes + bytes / 2;
         if (dev_malloc(&c->scratch, want) != hipSuccess) return fail(c->ctx, WA_ERR_ALLOC, "wa_comm: staging");
@@ -591,7 +591,7 @@ int wa_comm_allreduce_f64(wa_comm *c, double *inout, int32_t count, int32_t op)
     COMM_LIVE(c);
     if (count > c->tmp_cap) {
         { const int wrc = comm_wait(c, "wa_comm_allreduce_f64"); if (wrc) return wrc; }
-        hipFree(c->d_tmp);
+        dev_free(c->d_tmp);
         c->d_tmp = nullptr; c->tmp_cap = 0;
         if (dalloc(&c->d_tmp, (size_t)count)) return fail(c->ctx, WA_ERR_ALLOC, "wa_comm_allreduce_f64: staging");
         c->tmp_cap = count;

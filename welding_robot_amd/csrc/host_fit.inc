@@ -39,7 +39,7 @@ static hipError_t fit_spline_room(wa_ctx *ctx, FitBuffers &B, int32_t degree, lo
     S.n_middle = n_cps - 2 * degree;              // BSplineBasic.h:40
     S.n_knots = n_cps + degree + 1;               // :38-39
     if (n_cps <= B.cap_cps) return hipSuccess;
-    hipFree(S.knots); hipFree(S.cps);   // (the spline's own: it grows by half)
+    dev_free(S.knots); dev_free(S.cps);   // (the spline's own: it grows by half)
     S.knots = nullptr; S.cps = nullptr;
     B.cap_cps = 0;
     const long long cap = std::min(n_cps + n_cps / 2, (long long)WA_FIT_MAX_CPS);

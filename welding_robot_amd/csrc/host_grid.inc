@@ -80,7 +80,7 @@ static int grid_count_free(wa_grid *g)
     }
     e = e ? e : hipMemcpyAsync(&h, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream);
     e = e ? e : hipStreamSynchronize(ctx->stream);
-    hipFree(d_cnt);
+    dev_free(d_cnt);
     if (e != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "free-voxel count: %s", hipGetErrorString(e));
     g->n_free = (int64_t)h;
     return WA_OK;
@@ -162,7 +162,7 @@ void wa_grid_destroy(wa_grid *g)
 {
     WaDevGuard dev_guard_(g ? g->ctx : nullptr);
     if (!g) return;
-    hipFree(g->cx); hipFree(g->cy); hipFree(g->cz); hipFree(g->occ); hipFree(g->d2); hipFree(g->fbits);
+    dev_free(g->cx); dev_free(g->cy); dev_free(g->cz); dev_free(g->occ); dev_free(g->d2); dev_free(g->fbits);
     delete g;
 }
 int wa_grid_info(const wa_grid *g, int32_t dims3[3], float *precision, int32_t *wall, int64_t *n_free)

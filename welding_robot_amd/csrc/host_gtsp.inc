@@ -26,8 +26,8 @@ int wa_gtsp_solve(wa_ctx *ctx, const double *dist, int32_t n, int32_t cnt, int32
     e = e ? e : dalloc(&G.out_cost, I);
     e = e ? e : dalloc(&G.out_iters, I);
     auto cleanup = [&]() {
-        hipFree(d_dist); hipFree(G.pher); hipFree(G.h6); hipFree(G.info); hipFree(G.antL); hipFree(G.tours);
-        hipFree(G.best); hipFree(G.inJ); hipFree(G.rbuf); hipFree(G.rng); hipFree(G.out_cost); hipFree(G.out_iters);
+        dev_free(d_dist); dev_free(G.pher); dev_free(G.h6); dev_free(G.info); dev_free(G.antL); dev_free(G.tours);
+        dev_free(G.best); dev_free(G.inJ); dev_free(G.rbuf); dev_free(G.rng); dev_free(G.out_cost); dev_free(G.out_iters);
     };
     if (e != hipSuccess) { cleanup(); return fail(ctx, WA_ERR_ALLOC, "wa_gtsp_solve: %s", hipGetErrorString(e)); }
     G.dist = d_dist;
@@ -93,8 +93,8 @@ int wa_gtsp_solve(wa_ctx *ctx, const double *dist, int32_t n, int32_t cnt, int32
 #undef WA_GTSPW_CONSTRUCT
             if (h == hipSuccess) h = hipGetLastError();
             h = h ? h : hipStreamSynchronize(ctx->stream);
-            hipFree(W.state);
-            hipFree(W.valid);
+            dev_free(W.state);
+            dev_free(W.valid);
         } else if (n <= 256 && env_int("WA_GTSP_GENERIC", 0) == 0) {
             size_t shm = (in_lds ? info_bytes : 0) + (prefix ? sizeof(double) * ld * threads : 0);
 #define WA_GTSP_LAUNCH(NW, LDS, PFX)                                                                                     \

@@ -82,7 +82,7 @@ void wa_traj_destroy(wa_traj *t)
 {
     WaDevGuard dev_guard_(t ? t->ctx : nullptr);
     if (!t) return;
-    hipFree(t->xyz);
+    dev_free(t->xyz);
     delete t;
 }
 
@@ -122,7 +122,7 @@ void wa_bspline_destroy(wa_bspline *b)
 {
     WaDevGuard dev_guard_(b ? b->ctx : nullptr);
     if (!b) return;
-    hipFree(b->S.knots); hipFree(b->S.cps); hipFree(b->d_ends);
+    dev_free(b->S.knots); dev_free(b->S.cps); dev_free(b->d_ends);
     delete b;
 }
 

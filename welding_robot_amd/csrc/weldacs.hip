@@ -70,6 +70,9 @@ struct wa_ctx {
     bool cache_on = true, poison = false;      // WA_DEV_CACHE=0 / WA_DEV_POISON=1, read at wa_ctx_create
     int poison_byte = 0xff;                    // WA_DEV_POISON_BYTE (0 .. 255), read at wa_ctx_create: what a poisoned block is filled with
     mutable std::atomic<int64_t> poison_stat[4] = {};   // wa_ctx_poison_stats: blocks / bytes filled by ctx_alloc, blocks / bytes filled by dev_malloc
+    bool guard = false;                        // WA_DEV_GUARD=1, read at wa_ctx_create: every dev_malloc block of a call on this context stands between two red zones
+    int guard_byte = 0xa5;                     // WA_DEV_GUARD_BYTE (0 .. 255), read at wa_ctx_create: what the zones are filled with
+    mutable int64_t guard_stat[8] = {0, 0, 0, 0, 0, 0, -1, 0};   // wa_ctx_guard_stats, written under g_guard_mu (dev_malloc / dev_free)
     // the arena (round 5): physical chunks of two sizes, created once and mapped into whatever virtual range the next block needs
     bool arena_on = false;                     // the device supports virtual memory management and WA_DEV_ARENA != 0
     bool arena_strict = false;       // kept blocks are only reused for requests of exactly their size (the retry of a solver that did not fit)
@@ -234,19 +237,20 @@ static int fail(wa_ctx *c, int code, const char *fmt, const char *a = "", const 
 
 // Every entry point runs on the device of its context, whatever device the calling thread had current (another
 // context on another GPU, torch.cuda.set_device ...), and leaves the caller's current device as it found it.
-// ... and names the context to dev_malloc for as long as the call runs when it was created with WA_DEV_POISON=1 (null otherwise, also
-// for a call on a context without the knob made from inside a poisoned call): every plain device block the calling thread allocates
-// meanwhile is filled with that context's poison byte (poison_fill below).  One thread-local pointer saved, set and put back per call.
-static thread_local const wa_ctx *g_poison_ctx = nullptr;
+// ... and names the context to dev_malloc for as long as the call runs when it was created with WA_DEV_POISON=1 or WA_DEV_GUARD=1 (null
+// otherwise, also for a call on a context without either knob made from inside a call on one that has them): every plain device block
+// the calling thread allocates meanwhile is filled with that context's poison byte (poison_fill below) and / or put between two red
+// zones of its guard byte (guard_arm below).  One thread-local pointer saved, set and put back per call.
+static thread_local const wa_ctx *g_alloc_ctx = nullptr;
 struct WaDevGuard {
     int prev = -1;
     bool switched = false, ok = true, named = false;
-    const wa_ctx *prev_poison = nullptr;
+    const wa_ctx *prev_named = nullptr;
     explicit WaDevGuard(const wa_ctx *c)
     {
         if (!c) return;
-        prev_poison = g_poison_ctx;   // (entry points call each other: restored on the way out)
-        g_poison_ctx = c->poison ? c : nullptr;
+        prev_named = g_alloc_ctx;   // (entry points call each other: restored on the way out)
+        g_alloc_ctx = (c->poison || c->guard) ? c : nullptr;
         named = true;
         if (hipGetDevice(&prev) != hipSuccess) prev = -1;
         if (prev != c->device) {
@@ -256,7 +260,7 @@ struct WaDevGuard {
     }
     ~WaDevGuard()
     {
-        if (named) g_poison_ctx = prev_poison;
+        if (named) g_alloc_ctx = prev_named;
         if (switched) hipSetDevice(prev);
     }
     WaDevGuard(const WaDevGuard &) = delete;
@@ -377,6 +381,7 @@ static size_t arena_oldest_kept(const wa_ctx *c)
     return best;
 }
 
+static hipError_t dev_free(void *p);   // (with dev_malloc below: a block with red zones is checked before it goes)
 // kept memory of one context -> the driver, at least `need` bytes of it if there is that much (need = 0: everything).  Pooled chunks of
 // the size classes that are NOT wanted go first (the wanted class's pool is empty on the asking context), then kept blocks, least
 // recently used first, then cached whole blocks, least recently used first.
@@ -402,7 +407,7 @@ static size_t cache_release_locked(wa_ctx *c, size_t need = 0, int spare_class =
     }
     std::sort(c->cache.begin(), c->cache.end(), [](const WaDevBlock &a, const WaDevBlock &b) { return a.stamp > b.stamp; });   // oldest last
     while (!c->cache.empty() && !enough()) {
-        hipFree(c->cache.back().p);
+        dev_free(c->cache.back().p);
         freed += c->cache.back().bytes;
         c->cache.pop_back();
     }
@@ -427,24 +432,51 @@ static size_t cache_release_device(int device, size_t need = 0)
 // the device is out of memory the kept memory of the contexts on it is released -- as much as is needed -- and the call retried while
 // the driver's wipe proceeds, for a few seconds at most
 //
-// WA_DEV_POISON=1: a block allocated inside a call on such a context (g_poison_ctx, set by the call's WaDevGuard) is filled with the
+// WA_DEV_POISON=1: a block allocated inside a call on such a context (g_alloc_ctx, set by the call's WaDevGuard) is filled with the
 // context's poison byte before it is handed out.  The fill is enqueued on the context's stream, in front of the call's own work there --
 // and then WAITED FOR: some blocks are first used on another stream (the communicator's, the solver's group streams), which the
-// context's stream does not order.  Poison mode is a test mode; the wait keeps the rule simple.  Without the knob g_poison_ctx is null:
+// context's stream does not order.  Poison mode is a test mode; the wait keeps the rule simple.  Without the knob g_alloc_ctx is null:
 // nothing is enqueued, locked or waited for.  fill = false: the caller (ctx_alloc_bytes) fills and counts the block itself.
-// tests/test_alloc_rules.py: the runtime's device allocators are called between the two marker lines below and nowhere else in csrc.
+//
+// WA_DEV_GUARD=1: a block allocated inside a call on such a context is bytes + 2 * WA_GUARD_Z long.  The WA_GUARD_Z bytes in front of what
+// the caller gets and the WA_GUARD_Z bytes behind the bytes it ASKED FOR (before the < 16 -> 16 rounding: one stray uint8 lands in the
+// zone) are filled with the context's guard byte, and {caller's pointer -> base, bytes, context} goes into a process-wide table.
+// dev_free looks the pointer up, waits for the device, copies both zones to the host and compares every byte with the guard byte
+// (zone comparison): a write in front of a block or behind it -- into the slack of the driver's granule, where it changes nothing that
+// anybody reads -- is counted on the owning context (wa_ctx_guard_stats), with the block's size and the distance of the first damaged
+// byte.  Blocks that are live say what has not been given back.  Whoever asks is covered: DevBuf, dalloc, the whole blocks of the
+// context's allocator.  Blocks the arena builds from chunks are not (sizes rounded to 2 MiB by construction).
+// Guard mode is a test mode like the poison.  Without the knob in any context of the process (g_guard_any) the table is never touched:
+// dev_malloc reads the thread-local it read before, dev_free one flag; nothing is locked, enqueued or waited for.
+// tests/test_alloc_rules.py: the runtime's device allocators and hipFree are called between the marker lines and nowhere else in csrc.
 // ---- device allocation: begin
+static const size_t WA_GUARD_Z = 4096;   // a row of int32 at the widest small shape of the tests is 130 * 4 B; keeps hipMalloc's alignment
+struct WaGuardEntry { void *base; size_t bytes; const wa_ctx *ctx; };   // ctx: null once the owning context is gone
+static std::mutex g_guard_mu;
+static std::unordered_map<void *, WaGuardEntry> g_guard_table;
+static std::atomic<bool> g_guard_any{false};   // a context with WA_DEV_GUARD=1 has been created in this process
 static hipError_t poison_fill(const wa_ctx *c, void *p, size_t bytes, bool plain)
 {
-    hipError_t e = hipMemsetAsync(p, c->poison_byte, bytes, c->stream);
+    hipError_t e = bytes ? hipMemsetAsync(p, c->poison_byte, bytes, c->stream) : hipSuccess;
     if (e != hipSuccess) return e;   // (nothing was filled: nothing is counted)
     c->poison_stat[plain ? 2 : 0] += 1;
     c->poison_stat[plain ? 3 : 1] += (int64_t)bytes;
     return plain ? hipStreamSynchronize(c->stream) : hipSuccess;
 }
+// the two zones of a fresh block; waited for, like a plain block's poison and for the same reason
+static hipError_t guard_arm(const wa_ctx *c, void *base, size_t bytes)
+{
+    hipError_t e = hipMemsetAsync(base, c->guard_byte, WA_GUARD_Z, c->stream);
+    e = e ? e : hipMemsetAsync((char *)base + WA_GUARD_Z + bytes, c->guard_byte, WA_GUARD_Z, c->stream);
+    return e ? e : hipStreamSynchronize(c->stream);
+}
 static hipError_t dev_malloc(void **out, size_t bytes, bool fill = true)
 {
+    const wa_ctx *pc = g_alloc_ctx;
+    const bool zones = pc && pc->guard;
+    const size_t asked = bytes;
     if (bytes < 16) bytes = 16;
+    if (zones) bytes = asked + 2 * WA_GUARD_Z;
     hipError_t e = hipMalloc(out, bytes);
     int dev = 0;
     if (e == hipErrorOutOfMemory && ((void)hipGetLastError(), hipGetDevice(&dev)) == hipSuccess) {
@@ -468,12 +500,69 @@ static hipError_t dev_malloc(void **out, size_t bytes, bool fill = true)
         }
         if (e != hipSuccess) *out = nullptr;
     }
-    if (e == hipSuccess && fill)
-        if (const wa_ctx *pc = g_poison_ctx) {
-            e = poison_fill(pc, *out, bytes, true);
-            if (e != hipSuccess) { hipFree(*out); *out = nullptr; }
-        }
+    if (e != hipSuccess) return e;
+    void *base = *out;
+    if (zones) {
+        *out = (char *)base + WA_GUARD_Z;
+        bytes = asked;      // (the poison covers what was asked for: the back zone starts behind it)
+        e = guard_arm(pc, base, asked);
+    }
+    if (e == hipSuccess && fill && pc && pc->poison) e = poison_fill(pc, *out, bytes, true);
+    if (e != hipSuccess) { hipFree(base); *out = nullptr; return e; }
+    if (zones) {
+        std::lock_guard<std::mutex> lk(g_guard_mu);
+        g_guard_table[*out] = {base, asked, pc};
+        pc->guard_stat[0] += 1;
+        pc->guard_stat[2] += 1;
+        pc->guard_stat[3] += (int64_t)asked;
+    }
     return e;
+}
+// Every device block of the library is given back here.  A block with zones is checked first (above); any other pointer goes to hipFree
+// as it always did.
+static hipError_t dev_free(void *p)
+{
+    if (!p || !g_guard_any.load(std::memory_order_relaxed)) return hipFree(p);
+    WaGuardEntry ent;
+    {
+        std::lock_guard<std::mutex> lk(g_guard_mu);
+        auto it = g_guard_table.find(p);
+        if (it == g_guard_table.end()) ent.base = nullptr;
+        else ent = it->second;
+    }
+    if (!ent.base) return hipFree(p);
+    // zone comparison: everything enqueued on the device has finished, so whatever was going to write the zones has
+    std::vector<unsigned char> h(2 * WA_GUARD_Z);
+    hipError_t e = hipDeviceSynchronize();
+    e = e ? e : hipMemcpy(h.data(), ent.base, WA_GUARD_Z, hipMemcpyDeviceToHost);
+    e = e ? e : hipMemcpy(h.data() + WA_GUARD_Z, (char *)p + ent.bytes, WA_GUARD_Z, hipMemcpyDeviceToHost);
+    {
+        std::lock_guard<std::mutex> lk(g_guard_mu);
+        auto it = g_guard_table.find(p);
+        const wa_ctx *c = it != g_guard_table.end() ? it->second.ctx : nullptr;   // (null: the owner went first, wa_ctx_destroy)
+        if (it != g_guard_table.end()) g_guard_table.erase(it);
+        if (c) {
+            c->guard_stat[2] -= 1;
+            c->guard_stat[3] -= (int64_t)ent.bytes;
+            if (e == hipSuccess) {
+                const unsigned char gb = (unsigned char)c->guard_byte;
+                int64_t front = -1, back = -1;    // the first damaged byte of either zone, lowest address first
+                for (size_t i = 0; i < WA_GUARD_Z && front < 0; i++)
+                    if (h[i] != gb) front = (int64_t)i;
+                for (size_t i = 0; i < WA_GUARD_Z && back < 0; i++)
+                    if (h[WA_GUARD_Z + i] != gb) back = (int64_t)i;
+                c->guard_stat[1] += 1;
+                if (front >= 0) c->guard_stat[4] += 1;
+                if (back >= 0) c->guard_stat[5] += 1;
+                if ((front >= 0 || back >= 0) && c->guard_stat[6] < 0) {
+                    c->guard_stat[6] = (int64_t)ent.bytes;
+                    c->guard_stat[7] = front >= 0 ? front - (int64_t)WA_GUARD_Z : back;
+                }
+            }
+        }
+    }
+    const hipError_t f = hipFree(ent.base);
+    return e ? e : f;
 }
 // ---- device allocation: end (hipMalloc)
 template <class T>
@@ -490,8 +579,8 @@ struct DevBuf {
     DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); return *this; }
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { hipFree(p); }
-    hipError_t alloc(size_t count) { hipFree(p); p = nullptr; return dalloc(&p, count); }   // (what it held before is given back first)
+    ~DevBuf() { dev_free(p); }
+    hipError_t alloc(size_t count) { dev_free(p); p = nullptr; return dalloc(&p, count); }   // (what it held before is given back first)
     T *detach() { T *q = p; p = nullptr; return q; }                            // the caller owns it from here
     operator T *() const { return p; }
 };
@@ -651,7 +740,7 @@ static void cache_enforce_limits_locked(wa_ctx *c)
     if (whole > small_limit) {
         std::sort(c->cache.begin(), c->cache.end(), [](const WaDevBlock &a, const WaDevBlock &b) { return a.stamp > b.stamp; });
         while (!c->cache.empty() && whole > small_limit) {
-            hipFree(c->cache.back().p);
+            dev_free(c->cache.back().p);
             whole -= c->cache.back().bytes;
             c->cache_bytes -= c->cache.back().bytes;
             c->stat[WA_ST_RELEASED_BYTES] += (int64_t)c->cache.back().bytes;
@@ -745,7 +834,7 @@ static void ctx_free(wa_ctx *c, const void *cp)
             }
         }
     }
-    hipFree(p);
+    dev_free(p);
 }
 // DevBuf's sibling for a block from ctx_alloc.  Such a block goes back to the context's cache, where the next caller may be handed it
 // at once: the context's stream is waited for first, so that nothing launched by this call still writes it.
@@ -787,6 +876,9 @@ int wa_ctx_create(int device_ordinal, wa_ctx **out)
     c->cache_on = env_int("WA_DEV_CACHE", 1) != 0;
     c->poison = env_int("WA_DEV_POISON", 0) != 0;
     c->poison_byte = env_int("WA_DEV_POISON_BYTE", 255) & 255;
+    c->guard = env_int("WA_DEV_GUARD", 0) != 0;
+    c->guard_byte = env_int("WA_DEV_GUARD_BYTE", 0xa5) & 255;
+    if (c->guard) g_guard_any.store(true);
     {   // the arena needs virtual memory management; how much the context may keep is a share of the device's memory
         int vmm = 0;
         if (hipDeviceGetAttribute(&vmm, hipDeviceAttributeVirtualMemoryManagementSupported, device_ordinal) != hipSuccess) { vmm = 0; (void)hipGetLastError(); }
@@ -851,6 +943,34 @@ int wa_ctx_poison_stats(wa_ctx *c, int64_t out[4])
     for (int i = 0; i < 4; i++) out[i] = c->poison_stat[i].load();
     return WA_OK;
 }
+int wa_ctx_guard_stats(wa_ctx *c, int64_t out[8])
+{
+    if (!c || !out) return WA_ERR_ARG;
+    if (!c->guard) {   // (nothing is locked without the knob)
+        for (int i = 0; i < 8; i++) out[i] = i == 6 ? -1 : 0;
+        return WA_OK;
+    }
+    std::lock_guard<std::mutex> lk(g_guard_mu);
+    for (int i = 0; i < 8; i++) out[i] = c->guard_stat[i];
+    return WA_OK;
+}
+// one byte written on purpose into a block of the library's own, inside it or inside its zones: what shows that the check fires
+int wa_ctx_guard_selftest(wa_ctx *c, int64_t bytes, int64_t offset)
+{
+    if (!c) return WA_ERR_ARG;
+    if (!c->guard) return fail(c, WA_ERR_STATE, "wa_ctx_guard_selftest: the context was created without WA_DEV_GUARD=1");
+    if (bytes < 0 || offset < -(int64_t)WA_GUARD_Z || offset >= bytes + (int64_t)WA_GUARD_Z)
+        return fail(c, WA_ERR_ARG, "wa_ctx_guard_selftest: the offset leaves the zones");
+    WaDevGuard dev_guard_(c);
+    if (!dev_guard_.ok) return WA_ERR_DEVICE;
+    char *p = nullptr;
+    if (dev_malloc((void **)&p, (size_t)bytes) != hipSuccess) return fail(c, WA_ERR_ALLOC, "wa_ctx_guard_selftest");
+    const hipError_t e = hipMemsetAsync(p + offset, ~c->guard_byte & 255, 1, c->stream);
+    const hipError_t f = dev_free(p);
+    HIPC(c, e);
+    HIPC(c, f);
+    return WA_OK;
+}
 int wa_ctx_trim(wa_ctx *c)
 {
     if (!c) return WA_ERR_ARG;
@@ -867,6 +987,11 @@ void wa_ctx_destroy(wa_ctx *c)
     {
         std::lock_guard<std::mutex> lk(g_cache_mu);
         cache_release_locked(c);
+        if (c->guard) {   // blocks that outlive their context are still checked when they go, and counted nowhere
+            std::lock_guard<std::mutex> gl(g_guard_mu);
+            for (auto &kv : g_guard_table)
+                if (kv.second.ctx == c) kv.second.ctx = nullptr;
+        }
         g_cache_ctxs.erase(std::remove(g_cache_ctxs.begin(), g_cache_ctxs.end(), c), g_cache_ctxs.end());
     }
     hipStreamDestroy(c->stream);
