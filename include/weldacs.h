@@ -319,8 +319,8 @@ int wa_acs_converged_info(wa_acs *s, int32_t slot, uint64_t out[4]);
  * longer than the stream takes to drain; a wait given up enqueues every generation of the window, which is right whatever the window committed.
  * Behind a window that committed whole the next window's flush (the two launches behind the walk of its last generation) is enqueued directly behind the
  * window kernel, before the verdict: it flushes if that window commits whole too and returns at once otherwise (WA_CONVERGED_SPECULATE=0: never).
- * out: [0] verdicts the host went to read since the solver was created, [1] generations whose launches were not enqueued, [2] speculative flushes
- * cancelled, [3] waits given up, of [0].  Results are bit-identical with the read-back on or off.  Does not wait. */
+ * out: [0] verdicts the host went to read since the solver was created, [1] generations whose launches were not enqueued, [2] speculative launches
+ * (flushes, or walk launches: wa_acs_converged_carried_info) cancelled because their window did not commit whole, [3] waits given up, of [0].  Results are bit-identical with the read-back on or off.  Does not wait. */
 int wa_acs_converged_host_info(wa_acs *s, uint64_t out[4]);
 /* Owed evaporations, on the same path (a lone search whose verdicts the host reads; WA_CONVERGED_OWED=0, read at wa_acs_create: never).  A window that
  * commits whole in front of a generation that is enqueued in full whatever happens -- the last of the call, or one stamped for wa_acs_profile -- also
@@ -330,6 +330,14 @@ int wa_acs_converged_host_info(wa_acs *s, uint64_t out[4]);
  * window's evaporations with its own, [2] whole windows that were not carried (an ant leaves the path behind them: flushed as ever), [3] / [4]: of [1],
  * the sweeps that ran out of place / in place.  Results are bit-identical with the switch on or off.  Does not wait. */
 int wa_acs_converged_owed_info(wa_acs *s, uint64_t out[5]);
+/* The carried walk, where owed evaporations apply (WA_CONVERGED_CARRIED_WALK=0, read at wa_acs_create: never).  The flush of a carried window has one reader,
+ * the walk of the generation behind it, and the window has already tested that generation's ants: the flush is not enqueued at all, and the walk launch
+ * delivers every ant as a whole replay of the best path without reading the replay table.  Behind a window that committed whole that walk launch goes
+ * out in front of the next window's verdict and returns at its top unless the window turns out carried (WA_CONVERGED_SPECULATE=0: never ahead).
+ * out: [0] walk launches that took the carried path since the solver was created, [1] rows launches of carried windows that were not enqueued,
+ * [2] walk launches enqueued ahead of a verdict, [3] of [2], those cancelled.  Results are bit-identical with the switch on or off.  Waits for the
+ * work enqueued so far. */
+int wa_acs_converged_carried_info(wa_acs *s, uint64_t out[4]);
 /* evaporation sweep alone (ACSRank_3D.hpp:268-272) over `slot` -- for roofline measurements */
 int wa_acs_evaporate(wa_acs *s, int32_t slot, float rho, int32_t repeats);
 

@@ -2,7 +2,7 @@
 """Where the converged phase of a plain `bench.py` goes, from a rocprofv3 --kernel-trace CSV of the run: window kernels, launches that return at
 once, flushes and full generations, each with the gap in front of its dispatches.
 
-  python tools/converged_split.py <rocprof output dir or kernel_trace.csv> <bench json line file> [--from-window N] [--empty-us X] [--walk-us Y]
+  python tools/converged_split.py <rocprof output dir or kernel_trace.csv> <bench json line file> [--from-window N] [--empty-us X] [--walk-us Y] [--walk-ahead]
 
 The timed region starts at the W-th k_walk_dev dispatch (W warm-up generations of a throw-away search, which commit nothing, are in front).  The
 region reported starts at the generation in front of window kernel number N of the timed region (default 10: with bench.py's 50-generation calls
@@ -17,7 +17,12 @@ otherwise.  A speculative flush (two launches directly behind a window kernel, n
 was cancelled.  With owed evaporations (WA_CONVERGED_OWED) the flush of a carried window is one small launch: the table blocks of
 k_apply_table alone, or the speculative pair whose sweep blocks returned at once; both are classed `rows` (a cancelled speculative flush, whose
 two launches both return at once, cannot be told from the latter by its times and is counted there too).  The gap in front of a dispatch is its start minus the latest end of everything dispatched
-before it.  The classes' kernel time and gaps add up to the region's span."""
+before it.  The classes' kernel time and gaps add up to the region's span.
+
+--walk-ahead: the trace is of a library with the carried walk (WA_CONVERGED_CARRIED_WALK): a carried window has no rows launch, and the walk launch
+of the generation behind it stands directly behind the window kernel, enqueued ahead of the verdict.  Three launches directly behind a window kernel
+whose sweep ran are then that `full` generation (its short walk is the carried one, not a launch that returned at once), and a walk launch that
+nothing of its generation follows -- cancelled: the window was not carried -- is classed `walk ahead`."""
 import csv
 import glob
 import json
@@ -36,6 +41,7 @@ def main():
     d = json.loads([l for l in open(jpath).read().splitlines() if l.startswith("{")][-1])
     K, W = int(d["steps"]), int(d["warmup"])
     first_window, empty_us, walk_us = int(opt("--from-window", 10)), opt("--empty-us", 10.0), opt("--walk-us", 3.0)
+    walk_ahead = "--walk-ahead" in sys.argv
     files = [path] if os.path.isfile(path) else glob.glob(os.path.join(path, "**", "*kernel_trace.csv"), recursive=True)
     rows = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for f in files for r in csv.DictReader(open(f)))
     # every dispatch with the gap in front of it
@@ -68,13 +74,17 @@ def main():
             items.append(("rows", [None, None, timed[i]]))
             i += 1
             continue
+        if walk_ahead and (i + 1 >= len(timed) or timed[i + 1]["kind"] != TRIO[1]):
+            items.append(("walk ahead", [timed[i]]))
+            i += 1
+            continue
         trio = timed[i:i + 3]
         assert tuple(x["kind"] for x in trio) == TRIO, "dispatch %d of the timed region: %s" % (i, [x["kind"] for x in trio])
         if trio[1]["us"] < empty_us:
             cls = "at once"
         elif items and items[-1][0] == "at once":
             cls = "flush"            # (launches that return at once are followed by the flush of their window)
-        elif items and items[-1][0] == "window" and trio[0]["us"] < walk_us:
+        elif items and items[-1][0] == "window" and trio[0]["us"] < walk_us and not walk_ahead:
             cls = "flush"            # a window that committed its first generation alone
         else:
             cls = "full"
@@ -94,14 +104,14 @@ def main():
     print("| class | count | kernels us | gaps us | total us | share | per item us |")
     print("|---|---|---|---|---|---|---|")
     total = 0.0
-    for cls in ("window", "at once", "flush", "rows", "full"):
+    for cls in ("window", "at once", "flush", "rows", "walk ahead", "full"):
         mine = [xs for c, xs in region if c == cls]
         first_gap = region[0][1][0]["gap"] if region[0][0] == cls else 0.0      # (the gap in front of the region is not part of its span)
         kus, gus = sum(x["us"] for xs in mine for x in xs), sum(x["gap"] for xs in mine for x in xs) - first_gap
         total += kus + gus
         print("| %s | %d | %.1f | %.1f | %.1f | %.1f %% | %.2f |" % (cls, len(mine), kus, gus, kus + gus, 100 * (kus + gus) / span, (kus + gus) / max(len(mine), 1)))
     print("| all | %d | | | %.1f | %.1f %% | |" % (len(region), total, 100 * total / span))
-    for cls in ("window", "at once", "flush", "rows", "full"):
+    for cls in ("window", "at once", "flush", "rows", "walk ahead", "full"):
         mine = [xs for c, xs in region if c == cls]
         if not mine:
             continue

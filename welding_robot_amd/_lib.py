@@ -204,6 +204,7 @@ SYMBOLS = {
     "wa_acs_converged_info": (C.c_int, [_V, _I, _P]),
     "wa_acs_converged_host_info": (C.c_int, [_V, _P]),
     "wa_acs_converged_owed_info": (C.c_int, [_V, _P]),
+    "wa_acs_converged_carried_info": (C.c_int, [_V, _P]),
     "wa_acs_set_stragglers": (C.c_int, [_V, _I]),
     "wa_acs_walk_info": (C.c_int, [_V, _P]),
     "wa_acs_evaporate": (C.c_int, [_V, _I, _F, _I]),

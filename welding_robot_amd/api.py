@@ -667,6 +667,13 @@ class AcsSolver:
         self.ctx.check(self.ctx.lib.wa_acs_converged_owed_info(self.h, out))
         return dict(carried=int(out[0]), merged=int(out[1]), fallback=int(out[2]), out_of_place=int(out[3]), in_place=int(out[4]))
 
+    def converged_carried_info(self):
+        """the carried walk (where owed evaporations apply) since the solver was created: walk launches that took the carried path, rows launches
+        of carried windows that were not enqueued, walk launches enqueued ahead of their window's verdict and, of those, the cancelled ones"""
+        out = (C.c_uint64 * 4)()
+        self.ctx.check(self.ctx.lib.wa_acs_converged_carried_info(self.h, out))
+        return dict(walks=int(out[0]), rows_skipped=int(out[1]), spec_walks=int(out[2]), spec_cancelled=int(out[3]))
+
     def set_stragglers(self, generations):
         """generations of a search during which ants may be handed over (0: off, < 0: default)"""
         self.ctx.check(self.ctx.lib.wa_acs_set_stragglers(self.h, generations))

@@ -33,6 +33,11 @@
 // advanced.  If every ant of g + W replays the path the commit records the window as CARRIED in the header and in the verdict (WA_CONV_CARRIED); the
 // host then leaves the flush's sweep out and has the sweep of g + W multiply W + 1 times, from the buffer the window found the field in.  The header
 // keeps what a later change needs to chain windows without a field pass in between: `pending`, the evaporations owed, and `carried`.
+//
+// The CARRIED WALK (WA_CONVERGED_CARRIED_WALK).  The rows of a carried window's last snapshot had one reader: the walk of generation g + W, for the test
+// this kernel has just made.  The host therefore enqueues nothing at all for a window it has read as carried, and that generation's walk launch, told so
+// by WA_GEN_OWED, delivers every ant as a whole replay without the table (k_walk_dev, wa_walk_carried) -- when the header names its generation: `end`,
+// written with every commit, so that a header an earlier window left does not qualify.  k_apply_table of g + W rebuilds every row from the records.
 #pragma once
 
 #define WA_CONV_CHECK_WAVES 4     // wavefronts of a block that check the ants (lane = ant), ...
@@ -51,7 +56,10 @@ struct WaConvHdr {                // head of a slot's scratch block; the snapsho
     int32_t pending;              // j of the last commit: evaporations the flush applies (or, owed, the sweep of the generation behind it)
     int32_t carried;              // the last commit was of a whole window, and every ant of the generation behind it replays the path too
     unsigned long long whole, cut, gens;   // windows committed whole / cut (0 < j < W), generations committed (wa_acs_converged_info)
-    unsigned long long pad2_[3];
+    int32_t end;                  // the generation behind the last commit (gen0 + j): `carried` speaks of this generation's ants and of no other's
+    int32_t pad1_;
+    unsigned long long walks;     // walk launches that took the carried path (wa_acs_converged_carried_info)
+    unsigned long long pad2_;
 };
 static_assert(WA_CONV_SNAP == 14, "wa_table_rows strides the owed records by 14 floats");
 static_assert(sizeof(WaConvHdr) == 64, "the snapshots start 64 bytes into the block");
@@ -64,6 +72,15 @@ __device__ __forceinline__ float *wa_conv_snap(const WaAcsDev &D, int32_t slot, 
 }
 __device__ __forceinline__ int32_t wa_conv_pending(const WaAcsDev &D, int32_t slot) { return wa_conv_hdr(D, slot)->pending; }
 __device__ __forceinline__ bool wa_conv_carried(const WaAcsDev &D, int32_t slot) { return wa_conv_hdr(D, slot)->carried != 0; }
+// Generation `gen` is the one a carried window judged: the last commit was of a whole window that ends directly in front of it, and every ant of it
+// replays the best path (a header left by an earlier window names another generation and does not qualify)
+__device__ __forceinline__ bool wa_conv_carried_at(const WaAcsDev &D, int32_t slot, int32_t gen)
+{
+    if (!D.conv) return false;
+    const WaConvHdr *h = wa_conv_hdr(D, slot);
+    return h->carried != 0 && h->end == gen && D.ctl[slot].spec_until == gen;
+}
+__device__ __forceinline__ void wa_conv_count_walk(const WaAcsDev &D, int32_t slot) { wa_conv_hdr(D, slot)->walks += 1; }   // (one lane of one block per launch)
 // the path nodes' records of the last commit, [node][WA_CONV_SNAP] (the table blocks of the generation behind a carried window: wa_table_rows)
 __device__ __forceinline__ const float *wa_conv_owed_records(const WaAcsDev &D, int32_t slot) { return wa_conv_snap(D, slot, wa_conv_pending(D, slot) - 1); }
 #define WA_CONV_CARRIED 0x80u     // in the verdict word beside j (j <= WA_CONV_MAX_WINDOW < 128)
@@ -345,6 +362,7 @@ __global__ __launch_bounds__(WA_CONV_THREADS) void k_converged_run(WaAcsDev D, W
             *ctl = c;
             hdr->pending = j;
             hdr->carried = carried ? 1 : 0;
+            hdr->end = gen0 + j;
             hdr->gens += (unsigned long long)j;
             if (j == W) hdr->whole += 1; else hdr->cut += 1;
         }

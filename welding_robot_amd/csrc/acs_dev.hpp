@@ -12,7 +12,10 @@
 //   on the launches of generation g + W - 1 (the flush): behind a carried window the sweep blocks do nothing and the table blocks put the rows in
 //     place, not the records; behind any other window the launches flush as ever;
 //   on the launches of generation g + W (the host has read "carried"): the sweep blocks multiply every value pending + 1 times, the table blocks take
-//     the path nodes' records from the commit's snapshot.
+//     the path nodes' records from the commit's snapshot;
+//   on the WALK launch of generation g + W (k_walk_dev; WA_CONVERGED_CARRIED_WALK): the window has tested this generation's ants, so every ant delivers
+//     a whole replay without the replay table, whose rows of the commit nobody wrote -- the carried window has no flush at all.  With WA_GEN_SPEC beside
+//     it the launch stands in front of the verdict: carried path if the header names this generation (WaConvHdr::end), nothing otherwise.
 #define WA_GEN_OWED 0x20000000
 #define WA_GEN_FLAGS (WA_GEN_SPEC | WA_GEN_OWED)
 

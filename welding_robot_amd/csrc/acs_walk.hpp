@@ -1095,6 +1095,49 @@ __global__ __launch_bounds__(256) void k_apply_table(WaAcsDev D, WaRun R, int32_
     wa_apply_body<6>(D, slot, 0, ab >> split_log2, ab & ((1 << split_log2) - 1), 1 << split_log2, true);
 }
 
+__device__ __forceinline__ bool wa_conv_carried_at(const WaAcsDev &D, int32_t slot, int32_t gen);   // (acs_converged.hpp)
+__device__ __forceinline__ void wa_conv_count_walk(const WaAcsDev &D, int32_t slot);
+// One block of the walk launch behind a carried window (k_walk_dev).  An ant's block delivers a whole replay: L = bestL, the best path's node
+// count, "arrived on the replay track", and the best path's words in the ant's path array (512 words per round, as wa_walk_one copies them).  No
+// arrival is filed: nobody in this launch checks against the list, and apply + table of this generation empties it.  A resume block has nothing to
+// resume -- a window runs only while both straggler pools are empty.  Block 0 also does what the flush's table launch did besides the rows: the
+// next generation starts with no arrivals and an empty pool of its own
+__device__ __forceinline__ void wa_walk_carried(const WaAcsDev &D, int32_t slot, int32_t ant, int32_t colony, float bestL, int32_t rlen)
+{
+    const int32_t lane = threadIdx.x;
+    if (ant == 0) {
+        if (D.pool_n) {
+            const WaStrag sg = wa_strag_of(D, slot);
+#pragma unroll
+            for (int u = 0; u < 4; u++) sg.arr_len[u * 64 + lane] = 0xffffffffu;
+            if (lane == 0) { *sg.arr_n = 0; sg.pool_n[D.ctl[slot].gen & 1] = 0; }
+        }
+        if (lane == 0) wa_conv_count_walk(D, slot);
+    }
+    if (ant >= colony || colony > D.max_colony || ant >= D.max_colony) return;
+    const int32_t *bpath = D.bestpath + (int64_t)slot * D.path_cap;
+    int32_t *path = D.paths + ((int64_t)slot * D.max_colony + ant) * D.path_cap;
+    if (rlen > (int32_t)D.path_cap) rlen = (int32_t)D.path_cap;   // (never: a window covers no path longer than its snapshots)
+    for (int32_t q0 = 0; q0 < rlen; q0 += 512) {
+        int32_t w[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            const int32_t q = q0 + u * 64 + lane;
+            w[u] = q < rlen ? bpath[q] : 0;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            const int32_t q = q0 + u * 64 + lane;
+            if (q < rlen) path[q] = w[u];
+        }
+    }
+    if (lane == 0) {
+        D.antL[(int64_t)slot * D.max_colony + ant] = bestL;
+        D.antLen[(int64_t)slot * D.max_colony + ant] = rlen;
+        D.antRep[(int64_t)slot * D.max_colony + ant] = 1;
+    }
+}
+
 // DEV: grid = (max_colony, n_problems), block = one wavefront
 // WARM: the hand-scheduled loop touches the records two hops ahead of the ant (pays while a search has the GPU to itself, costs
 // when many searches saturate it: see walk_loop_gfx950.hpp)
@@ -1108,8 +1151,20 @@ __global__ __launch_bounds__(64) void k_walk_dev(WaAcsDev D, WaRun R, int hash_l
     extern __shared__ int32_t lds[];
     const int32_t slot = blockIdx.y, ant = blockIdx.x;
     const WaSlotCtl *c = &D.ctl[slot];
+    const int32_t gflags = gen & WA_GEN_FLAGS;
+    gen &= ~WA_GEN_FLAGS;
     if (gen < c->spec_until) return;   // a committed generation (acs_converged.hpp): ants and resume blocks alike have nothing to do
     const int32_t colony = c->colony[gen & 1];
+    if (!SPARSE && ALPHA1 && (gflags & WA_GEN_OWED)) {
+        // ---- the generation behind a CARRIED window (WA_GEN_OWED on the walk launch, acs_dev.hpp): the window kernel has tested every ant of this
+        // generation against the rows of its last snapshot and none leaves the path, so every ant delivers what a whole replay delivers -- without a
+        // draw and without the replay table, whose rows of that snapshot nobody has written.  The launch decides alike in all its blocks (one header)
+        if (wa_conv_carried_at(D, slot, gen)) {
+            wa_walk_carried(D, slot, ant, colony, c->bestL, c->best_len);
+            return;
+        }
+    }
+    if (gflags & WA_GEN_SPEC) return;   // enqueued in front of the verdict, and the window was not carried up to this generation: nothing at all
 #ifdef WA_STRAG_TIME
     if (threadIdx.x == 0 && gen < 128) atomicMax(&wa_strag_t[gen * 8 + 0], ~(unsigned long long)wall_clock64());
 #endif

@@ -186,6 +186,7 @@ static int acs_create_once(wa_ctx *ctx, const wa_grid *grid, int32_t n_slots, in
     s->conv_wait_us = env_int("WA_CONVERGED_WAIT_US", 200000);
     s->conv_spec = env_int("WA_CONVERGED_SPECULATE", 1) != 0;
     s->conv_owed = env_int("WA_CONVERGED_OWED", 1) != 0;
+    s->conv_cwalk = env_int("WA_CONVERGED_CARRIED_WALK", 1) != 0;
     s->prof_dispatch = env_int("WA_PROF_DISPATCH", 1) != 0;
     s->conv_enqueued.assign((size_t)n_slots, 0);
     {   // sweep grid: measured on MI355X -- 100 MB fields (128^3 x 6) peak at 4096 blocks (6.0 TB/s; 2048: 5.5, 8192: 5.8),
@@ -587,7 +588,7 @@ int wa_acs_begin(wa_acs *s, const wa_acs_params *p, int32_t n_problems, const in
     s->gens_enqueued = 0;
     s->conv_until = 0;
     s->conv_prev_whole = false;
-    s->conv_owed_flush = s->conv_owed_gen = -1;
+    s->conv_owed_flush = s->conv_owed_gen = s->conv_walk_done = -1;
     s->ran_before = false;
     return WA_OK;
 }
@@ -793,8 +794,11 @@ static void launch_fused(wa_acs *s, WaGroupRun &G, const float *src, float *dst,
 // the walk launch, rank beside the sweep, in-place sweep, hipGraph replay of the loop, non-temporal hints on the sweep -- all
 // bit-identical, all slower.
 // owed: the generation behind a carried window (a lone dense 6-neighbour search on the fused path): its sweep pays the window's evaporations too (WA_GEN_OWED)
+// walk_gflags: WA_GEN_OWED on the walk launch of that generation (its ants replay without the table: k_walk_dev), with WA_GEN_SPEC where the launch goes
+// out in front of the window's verdict.  part: the walk launch alone (the speculative one), or the generation without it (that launch ran)
+enum { WA_PART_ALL = 0, WA_PART_WALK = 1, WA_PART_REST = 2 };
 static void enqueue_generation(wa_acs *s, WaGroupRun &G, int32_t gen, bool last_of_call, bool sampled, bool fused, int32_t chunks,
-                               size_t shmem, int32_t P_all, bool owed = false)
+                               size_t shmem, int32_t P_all, bool owed = false, int32_t walk_gflags = 0, int part = WA_PART_ALL)
 {
     wa_ctx *ctx = s->ctx;
     const int32_t P = G.P;
@@ -813,8 +817,8 @@ static void enqueue_generation(wa_acs *s, WaGroupRun &G, int32_t gen, bool last_
     // Classes of several launches (the REF-mode walk, the plain path) keep the recorded pairs, and so does WA_PROF_DISPATCH=0
     const bool disp = sampled && s->prof_dispatch && fused && s->R.rng_mode == WA_RNG_DEV && s->colony_bound > 0;
     EvPair wp;
-    const bool wev = disp && prof_take(s, wp, WA_K_WALK);
-    EvPair *e = prof_open(s, st, WA_K_WALK, sampled && !disp);
+    const bool wev = part != WA_PART_REST && disp && prof_take(s, wp, WA_K_WALK);
+    EvPair *e = prof_open(s, st, WA_K_WALK, part != WA_PART_REST && sampled && !disp);
     // stragglers (DESIGN 4e): WA_RESUME_MAX resume blocks per search behind the ants' blocks, only where the apply + table launch follows
     // (it resets the arrival list and the pool) and only while a search explores (its first WA_STRAGGLER_GENS generations: once
     // converged every ant replays the best path, nothing is handed over, and empty resume blocks at the tail of every walk
@@ -824,8 +828,10 @@ static void enqueue_generation(wa_acs *s, WaGroupRun &G, int32_t gen, bool last_
     // ... or the last one, when draining is allowed: its stragglers are then finished by the next call's first launch or, if results are
     // asked for first, by a drain launch of resume blocks only (acs_drain)
     const bool hand_over = strag && (!last_of_call || (s->drain_ok && s->chained)) && gen + 1 <= s->straggler_gens;
-    if (last_of_call) s->pending_resume = hand_over;
-    if (s->nb == 26) {
+    if (last_of_call && part != WA_PART_WALK) s->pending_resume = hand_over;
+    if (part == WA_PART_REST) {
+        // (the walk launch is in the stream already)
+    } else if (s->nb == 26) {
         if (s->R.rng_mode == WA_RNG_DEV) {
             if (s->colony_bound > 0)
             {
@@ -860,10 +866,10 @@ static void enqueue_generation(wa_acs *s, WaGroupRun &G, int32_t gen, bool last_
                 t16 = s->tab16_env == 1 || (s->tab16_env < 0 && s->id_bits <= 21 && (int64_t)wg.x * P_all > per_cu * ctx->prop.multiProcessorCount);
             }
             const size_t shmem16 = ((size_t)2 << s->hash_log2) + WA_WALK_LDS_EXTRA + (size_t)s->lds_pad;
-#define WA_LAUNCH_WALK16(SP, RJ) do { if (wev) hipExtLaunchKernelGGL((k_walk_dev<true, SP, false, RJ, false, true>), wg, dim3(64), shmem16, st, wp.a, wp.b, 0, G.V, s->R, s->hash_log2, gen, walk_flags); \
-        else k_walk_dev<true, SP, false, RJ, false, true><<<wg, 64, shmem16, st>>>(G.V, s->R, s->hash_log2, gen, walk_flags); } while (0)
-#define WA_LAUNCH_WALK(A1, SP, WM, RJ, DR) do { if (wev) hipExtLaunchKernelGGL((k_walk_dev<A1, SP, WM, RJ, DR>), wg, dim3(64), shmem, st, wp.a, wp.b, 0, G.V, s->R, s->hash_log2, gen, walk_flags); \
-        else k_walk_dev<A1, SP, WM, RJ, DR><<<wg, 64, shmem, st>>>(G.V, s->R, s->hash_log2, gen, walk_flags); } while (0)
+#define WA_LAUNCH_WALK16(SP, RJ) do { if (wev) hipExtLaunchKernelGGL((k_walk_dev<true, SP, false, RJ, false, true>), wg, dim3(64), shmem16, st, wp.a, wp.b, 0, G.V, s->R, s->hash_log2, gen | walk_gflags, walk_flags); \
+        else k_walk_dev<true, SP, false, RJ, false, true><<<wg, 64, shmem16, st>>>(G.V, s->R, s->hash_log2, gen | walk_gflags, walk_flags); } while (0)
+#define WA_LAUNCH_WALK(A1, SP, WM, RJ, DR) do { if (wev) hipExtLaunchKernelGGL((k_walk_dev<A1, SP, WM, RJ, DR>), wg, dim3(64), shmem, st, wp.a, wp.b, 0, G.V, s->R, s->hash_log2, gen | walk_gflags, walk_flags); \
+        else k_walk_dev<A1, SP, WM, RJ, DR><<<wg, 64, shmem, st>>>(G.V, s->R, s->hash_log2, gen | walk_gflags, walk_flags); } while (0)
             s->last_walk[0] = s->hash_log2; s->last_walk[1] = t16 ? 1 : 0; s->last_walk[2] = (int32_t)(t16 ? shmem16 : shmem); s->last_walk[3] = warm ? 1 : 0;
             if (t16) {
                 if (s->lazy) { if (rej) WA_LAUNCH_WALK16(true, true); else WA_LAUNCH_WALK16(true, false); }
@@ -896,6 +902,7 @@ static void enqueue_generation(wa_acs *s, WaGroupRun &G, int32_t gen, bool last_
     }
     prof_close(st, e);
     if (wev) s->ev.push_back(wp);
+    if (part == WA_PART_WALK) return;
 #ifdef WA_STATE_HASH
 #define WA_HASH_GENS 256
 #define WA_HASH_AT(phase) do { if (s->d_hashlog && gen < WA_HASH_GENS) k_state_hash<<<dim3(96, (unsigned)P), 256, 0, st>>>(G.V, s->R, s->d_hashlog + (((int64_t)gen * 3 + (phase)) * s->n_slots + G.slot0) * 8, (phase)); } while (0)
@@ -1218,6 +1225,7 @@ int wa_acs_run(wa_acs *s, int32_t n_generations)
     const bool conv = n_generations > 1 && conv_rule(s, fused) && conv_scratch(s);
     const bool readback = conv && s->conv_readback && s->h_verdict && P == 1;   // (one search is one group)
     const bool owed_on = readback && s->conv_owed;   // carried windows leave their evaporations to the sweep of the generation behind them
+    const bool cwalk = owed_on && s->conv_cwalk;     // ... get no rows launch, and the walk behind them replays without the table
     const int32_t gen_last = s->gens_enqueued + n_generations - 1;
     const int32_t NG = n_generations > 0 ? pipe_groups(s, P) : 1;
     s->last_groups = NG;
@@ -1255,8 +1263,15 @@ int wa_acs_run(wa_acs *s, int32_t n_generations)
         if (gen == s->conv_owed_flush) {
             // the last generation of a window the host has read "carried" of: the rows launch alone, and the next generation pays the evaporations
             s->conv_owed_flush = -1;
-            const hipError_t re = enqueue_owed_rows(s, groups[0], gen);
-            if (re != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_acs_run: rows of a carried window: %s", hipGetErrorString(re));
+            if (cwalk) {
+                // ... and not even that: the rows have one reader, the walk of the next generation, which replays without them (WA_GEN_OWED on its launch);
+                // the generation is counted and the buffers flip as by any other
+                groups[0].cur ^= 1;
+                s->conv_cwalk_info[1]++;
+            } else {
+                const hipError_t re = enqueue_owed_rows(s, groups[0], gen);
+                if (re != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_acs_run: rows of a carried window: %s", hipGetErrorString(re));
+            }
             s->conv_owed_gen = gen + 1;
             s->gens_enqueued++;
             continue;
@@ -1284,7 +1299,55 @@ int wa_acs_run(wa_acs *s, int32_t n_generations)
             }
         }
         int32_t known = -2;                    // the verdict, where the host has it already
-        if (ask && s->conv_spec && s->conv_prev_whole && s->conv_wait_us > 0) {
+        if (ask && owe && cwalk && s->conv_spec && s->conv_prev_whole && s->conv_wait_us > 0) {
+            // The search's last window committed whole, and this one may be carried: it will be, most likely.  The WALK launch of generation gen+ask goes
+            // directly behind it (WA_GEN_SPEC | WA_GEN_OWED): its ants replay if the window was carried up to that generation, and it returns at its top
+            // otherwise.  It flips no buffer and writes the ants' arrays alone, which the next walk launch writes anyway: cancelled, it leaves nothing
+            WaGroupRun &G = groups[0];
+            const int cur0 = G.cur;
+            const int32_t gw = gen + ask;
+            const bool gw_last = gw == gen_last, gw_sampled = s->prof && (gw % s->prof_every) == 0;
+            const size_t ev0 = s->ev.size();
+            G.cur = cur0 ^ (ask & 1);          // (as the ask generations in front of it leave the buffers)
+            enqueue_generation(s, G, gw, gw_last, gw_sampled, fused, chunks, shmem, P, true, WA_GEN_SPEC | WA_GEN_OWED, WA_PART_WALK);
+            s->conv_cwalk_info[2]++;
+            known = conv_verdict(s, G.st, ask);
+            if (known < 0) {
+                HIPC(ctx, hipStreamSynchronize(G.st));
+                const uint32_t v = __atomic_load_n(s->h_verdict, __ATOMIC_ACQUIRE);
+                if ((v >> 8) != (s->conv_seq & 0xffffffu) || (int32_t)(v & 0x7fu) > ask) return fail(ctx, WA_ERR_DEVICE, "wa_acs_run: a window ended without its verdict");
+                known = (int32_t)(v & 0x7fu);
+                s->conv_carried = known == ask && (v & WA_CONV_CARRIED) != 0;
+            }
+            if (known == ask && s->conv_carried) {
+                // the walk ran: none of gen .. gen+ask-1 is enqueued, not even a rows launch; the other two launches of generation gen+ask follow
+                s->gens_enqueued += ask;
+                s->conv_host[1] += (uint64_t)(ask - 1);
+                g += ask - 1;
+                s->conv_owed_info[0]++;
+                s->conv_cwalk_info[1]++;
+                s->conv_owed_gen = s->conv_walk_done = gw;
+                s->conv_owed_reps = ask + 1;
+                continue;
+            }
+            // cancelled: the launch returned at its top, and its stamps (of a sampled generation) go back to the pool unharvested
+            s->conv_cwalk_info[3]++;
+            for (size_t q = ev0; q < s->ev.size(); q++) s->ev[q].cls = -1;
+            if (known == ask) {
+                // whole but not carried: an ant leaves the path in generation gen+ask and reads the field -- today's flush, now that the verdict is known
+                G.cur = cur0 ^ ((ask - 1) & 1);
+                const hipError_t fe = enqueue_spec_flush(s, G, gen + ask - 1, 0);
+                if (fe != hipSuccess) return fail(ctx, WA_ERR_DEVICE, "wa_acs_run: flush of a whole window: %s", hipGetErrorString(fe));
+                s->gens_enqueued += ask;
+                s->conv_host[1] += (uint64_t)(ask - 1);
+                g += ask - 1;
+                s->conv_owed_info[2]++;
+                continue;
+            }
+            G.cur = cur0;
+            s->conv_host[2]++;
+            s->conv_prev_whole = false;
+        } else if (ask && s->conv_spec && s->conv_prev_whole && s->conv_wait_us > 0) {
             // The search's last window committed whole: this one will, most likely.  Its flush -- the launches of generation gen+ask-1 -- goes directly behind
             // it, marked speculative, in place of generation gen's launches; the buffers are flipped as the ask-1 generations in front of it would have.
             WaGroupRun &G = groups[0];
@@ -1316,8 +1379,11 @@ int wa_acs_run(wa_acs *s, int32_t n_generations)
             s->conv_host[2]++;
             s->conv_prev_whole = false;
         }
+        const bool walked = gen == s->conv_walk_done;   // (its walk launch went out in front of the verdict, and ran)
+        if (walked) s->conv_walk_done = -1;
         for (int32_t k = 0; k < NG; k++)
-            enqueue_generation(s, groups[(size_t)k], gen, g + 1 == n_generations, sampled, fused, chunks, shmem, P, owed);
+            enqueue_generation(s, groups[(size_t)k], gen, g + 1 == n_generations, sampled, fused, chunks, shmem, P, owed, owed && cwalk ? WA_GEN_OWED : 0,
+                               walked ? WA_PART_REST : WA_PART_ALL);
         s->gens_enqueued++;
         if (ask) {
             // Generation gen's launches (a full generation, the flush or launches that return at once, whichever the device finds) are behind the window: the
@@ -1731,6 +1797,27 @@ int wa_acs_converged_owed_info(wa_acs *s, uint64_t out[5])
 {
     if (!s || !out) return WA_ERR_ARG;
     for (int i = 0; i < 5; i++) out[i] = s->conv_owed_info[i];
+    return WA_OK;
+}
+// The carried walk (WA_CONVERGED_CARRIED_WALK; where owed evaporations apply, all zero otherwise): [0] walk launches that took the carried path (counted
+// on the device), [1] rows launches of carried windows that were not enqueued, [2] walk launches enqueued in front of their window's verdict, [3] of
+// [2], those that were cancelled (the window was cut, or whole but not carried).  Waits for the work enqueued so far.
+int wa_acs_converged_carried_info(wa_acs *s, uint64_t out[4])
+{
+    WaDevGuard dev_guard_(s ? s->ctx : nullptr);
+    if (!dev_guard_.ok) return WA_ERR_DEVICE;
+    if (!s || !out) return WA_ERR_ARG;
+    wa_ctx *ctx = s->ctx;
+    out[0] = 0;
+    for (int i = 1; i < 4; i++) out[i] = s->conv_cwalk_info[i];
+    if (!s->d_conv) return WA_OK;
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    for (int32_t q = 0; q < s->n_slots; q++) {
+        WaConvHdr h;
+        HIPC(ctx, hipMemcpyAsync(&h, s->d_conv + (int64_t)q * s->D.conv_stride, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+        HIPC(ctx, hipStreamSynchronize(ctx->stream));
+        out[0] += h.walks;
+    }
     return WA_OK;
 }
 int wa_acs_converged_host_info(wa_acs *s, uint64_t out[4])

@@ -217,7 +217,10 @@ struct wa_acs {
     int32_t conv_owed_gen = -1;          // the generation whose launches carry WA_GEN_OWED (the one behind a carried window), -1: none
     int32_t conv_owed_reps = 0;          // multiplications its sweep applies (the window's length + 1)
     uint64_t conv_owed_info[5] = {0, 0, 0, 0, 0};   // wa_acs_converged_owed_info
-    bool conv_prev_whole = false;        // the last window of the running search whose verdict was read committed whole
+    bool conv_cwalk = true;              // WA_CONVERGED_CARRIED_WALK (read at creation): a carried window gets no rows launch, the walk behind it replays without the table
+    int32_t conv_walk_done = -1;         // the generation whose walk launch went out ahead of the verdict and ran (its other two launches follow), -1: none
+    uint64_t conv_cwalk_info[4] = {0, 0, 0, 0};   // wa_acs_converged_carried_info: [1] rows launches not enqueued, [2] / [3] speculative walks enqueued / cancelled
+    bool conv_prev_whole = false;       // the last window of the running search whose verdict was read committed whole
 };
 
 static int fail(wa_ctx *c, int code, const char *fmt, const char *a = "", const char *b = "")
