@@ -1155,10 +1155,13 @@ __global__ __launch_bounds__(64) void k_walk_dev(WaAcsDev D, WaRun R, int hash_l
     gen &= ~WA_GEN_FLAGS;
     if (gen < c->spec_until) return;   // a committed generation (acs_converged.hpp): ants and resume blocks alike have nothing to do
     const int32_t colony = c->colony[gen & 1];
-    if (!SPARSE && ALPHA1 && (gflags & WA_GEN_OWED)) {
+    if (!SPARSE && (gflags & WA_GEN_OWED)) {
         // ---- the generation behind a CARRIED window (WA_GEN_OWED on the walk launch, acs_dev.hpp): the window kernel has tested every ant of this
         // generation against the rows of its last snapshot and none leaves the path, so every ant delivers what a whole replay delivers -- without a
-        // draw and without the replay table, whose rows of that snapshot nobody has written.  The launch decides alike in all its blocks (one header)
+        // draw and without the replay table, whose rows of that snapshot nobody has written.  The launch decides alike in all its blocks (one header).
+        // For any alpha: the host marks the launch whatever alpha is (windows run with alpha != 1, their rows follow it), and the replay track of
+        // wa_walk_one delivers the same for every alpha.  The instantiations for alpha != 1 once stepped over this: the walk then read rows nobody
+        // had written, and the launch enqueued ahead of the verdict returned below while the host counted it as run
         if (wa_conv_carried_at(D, slot, gen)) {
             wa_walk_carried(D, slot, ant, colony, c->bestL, c->best_len);
             return;
