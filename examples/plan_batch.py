@@ -587,7 +587,16 @@ def tick_pose_stage(ctx, metal, xyz, limits, tick, omega, h, duration_free):
     return info
 
 
-def weld_pass_stage(ctx, metal, segs, rev, weld_speed, t_start, t_end, limits, tick):
+def jerk_report(ctx, metal, sj, filtered, tick, plain_ticks, plain_time_q, jerk):
+    """what --jerk adds to the JSON: the summary of wa_traj_retime_jerk, the filtered duration against the unfiltered one and the
+    clearance check of the filtered ticks"""
+    return dict(sj, jerk_limit=jerk, jerk_bound=2.0 * sj["in_max_d2"] / sj["window"] / api.RETIME_Q / tick ** 3,
+                max_jerk=sj["max_d3"] / api.RETIME_Q / tick ** 3, duration_s=(sj["n_ticks"] - 1) * tick,
+                unfiltered_duration_s=plain_time_q / api.RETIME_Q, unfiltered_n_ticks=plain_ticks,
+                ticks_clearance=filtered.clearance(metal)[3] if filtered is not None else None)
+
+
+def weld_pass_stage(ctx, metal, segs, rev, weld_speed, t_start, t_end, limits, tick, jerk=None):
     """Weld passes in the timed trajectory (--seams --weld-passes): the stitched polyline as it stands -- segs alternates seams and the
     travel between them, each walked in its tour direction -- cut into steps of at most half the grid precision, the sample at both
     ends of every seam doubled.  The doubled sample at a seam's entry is a stop of t_start seconds (strike the arc), the one at its
@@ -630,8 +639,19 @@ def weld_pass_stage(ctx, metal, segs, rev, weld_speed, t_start, t_end, limits, t
     xyz = np.concatenate(parts)
     dwell, tag = np.asarray(dwell, np.float64), np.asarray(tag, np.uint8)
     curve = api.Trajectory.from_points(ctx, xyz)
-    time_q, w_q, _, ticks, rs, ss = curve.retime_stops(v_max, acc, dec, tick, dwell=dwell, a_lat=a_lat, grid=metal, v_near=v_near,
-                                                       near_d2=int(near_d2), v_limit=np.asarray(vlim, np.float32))
+    kw = dict(dwell=dwell, a_lat=a_lat, grid=metal, v_near=v_near, near_d2=int(near_d2), v_limit=np.asarray(vlim, np.float32))
+    if jerk is not None:   # the same passes through the moving average: its ticks, its tags; the timing reported is the underlying profile's
+        _, _, _, _, plain, _ = curve.retime_stops(v_max, acc, dec, tick, ticks=False, **kw)
+        time_q, w_q, _, ticks, _, tags, rs, ss, sj = curve.retime_jerk(v_max, acc, dec, tick, api.jerk_window(acc, dec, jerk, tick),
+                                                                       seg_tag=tag, **kw)
+        weld_q = int(np.diff(time_q)[tag != 0].sum())
+        return dict(n_stops=ss["n_stops"], dwell_s=ss["dwell_q"] / api.RETIME_Q, weld_s=weld_q / api.RETIME_Q,
+                    travel_s=(rs["time_q"] - weld_q - ss["dwell_q"]) / api.RETIME_Q, duration_s=rs["time_q"] / api.RETIME_Q,
+                    n_ticks=sj["n_ticks"], weld_ticks=int((tags != 0).sum()) if tags is not None else None,
+                    ticks_clearance=ticks.clearance(metal)[3] if ticks is not None else None, samples=len(xyz), seam_length=seam_length,
+                    weld_speed=weld_speed, t_start_s=t_start, t_end_s=t_end, tick_s=tick,
+                    jerk=jerk_report(ctx, metal, sj, ticks, tick, plain["n_ticks"], plain["time_q"], jerk))
+    time_q, w_q, _, ticks, rs, ss = curve.retime_stops(v_max, acc, dec, tick, **kw)
     q = np.tile(np.array([0, 0, 16384], np.int32), (len(xyz), 1))
     _, _, _, _, ts = curve.tick_axes_stops(q, time_q, w_q, acc, dec, tick, seg_tag=tag, axes=False, blocked=False)
     weld_q = int(np.diff(time_q)[tag != 0].sum())
@@ -697,6 +717,10 @@ def main():
     ap.add_argument("--seams", action="store_true",
                     help="points 2k and 2k+1 are the two ends of weld seam k: order AND direction of the seams by wa_gtsp_seam_tour, started from "
                          "the seam-level ACS-TSP tour; the exact tour beside it up to 16 seams")
+    ap.add_argument("--jerk", type=float, default=None, metavar="J",
+                    help="--retime, or --seams --weld-passes: jerk-limited controller ticks (wa_traj_retime_jerk): a moving average along the arc "
+                         "length over the window that bounds the jerk by J (coordinate units per s^3), caps lowered over its reach, dwells "
+                         "extended; reported under jerk")
     ap.add_argument("--weld-passes", type=float, nargs=3, default=None, metavar=("V", "T_START", "T_END"),
                     help="--seams: time the stitched polyline with the weld passes in it (wa_traj_retime_stops): the torch stops T_START seconds "
                          "where it enters a seam, welds at no more than V, stops T_END seconds where it leaves; --retime-limits and "
@@ -811,6 +835,13 @@ def main():
         ap.error("--fit needs the waypoints of --shortcut")
     if args.seams and (args.points % 2 or args.points < 2):
         ap.error("--seams needs an even number of --points (two per seam)")
+    if args.jerk is not None:
+        if args.tick_poses is not None:
+            ap.error("--jerk does not go together with --tick-poses yet: the torch axes at filtered ticks are not built")
+        if not args.retime and args.weld_passes is None:
+            ap.error("--jerk needs --retime, or --seams --weld-passes")
+        if not (args.jerk > 0 and np.isfinite(args.jerk)):
+            ap.error("--jerk takes a jerk limit > 0")
     if args.seams and (args.fit is not None or args.retime):
         ap.error("--seams does not go together with --fit / --retime yet (--weld-passes times a tour of seams)")
     seam_rules = parse_seam_rules(ap, args)
@@ -1007,14 +1038,21 @@ def main():
         if args.weld_passes is not None:
             t6 = time.perf_counter()
             out.update(weld_passes=weld_pass_stage(ctx, metal, wsegs if args.shortcut else segs, rev, *args.weld_passes, args.retime_limits,
-                                                   args.retime_tick),
+                                                   args.retime_tick, args.jerk),
                        t_weld_passes_s=time.perf_counter() - t6)
         if args.retime:
             # what the controller is sent: the same curve at a fixed period, as fast as the limits allow
             t3 = time.perf_counter()
             v_max, acc, dec, a_lat, v_near, near_d2 = args.retime_limits
             curve = api.Trajectory.from_points(ctx, traj[ok.astype(bool)])
-            _, _, _, ticks, rs = curve.retime(v_max, acc, dec, args.retime_tick, a_lat=a_lat, grid=metal, v_near=v_near, near_d2=int(near_d2))
+            kw = dict(a_lat=a_lat, grid=metal, v_near=v_near, near_d2=int(near_d2))
+            if args.jerk is not None:   # (the retime entry describes the underlying profile, the jerk entry the ticks)
+                _, _, _, _, plain = curve.retime(v_max, acc, dec, args.retime_tick, ticks=False, **kw)
+                _, _, _, ticks, _, _, rs, _, sj = curve.retime_jerk(v_max, acc, dec, args.retime_tick,
+                                                                    api.jerk_window(acc, dec, args.jerk, args.retime_tick), **kw)
+                out.update(jerk=jerk_report(ctx, metal, sj, ticks, args.retime_tick, plain["n_ticks"], plain["time_q"], args.jerk))
+            else:
+                _, _, _, ticks, rs = curve.retime(v_max, acc, dec, args.retime_tick, **kw)
             out.update(retime=dict(duration_s=rs["time_q"] / api.RETIME_Q, length=rs["length_q"] / api.RETIME_Q, n_ticks=rs["n_ticks"],
                                    tick_s=args.retime_tick, peak_speed=float(np.sqrt(rs["peak_w_q"] / api.RETIME_Q)),
                                    n_bound=dict(zip(("end", "v_max", "curvature", "clearance"), rs["n_bound"])),

@@ -1312,7 +1312,8 @@ int wa_grid_pose_fit_trajectory(const wa_grid *g, const wa_traj *poly, int32_t d
  *     axes: in a wide turn the interpolated axis of rule 41 moves faster in the middle of the dwell than at its ends; max_dwell_turn
  *     shows by how much, and a caller who minds inserts intermediate samples (more, smaller turns).  n is 1 .. 2^31.
  * Every WA_ERR_ARG is answered before anything is written.  Same bytes on every call; everything runs on the context's stream; g and
- * t are not modified.  Not covered: stops on segments that have a length, a jerk limit, angular acceleration, slerp. */
+ * t are not modified.  Not covered: stops on segments that have a length, angular acceleration, slerp.  (A jerk limit:
+ * wa_traj_retime_jerk, rules 48 - 55 at the end of this header.) */
 typedef struct {
     int64_t n_stops, n_stop_samples, dwell_q;
 } wa_stops_summary;
@@ -1388,6 +1389,66 @@ int wa_grid_pose_diag_paths(const wa_grid *g, const float *dirs, int32_t K, cons
                             const wa_pose_diag_costs *costs, const int64_t *start_ids, const int64_t *end_ids, const int32_t *pin_start,
                             const int32_t *pin_end, int32_t n_pairs, const int64_t *off, int64_t *ids_out, int32_t *dir_out,
                             int32_t *cost_out, int32_t *len_out);
+
+/* ---- jerk-limited controller ticks: a moving average along the arc length (not in the reference) ----
+ *      The profile of wa_traj_retime / wa_traj_retime_stops is bang-bang: where a ramp meets a cap the acceleration jumps by up to
+ *      acc + dec within one tick.  wa_traj_retime_jerk averages the last W ticks, not in x, y and z but in the ARC LENGTH, so the torch
+ *      stays on the polyline that wa_traj_clearance and the fit stages proved clear, and the third difference of the arc length is
+ *      bounded by 2 / W of the second difference the unfiltered ticks have.  An average carries speed into slow zones and eats the
+ *      first W - 1 ticks of a dwell: the caps are lowered over the distance a window can span before the profile is computed, and the
+ *      dwells are extended.  The rules continue the numbering above; Q = 2^30, tick_q, ds_i, L_i, A_i, D_i, the caps and kinds are those
+ *      of the retime section ("retime rule k"), stops and dq_i those of rule 40.  GL = the exclusive prefix sum of L (n entries),
+ *      length_q = GL_(n-1).  Integers and individually rounded doubles only.
+ * 48. Window and reach.  window = W, 1 .. 2^20 ticks.  step_q = (int64)floor((v_max * tick) * Q) + 1, R_q = (W - 1) * step_q: the farthest the
+ *     W ticks of one window can lie apart.  WA_ERR_ARG before anything is written: W out of range, R_q >= 2^61, (W - 1) * tick_q >= 2^61, a
+ *     dq_i + (W - 1) * tick_q >= 2^61, W * length_q >= 2^62, tag_out without seg_tag, a NULL stops or jerk, and everything retime rule 7 and
+ *     rule 40 refuse.
+ * 49. Lowered caps.  For EVERY sample, end points and stop samples included, cap13_j = retime rule 2's minimum over the kinds 1 - 3 only,
+ *     with its kind; C13_j its quanta by retime rule 2's floor.  The window of sample j is every sample m with
+ *     GL_max(j-1, 0) - R_q <= GL_m <= GL_min(j+1, n-1) + R_q.  C'_j = the minimum of C13 over the window, its kind the lowest-numbered kind
+ *     among the window's samples that attain it.  With R_q = 0 nothing is lowered: C' = C13.  Retime rule 2's kind 0 is then applied as
+ *     ever: samples 0 and n-1 and both samples of every stop get cap 0.  bound_out gains bit 6: C'_j < C13_j, the cap was lowered.
+ *     (The neighbours j-1 and j+1 belong to the interval because a filtered tick on segment i averages speeds taken on every segment
+ *     that meets [GL_i - R_q, GL_(i+1) + R_q], the speed on a segment is bounded by the caps at both of its ends, and with this window at
+ *     least one of C_i and C_(i+1) lies in the window of each of those ends.  [GL_j - R_q, GL_j + R_q] alone is not enough where samples
+ *     lie farther apart than R_q.)
+ * 50. Extended dwells.  On a stop dq'_i = dq_i + (W - 1) * tick_q.  stops->dwell_q reports the caller's own sum.
+ * 51. The underlying profile.  Retime rules 3 - 5 and rule 40 on (C', dq') give B, bound, T and time_q: what time_q_out, w_q_out and
+ *     bound_out return and *sum describes (sum->n_ticks = n_u of rule 52).  With W = 1 they are the bytes of wa_traj_retime_stops.
+ * 52. Unfiltered arc lengths.  n_u = retime rule 6's tick count on that profile; for k = 0 .. n_u - 1 tau_k = min(k * tick_q, duration), i
+ *     and lambda retime rule 6's for tau_k, U_k = GL_i + x with x = L_i if the tick is p_(i+1) exactly, 0 if L_i = 0, else
+ *     (int64)rint(lambda * (double)L_i).  U_k = 0 for k < 0 and length_q for k >= n_u.
+ * 53. The filter.  n_ticks = n_u + W - 1; S_k = floor((U_k + U_(k-1) + ... + U_(k-W+1)) / W) for k = 0 .. n_ticks - 1; s_q_out[k] = S_k (the
+ *     last one is length_q).  More than 2^31 output ticks: WA_ERR_CAPACITY as in retime rule 7, with the summaries and the per-sample
+ *     outputs filled, the tick fields of *jerk (max_d1 .. n_back) 0 and *ticks_out = NULL.
+ * 54. Where a tick lies.  (a) Rest tick: if some stop segment i has GL_i = S_k, the tick takes the lowest-numbered such stop, sits at p_i
+ *     and carries seg_tag[i]: stops in a row act as one stop with the sum of their dwells and the first one's tag.  (b) Otherwise
+ *     i = the largest index in 0 .. n-2 with GL_i <= S_k; if S_k >= GL_(i+1) the tick is p_(i+1); else if L_i = 0 it is p_i; else
+ *     lambda = (double)(S_k - GL_i) / (double)L_i and the position retime rule 6's per-axis expression.  tag_out[k] = seg_tag[i].
+ * 55. wa_jerk_summary.  window, reach_q = R_q; n_lowered = samples with bit 6; n_in = n_u, n_ticks; max_d1, max_d2, max_d3 = the largest
+ *     absolute first, second and third difference of S (quanta per tick, tick^2, tick^3); in_max_d2 = the largest absolute second
+ *     difference of U over k = -W .. n_u + W; n_rest_ticks; n_short_rests = groups of stops sharing one GL whose rest ticks number
+ *     fewer than floor(sum of their dq / tick_q); n_back = steps with S_(k+1) < S_k.  Property: max_d3 <= 2 * in_max_d2 / W + 4.
+ * wa_traj_jerk_window: W = max(1, ceil((2 * max(acc, dec)) / (jerk * tick))), the window that bounds the jerk along the path by `jerk`;
+ * WA_ERR_ARG for an argument that is not finite and > 0, a NULL window_out, a W above 2^20.  Host only; t may be NULL and is not read: like
+ * every wa_traj_ call it takes the trajectory first, whose context receives the error text.
+ * time_q_out, w_q_out, bound_out (n entries, host), ticks_out (a device-resident wa_traj of the filtered positions, owned by the
+ * caller), s_q_out (int64 per output tick, host), tag_out (one byte per output tick, host), dwell, v_limit, seg_tag (n - 1 bytes, host)
+ * and g may be NULL; s_q_out and tag_out hold jerk->n_ticks entries, which a call without them reports.  Same bytes on every call; everything runs on the context's stream; g and t are not modified.  The range minima of
+ * rule 49 take 8 * n bytes per power of two in the widest window; WA_ERR_ALLOC where that cannot be had.  Not covered: torch axes at
+ * filtered ticks, a reach tighter than rule 48's, cascaded windows (a bound on the snap), per-stop tags for stops in a row. */
+typedef struct {
+    int64_t window, reach_q, n_lowered, n_in, n_ticks;
+    int64_t max_d1, max_d2, max_d3, in_max_d2;
+    int64_t n_rest_ticks, n_short_rests, n_back;
+} wa_jerk_summary;
+int wa_traj_retime_jerk(const wa_grid *g, const wa_traj *t, const wa_retime_limits *lim, const float *v_limit,
+                        const double *dwell /* n-1, host, may be NULL */, double tick, int32_t window,
+                        const uint8_t *seg_tag /* n-1, host, may be NULL */,
+                        int64_t *time_q_out, int64_t *w_q_out, uint8_t *bound_out, wa_traj **ticks_out,
+                        int64_t *s_q_out /* n_ticks, host, may be NULL */, uint8_t *tag_out /* n_ticks, host, may be NULL */,
+                        wa_retime_summary *sum, wa_stops_summary *stops, wa_jerk_summary *jerk);
+int wa_traj_jerk_window(const wa_traj *t /* may be NULL */, double acc, double dec, double jerk, double tick, int32_t *window_out);
 
 #ifdef __cplusplus
 }

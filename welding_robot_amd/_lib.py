@@ -140,6 +140,12 @@ class AxesDwellsSummary(C.Structure):
     _fields_ = [("n", C.c_int64), ("n_jump", C.c_int64), ("n_stops", C.c_int64), ("n_raised", C.c_int64), ("max_need", C.c_double)]
 
 
+class JerkSummary(C.Structure):
+    _fields_ = [("window", C.c_int64), ("reach_q", C.c_int64), ("n_lowered", C.c_int64), ("n_in", C.c_int64), ("n_ticks", C.c_int64),
+                ("max_d1", C.c_int64), ("max_d2", C.c_int64), ("max_d3", C.c_int64), ("in_max_d2", C.c_int64),
+                ("n_rest_ticks", C.c_int64), ("n_short_rests", C.c_int64), ("n_back", C.c_int64)]
+
+
 WA_PEN_MAX = 31
 
 # every symbol include/weldacs.h declares: name -> (restype, argtypes)
@@ -293,6 +299,9 @@ SYMBOLS = {
     "wa_traj_tick_axes_stops": (C.c_int, [_V, _V, _P, C.POINTER(ToolBeads), _I, C.c_double, C.c_double, C.c_double, _P, _P, _P, C.POINTER(_V), _P,
                                           _P, C.POINTER(TickAxesSummary), C.POINTER(TickStopsSummary)]),
     "wa_traj_axes_dwells": (C.c_int, [_V, _P, C.c_double, _P, _P, C.POINTER(AxesDwellsSummary)]),
+    "wa_traj_retime_jerk": (C.c_int, [_V, _V, C.POINTER(RetimeLimits), _P, _P, C.c_double, _I, _P, _P, _P, _P, C.POINTER(_V), _P, _P,
+                                      C.POINTER(RetimeSummary), C.POINTER(StopsSummary), C.POINTER(JerkSummary)]),
+    "wa_traj_jerk_window": (C.c_int, [_V, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int32)]),
 }
 
 _libs = {}

@@ -1147,6 +1147,52 @@ class Trajectory:
         summary = {k: (list(getattr(s, k)) if k == "n_bound" else int(getattr(s, k))) for k, _ in L.RetimeSummary._fields_}
         return time_q, w_q, bound, Trajectory(self.ctx, th) if th.value else None, summary, {k: int(getattr(s2, k)) for k, _ in L.StopsSummary._fields_}
 
+    def retime_jerk(self, v_max, acc, dec, tick, window, dwell=None, seg_tag=None, a_lat=float("inf"), grid=None, v_near=0.0, near_d2=-1,
+                    v_limit=None, ticks=True, s_q=False, tags=None):
+        """wa_traj_retime_jerk: retime_stops() whose ticks are a moving average of `window` ticks along the arc length (jerk_window()
+        sizes it from a jerk limit).  The torch stays on the polyline, the caps are lowered over the window's reach before the profile is
+        computed and every dwell keeps its full number of rest ticks.  seg_tag: one byte per segment, carried to the ticks with
+        tags=True (the default when seg_tag is given); s_q=True also returns the filtered arc length per tick (quanta of 2^-30).
+        Returns (time_q, w_q, bound, ticks Trajectory or None, s_q int64 or None, tags uint8 or None, summary, stops dict, jerk dict);
+        the per-sample outputs and `summary` describe the underlying profile.  The host arrays s_q and tags are sized by a first
+        call without outputs (the same bytes on every call)."""
+        n = len(self)
+        lim = L.RetimeLimits(v_max, acc, dec, a_lat, v_near, near_d2)
+        if v_limit is not None:
+            v_limit = np.ascontiguousarray(v_limit, np.float32).reshape(-1)
+            if len(v_limit) != n:
+                raise ValueError("v_limit needs one entry per sample")
+        dwell = self._dwells(dwell, "dwell")
+        if seg_tag is not None:
+            seg_tag = np.ascontiguousarray(seg_tag, np.uint8).reshape(-1)
+            if len(seg_tag) != n - 1:
+                raise ValueError("seg_tag needs one entry per segment")
+        tags = seg_tag is not None if tags is None else tags
+        if tags and seg_tag is None:
+            raise ValueError("tags need seg_tag")
+        g = grid.h if grid is not None else None
+        s, s2, s3 = L.RetimeSummary(), L.StopsSummary(), L.JerkSummary()
+
+        def call(time_q, w_q, bound, th, sq, tg):
+            rc = self.ctx.lib.wa_traj_retime_jerk(g, self.h, C.byref(lim), _ptr(v_limit), _ptr(dwell), C.c_double(tick), int(window),
+                                                  _ptr(seg_tag), _ptr(time_q), _ptr(w_q), _ptr(bound), C.byref(th) if th is not None else None,
+                                                  _ptr(sq), _ptr(tg), C.byref(s), C.byref(s2), C.byref(s3))
+            if rc != 7:   # WA_ERR_CAPACITY: everything but the ticks is there
+                self.ctx.check(rc)
+            return rc
+
+        sq = tg = None
+        if s_q or tags:
+            if call(None, None, None, None, None, None) == 0:
+                sq = np.empty(int(s3.n_ticks), np.int64) if s_q else None
+                tg = np.empty(int(s3.n_ticks), np.uint8) if tags else None
+        time_q, w_q, bound = np.empty(n, np.int64), np.empty(n, np.int64), np.empty(n, np.uint8)
+        th = C.c_void_p()
+        call(time_q, w_q, bound, th if ticks else None, sq, tg)
+        summary = {k: (list(getattr(s, k)) if k == "n_bound" else int(getattr(s, k))) for k, _ in L.RetimeSummary._fields_}
+        return (time_q, w_q, bound, Trajectory(self.ctx, th) if th.value else None, sq, tg, summary,
+                {k: int(getattr(s2, k)) for k, _ in L.StopsSummary._fields_}, {k: int(getattr(s3, k)) for k, _ in L.JerkSummary._fields_})
+
     def axis_dwells(self, q, omega, dwell=None):
         """wa_traj_axes_dwells: the dwell every change of direction on a segment without length needs at the turn rate `omega` (chord of
         the unit axes per second), never below the caller's own `dwell` there.  Returns (float64[n-1] for retime_stops(dwell=...),
@@ -1382,6 +1428,16 @@ def seam_rules_check(order, dirs, before=None, after=None, fixed=None, closed=Tr
     if rc:
         raise ValueError("wa_gtsp_seam_rules_check: the rules or the tour are not well-formed (status %d)" % rc)
     return int(bad_p.value), int(bad_d.value)
+
+
+def jerk_window(acc, dec, jerk, tick):
+    """wa_traj_jerk_window (host only): the window, in ticks, of Trajectory.retime_jerk that bounds the jerk along the path by `jerk`
+    under the ramps acc / dec: max(1, ceil(2 * max(acc, dec) / (jerk * tick)))"""
+    w = C.c_int32(0)
+    rc = L.load().wa_traj_jerk_window(None, C.c_double(acc), C.c_double(dec), C.c_double(jerk), C.c_double(tick), C.byref(w))
+    if rc:
+        raise ValueError("wa_traj_jerk_window: acc, dec, jerk and tick must be finite and > 0, the window at most 2^20 ticks (status %d)" % rc)
+    return int(w.value)
 
 
 TORCH_INF = L.TORCH_INF   # leg cost of a one-sample leg whose two pins differ (wa_traj_tool_axes, rule 5)

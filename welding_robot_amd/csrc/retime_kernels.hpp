@@ -125,7 +125,9 @@ struct WaRtLimits {
 // Rule 2.  The voxel of a sample is found by field_voxel, the lookup k_clr_samples runs; a call without a grid passes a zeroed view.
 // STOPS (wa_traj_retime_stops, stops_kernels.hpp): dq holds the dwell of every segment in quanta, -1 where the segment is no stop; both
 // samples of a stop get the kind-0 cap of the end points.
-template <bool STOPS>
+// KEYS (wa_traj_retime_jerk, jerk_kernels.hpp): kinds 1 - 3 only, for every sample, and C takes the pair as ONE unsigned 64-bit key
+// C * 4 + kind (kind is not written): the smallest key of a range is its smallest cap with the lowest-numbered kind attaining it.
+template <bool STOPS, bool KEYS = false>
 __device__ __forceinline__ void rt_caps(const float *__restrict__ xyz, long long n, const WaRtLimits &lim, const float *__restrict__ v_limit,
                                         const WaField &F, long long *__restrict__ C, uint8_t *__restrict__ kind, WaRtRec *__restrict__ rec,
                                         const long long *__restrict__ dq)
@@ -163,11 +165,16 @@ __device__ __forceinline__ void rt_caps(const float *__restrict__ xyz, long long
                 if (k3 < cap) { cap = k3; k = 3; }
             }
         }
-        if (i == 0 || i == n - 1) { cap = 0.0; k = 0; }
+        if (!KEYS && (i == 0 || i == n - 1)) { cap = 0.0; k = 0; }
         if (STOPS && ((i > 0 && dq[i - 1] >= 0) || (i < n - 1 && dq[i] >= 0))) { cap = 0.0; k = 0; }
         const double q = cap * WA_RT_Q;
-        C[i] = !(q < (double)WA_RT_CAP) ? WA_RT_CAP : (long long)floor(q);
-        kind[i] = (uint8_t)k;
+        const long long cq = !(q < (double)WA_RT_CAP) ? WA_RT_CAP : (long long)floor(q);
+        if (KEYS) {
+            C[i] = (long long)((unsigned long long)cq * 4ull + (unsigned long long)k);
+        } else {
+            C[i] = cq;
+            kind[i] = (uint8_t)k;
+        }
     }
     outs = rt_wave_sum(outs);
     if ((threadIdx.x & 63) == 0 && outs) atomicAdd(&rec->n_outside, outs);

@@ -47,6 +47,7 @@
 #include "pose_fit_kernels.hpp"
 #include "ticks_kernels.hpp"
 #include "stops_kernels.hpp"
+#include "jerk_kernels.hpp"
 #include "stl_text.hpp"
 #include "acs_plan.hpp"
 
@@ -1030,6 +1031,7 @@ void *wa_ctx_stream(wa_ctx *c) { return c ? (void *)c->stream : nullptr; }
 #include "host_chamfer_weighted.inc"
 #include "host_fit.inc"
 #include "host_retime.inc"
+#include "host_jerk.inc"
 #include "host_seamtour.inc"
 #include "host_seamrules.inc"
 #include "host_torch.inc"
