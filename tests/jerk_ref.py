@@ -8,6 +8,8 @@ unfiltered profile promised: the caps of kinds 1 - 3 are lowered to their minimu
 profile is computed, and every dwell is extended by the W - 1 ticks the window eats.
 
 `lower=False` is a switch for the tests alone: it sets R_q = 0, which skips the lowering."""
+import bisect
+
 import numpy as np
 
 import retime_ref as R
@@ -85,10 +87,11 @@ def arcs(xyz, L, GL, time_q, B, acc, dec, tick_q):
 
 def window_means(U, W, length_q):
     """rule 53: S_k = floor((U_k + ... + U_(k-W+1)) / W) for k = 0 .. n_u + W - 2, U = 0 in front and length_q behind; the window sums
-    are differences of prefix sums modulo 2^64 (exact, since W * length_q < 2^62)"""
+    are differences of prefix sums modulo 2^64 (exact, since W * length_q < 2^62).  The prefix array is uint64 from its first element:
+    a Python 0 in front makes numpy promote the whole array to float64, which drops the low bits of every sum above 2^53."""
     n_u = len(U)
     with np.errstate(over="ignore"):
-        P = np.concatenate([[0], np.cumsum(U.astype(np.uint64), dtype=np.uint64)]).astype(np.uint64)
+        P = np.concatenate([np.zeros(1, np.uint64), np.cumsum(U.astype(np.uint64), dtype=np.uint64)])
         k = np.arange(n_u + W - 1, dtype=np.int64)
         s = P[np.minimum(k, n_u - 1) + 1] - P[np.maximum(k - W + 1, 0)] + (np.maximum(k - n_u + 1, 0) * np.int64(length_q)).astype(np.uint64)
     return (s // np.uint64(W)).astype(np.int64)
@@ -257,15 +260,16 @@ def retime_jerk_scalar(xyz, lim, dwell=None, window=1, v_limit=None, grid=None, 
     u_at = lambda k: 0 if k < 0 else (length_q if k >= n_u else U[k])
     s_q, segs, rests, tags = [], [], [], []
     pos = np.empty((n_u + W - 1, 3), np.float32)
+    stops = [i for i in range(n - 1) if stop[i]]
     for k in range(n_u + W - 1):
         s = sum(u_at(j) for j in range(k - W + 1, k + 1)) // W
         s_q.append(s)
-        hit = [i for i in range(n - 1) if stop[i] and GL[i] == s]
+        hit = [i for i in stops if GL[i] == s]
         if hit:
             i = hit[0]
             pos[k] = p32[i]
         else:
-            i = max(m for m in range(n - 1) if GL[m] <= s)
+            i = min(bisect.bisect_right(GL, s), n - 1) - 1   # (the last segment m with GL[m] <= s; GL never falls)
             if s >= GL[i + 1]:
                 pos[k] = p32[i + 1]
             elif L[i] == 0:
