@@ -182,8 +182,8 @@ if "c" in only:
     xyz = np.stack([t * 0.05, 0.3 * np.sin(t), 0.2 * np.cos(0.037 * t * t)], 1).astype(np.float32)
     s, ms = compare("c", api.Trajectory.from_points(ctx, xyz), (0.8, 1.0, 1.5, 0.6, 0.0, -1.0), 0.001)
     # bytes the kernels must move, from the arrays of rules 1 - 6 (int64 unless said; xyz 12 B, kind / bound 1 B per sample):
-    per_sample = {"k_rt_segments": 12 + 16, "k_rt_caps": 12 + 8 + 1, "k_rt_scan forward (reduce + add)": 2 * 16 + 8,
-                  "k_rt_scan backward (reduce + add)": 2 * 16 + 8, "k_rt_times": 12 + 4 * 8 + 1 + 1 + 8, "k_rt_scan times (reduce + add)": 2 * 8 + 8}
+    per_sample = {"k_rt_segments": 12 + 16, "k_rt_caps": 12 + 8 + 1, "k_scan forward (reduce + add)": 2 * 16 + 8,
+                  "k_scan backward (reduce + add)": 2 * 16 + 8, "k_rt_times": 12 + 4 * 8 + 1 + 1 + 8, "k_scan times (reduce + add)": 2 * 8 + 8}
     total = n * sum(per_sample.values()) + s["n_ticks"] * (12 + 12 + 3 * 8) + n * (8 + 8 + 1)
     for k, v in per_sample.items():
         print("    %-36s %6.1f MB" % (k, n * v / 1e6))

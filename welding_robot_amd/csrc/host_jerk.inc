@@ -71,7 +71,7 @@ static int jk_caps(wa_ctx *ctx, const wa_traj *t, const WaRtLimits &dl, const fl
     if (e != hipSuccess) return fail(ctx, WA_ERR_ALLOC, "wa_traj_retime_jerk: device buffers");
     e = hipMemsetAsync(J.rec, 0, sizeof(WaJkRec), ctx->stream);
     const JkLengths len = {t->xyz, J.GL, n};
-    e = e ? e : rt_scan(ctx->stream, len, scratch);
+    e = e ? e : wa_scan(ctx->stream, len, scratch);
     *done = false;
     if (e == hipSuccess && jk.R_q > 0) {
         e = J.key.alloc((size_t)n);
@@ -121,7 +121,7 @@ static int jk_groups(wa_ctx *ctx, long long n, const long long *dq, JerkRun &jk,
         e = hipMemsetAsync(J.need, 0, sizeof(unsigned long long) * n, ctx->stream);
         e = e ? e : hipMemsetAsync(J.rest_cnt, 0, sizeof(unsigned long long) * n, ctx->stream);
         const JkNext nx = {dq, J.next, n};
-        e = e ? e : rt_scan(ctx->stream, nx, scratch);
+        e = e ? e : wa_scan(ctx->stream, nx, scratch);
     }
     if (e == hipSuccess && (jk.any_stop || J.low.p)) {
         k_jk_groups<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(J.GL, n, J.low, dq, J.next, jk.ext, bound, J.need);
@@ -139,7 +139,7 @@ static int jk_ticks(wa_ctx *ctx, const wa_traj *t, double acc, double dec, const
     const long long n = t->n;
     hipError_t e = J.P.alloc((size_t)n_u + 1);
     DevBuf<RtPair> scratch;
-    e = e ? e : scratch.alloc((size_t)rt_scratch_pairs(n_u + 1));
+    e = e ? e : scratch.alloc((size_t)wa_scan_scratch(n_u + 1));
     if (jk.s_q_out) e = e ? e : J.s_q.alloc((size_t)n_out);
     if (jk.tag_out) {
         e = e ? e : J.tag.alloc((size_t)n_out);
@@ -152,7 +152,7 @@ static int jk_ticks(wa_ctx *ctx, const wa_traj *t, double acc, double dec, const
         e = hipGetLastError();
     }
     const RtSamples sums = {J.P, nullptr, J.P, n_u + 1, 0};   // (in place: a lane has read its eight entries before it writes them)
-    e = e ? e : rt_scan(ctx->stream, sums, scratch);
+    e = e ? e : wa_scan(ctx->stream, sums, scratch);
     if (e == hipSuccess) {
         WaJkTicks T;
         T.xyz = t->xyz; T.n = n; T.GL = J.GL; T.next = J.next; T.P = J.P; T.n_u = n_u; T.n_ticks = n_out; T.length_q = length_q;

@@ -25,13 +25,6 @@ struct RetimeBuffers {
     OwnedHandle<wa_traj> ticks;
 };
 
-static long long rt_scratch_pairs(long long n)
-{
-    long long total = 0;
-    for (long long m = (n + WA_RT_TILE - 1) / WA_RT_TILE; m > 1; m = (m + WA_RT_TILE - 1) / WA_RT_TILE) total += m;
-    return total + 1;
-}
-
 static bool rt_sum_fits(const unsigned long long w[2], int64_t *out)
 {
     const unsigned __int128 v = ((unsigned __int128)w[1] << 32) + w[0];
@@ -95,7 +88,7 @@ static int retime_run(const char *who, const wa_grid *g, const wa_traj *t, const
     for (DevBuf<long long> *b : {&R.A, &R.D, &R.C, &R.F, &R.B, &R.T, &R.time_q}) e = e ? e : b->alloc((size_t)n);
     e = e ? e : R.kind.alloc((size_t)n);
     e = e ? e : R.bound.alloc((size_t)n);
-    e = e ? e : R.scratch.alloc((size_t)rt_scratch_pairs(n));
+    e = e ? e : R.scratch.alloc((size_t)wa_scan_scratch(n));
     e = e ? e : R.rec.alloc(1);
     if (v_limit) e = e ? e : R.v_limit.alloc((size_t)n);
     if (with_stops) e = e ? e : R.dq.alloc((size_t)n - 1);
@@ -121,14 +114,14 @@ static int retime_run(const char *who, const wa_grid *g, const wa_traj *t, const
         e = hipGetLastError();
     }
     const RtSamples fwd = {R.A, R.C, R.F, n, 0}, bwd = {R.D, R.F, R.B, n, 1}, tim = {R.T, nullptr, R.time_q, n, 0};
-    e = e ? e : rt_scan(ctx->stream, fwd, R.scratch);
-    e = e ? e : rt_scan(ctx->stream, bwd, R.scratch);
+    e = e ? e : wa_scan(ctx->stream, fwd, R.scratch);
+    e = e ? e : wa_scan(ctx->stream, bwd, R.scratch);
     if (e == hipSuccess) {
         if (with_stops) k_st_times<<<blocks, 256, 0, ctx->stream>>>(t->xyz, n, dl.acc, dl.dec, R.A, R.D, R.C, R.B, R.kind, R.dq, R.bound, R.T, R.rec);
         else k_rt_times<<<blocks, 256, 0, ctx->stream>>>(t->xyz, n, dl.acc, dl.dec, R.A, R.D, R.C, R.B, R.kind, R.bound, R.T, R.rec);
         e = hipGetLastError();
     }
-    e = e ? e : rt_scan(ctx->stream, tim, R.scratch);
+    e = e ? e : wa_scan(ctx->stream, tim, R.scratch);
     if (jk && e == hipSuccess) {
         int rc = jk_groups(ctx, n, R.dq, *jk, R.scratch, R.bound);
         if (rc) return rc;

@@ -85,8 +85,8 @@ int wa_traj_axes_smooth(const wa_grid *g, const wa_traj *t, const int32_t *q, co
     e = e ? e : dL.alloc((size_t)n);
     e = e ? e : dGL.alloc((size_t)n);
     e = e ? e : dP.alloc((size_t)n);
-    e = e ? e : dscr3.alloc((size_t)rt_scratch_pairs(n));
-    e = e ? e : dscr.alloc((size_t)rt_scratch_pairs(n));
+    e = e ? e : dscr3.alloc((size_t)wa_scan_scratch(n));
+    e = e ? e : dscr.alloc((size_t)wa_scan_scratch(n));
     e = e ? e : dlist.alloc((size_t)n);
     if (e != hipSuccess) return fail(ctx, WA_ERR_ALLOC, "wa_traj_axes_smooth: device buffers");
     hipStream_t st = ctx->stream;
@@ -102,8 +102,8 @@ int wa_traj_axes_smooth(const wa_grid *g, const wa_traj *t, const int32_t *q, co
     }
     const RtSamples len = {dL, nullptr, dGL, n, 0};
     const Ax3Samples axes = {dq, dP, n};
-    e = e ? e : rt_scan(st, len, dscr);
-    e = e ? e : ax_scan3(st, axes, dscr3);
+    e = e ? e : wa_scan(st, len, dscr);
+    e = e ? e : wa_scan(st, axes, dscr3);
     WaAxSmooth A;
     A.xyz = t->xyz; A.q = dq; A.GL = dGL; A.P = dP; A.off = doff; A.n = n; A.h_q = h_q; A.n_legs = n_legs; A.max_level = max_level;
     A.check = g ? 1 : 0; A.q_out = dq_out; A.level = dlevel; A.blocked = dblocked; A.list = dlist;

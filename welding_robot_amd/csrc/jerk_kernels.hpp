@@ -4,8 +4,8 @@
 // and the dwells arrive already extended (the host adds (W - 1) * tick_q).  The profile itself is the stops path of retime_run as it
 // stands: k_rt_segments, k_st_caps or the lowering below, the scans, k_st_times.
 //   k_jk_caps     rt_caps<false, true>: kinds 1 - 3 for every sample as one key C * 4 + kind
-//   k_rt_scan     over JkLengths (GL, the minimum ignored), JkNext (the next stop at or after a sample, a suffix minimum) and, through
-//                 RtSamples, over the arc lengths of the unfiltered ticks modulo 2^64, in place
+//   k_scan        (scan_kernels.hpp) over JkLengths (GL, the minimum ignored), JkNext (the next stop at or after a sample, a suffix
+//                 minimum) and, through RtSamples, over the arc lengths of the unfiltered ticks modulo 2^64, in place
 //   k_jk_window   one lane per sample: two binary searches in GL give the index range of rule 49; the widest range goes to the record
 //   k_jk_level    one level of the sparse table of power-of-two minima of the keys
 //   k_jk_lower    one lane per sample: the range minimum by two overlapping loads, C', its kind, the kind-0 caps, the lowered flag
@@ -36,6 +36,7 @@ __global__ __launch_bounds__(256) void k_jk_caps(const float *__restrict__ xyz, 
 
 // GL: element e is sample e, its weight L_e (0 behind the last sample); the result is the exclusive sum.
 struct JkLengths {
+    typedef RtMinSum Op;
     const float *xyz;
     long long *out;
     long long n;
@@ -51,6 +52,7 @@ struct JkLengths {
 // The lowest stop segment at or after sample j (n where there is none): element e is sample n - 1 - e, all weights 0, so the pair's
 // minimum is the plain minimum of what came before -- a suffix minimum of (j if segment j is a stop, else n).
 struct JkNext {
+    typedef RtMinSum Op;
     const long long *dq;
     long long *out;
     long long n;

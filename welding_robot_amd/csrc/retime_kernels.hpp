@@ -2,11 +2,10 @@
 // trajectory (include/weldacs.h states the definition; tests/retime_ref.py restates it in numpy).
 //   k_rt_segments  one lane per segment: its float64 length, L, A, D in quanta of 2^-30; the sums of L, A, D; non-finite coordinates
 //   k_rt_caps      one lane per sample: the smallest of the speed caps (end point, v_max / v_limit, curvature, clearance), its kind
-//   k_rt_scan      the one scan of this file, over pairs (weight, cap) under  (s1, m1) + (s2, m2) = (s1 + s2, min(m1, m2 - s1)):  after
+//   k_scan         (scan_kernels.hpp) over pairs (weight, cap) under  (s1, m1) + (s2, m2) = (s1 + s2, min(m1, m2 - s1)):  after
 //                  sample i the pair holds GA_{i+1} and min_{j <= i} (C_j - GA_j), so F_i = m + GA_i comes out of ONE pass -- the add-scan
-//                  and the min-scan of a direction share every launch.  The backward pass is the same kernel on reversed indices, the
-//                  time scan the same kernel with the minimum ignored.  Device level: reduce (block aggregates) - scan (of the
-//                  aggregates, recursively) - add (block prefixes), with kernel boundaries in between: no workgroup waits for another.
+//                  and the min-scan of a direction share every launch.  The backward pass is the same scan on reversed indices, the
+//                  time scan the same scan with the minimum ignored.
 //   k_rt_times     one lane per sample: bound bits, the segment's time T, the summary's counters
 //   k_rt_ticks     one lane per tick: binary search in time_q, the position on its segment, stores staged through LDS
 // k_rt_caps and k_rt_times are the STOPS == false instantiations of rt_caps / rt_times; stops_kernels.hpp holds the others.
@@ -14,12 +13,11 @@
 // is bit-exact and independent of scheduling; what is accumulated across lanes is an integer.
 #pragma once
 #include "clearance_kernels.hpp"
+#include "scan_kernels.hpp"
 
 #define WA_RT_Q 1073741824.0                // 2^30 quanta per unit
 #define WA_RT_CAP (1ll << 61)               // "no cap"; also the bound every sum must stay below
 #define WA_RT_INF (1ll << 62)               // the scan's neutral minimum
-#define WA_RT_ITEMS 8
-#define WA_RT_TILE (256 * WA_RT_ITEMS)      // elements per workgroup of k_rt_scan
 #define WA_RT_MAX_N (1ll << 31)
 
 // what the host reads once, behind k_rt_times.  Sums that may not reach 2^61 are kept as two words, low 32 bits and the rest, each
@@ -43,6 +41,13 @@ __device__ __forceinline__ RtPair rt_comb(RtPair x, RtPair y)
     r.m = x.m < ym ? x.m : ym;
     return r;
 }
+// the scan's operator (scan_kernels.hpp)
+struct RtMinSum {
+    typedef RtPair T;
+    static __device__ __forceinline__ RtPair id() { return RtPair{0, WA_RT_INF}; }
+    static __device__ __forceinline__ RtPair comb(RtPair x, RtPair y) { return rt_comb(x, y); }
+    static __device__ __forceinline__ RtPair up(RtPair v, int o) { return RtPair{__shfl_up(v.s, o, 64), __shfl_up(v.m, o, 64)}; }
+};
 
 __device__ __forceinline__ unsigned long long rt_sat_add(unsigned long long a, unsigned long long b)   // a, b <= 2^61
 {
@@ -186,11 +191,12 @@ __global__ __launch_bounds__(256) void k_rt_caps(const float *__restrict__ xyz, 
     rt_caps<false>(xyz, n, lim, v_limit, F, C, kind, rec, nullptr);
 }
 
-// ---- the scan.  A source hands out element e = 0 .. n - 1 and takes its result: the exclusive prefix and the element itself.
+// ---- the scan's sources (k_scan, scan_kernels.hpp: a source hands out element e = 0 .. n - 1 and takes its result).
 // Samples: element e is sample e (rev: sample n - 1 - e); its weight is that of the segment towards element e + 1 (0 behind the last
 // one), its cap c[sample].  With c == nullptr the minimum is not used and the result is the exclusive sum; otherwise it is
 // min_{j <= e} (c_j - S_j) + S_e with S the exclusive sums: F of rule 3 going forward, B going backward on F.
 struct RtSamples {
+    typedef RtMinSum Op;
     const long long *w, *c;
     long long *out;
     long long n;
@@ -207,76 +213,6 @@ struct RtSamples {
         out[rev ? n - 1 - e : e] = c ? rt_comb(excl, v).m + excl.s : excl.s;
     }
 };
-// Block aggregates of a level below: scanned in place into their exclusive prefixes.
-struct RtPairs {
-    RtPair *p;
-    long long n;
-    __device__ __forceinline__ RtPair load(long long e) const { return p[e]; }
-    __device__ __forceinline__ void store(long long e, RtPair excl, RtPair) const { p[e] = excl; }
-};
-
-// One workgroup per tile of 2 048 elements, a lane takes 8 consecutive ones.  WRITE == false: the tile's aggregate into agg[block].
-// WRITE == true: every element's result, behind prefix[block] (nullptr: a lone tile).  The operator is not commutative: the lower
-// index is always the left operand.
-template <class SRC, bool WRITE>
-__global__ __launch_bounds__(256) void k_rt_scan(SRC src, const RtPair *__restrict__ prefix, RtPair *__restrict__ agg)
-{
-    __shared__ RtPair wtot[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long base = (long long)blockIdx.x * WA_RT_TILE + (long long)threadIdx.x * WA_RT_ITEMS;
-    const RtPair id = {0, WA_RT_INF};
-    RtPair v[WA_RT_ITEMS], t = id;
-#pragma unroll
-    for (int k = 0; k < WA_RT_ITEMS; k++) {
-        v[k] = base + k < src.n ? src.load(base + k) : id;
-        t = rt_comb(t, v[k]);
-    }
-    RtPair inc = t;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        RtPair u;
-        u.s = __shfl_up(inc.s, o, 64);
-        u.m = __shfl_up(inc.m, o, 64);
-        if (lane >= o) inc = rt_comb(u, inc);
-    }
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    RtPair before = id;
-    for (int w = 0; w < wave; w++) before = rt_comb(before, wtot[w]);
-    if (!WRITE) {
-        if (threadIdx.x == 255) agg[blockIdx.x] = rt_comb(before, inc);
-        return;
-    }
-    RtPair prev;
-    prev.s = __shfl_up(inc.s, 1, 64);
-    prev.m = __shfl_up(inc.m, 1, 64);
-    if (lane == 0) prev = id;
-    RtPair run = rt_comb(before, prev);
-    if (prefix) run = rt_comb(prefix[blockIdx.x], run);
-#pragma unroll
-    for (int k = 0; k < WA_RT_ITEMS; k++) {
-        if (base + k < src.n) src.store(base + k, run, v[k]);
-        run = rt_comb(run, v[k]);
-    }
-}
-
-// host side of the scan: reduce - scan - add: the tiles' aggregates, their exclusive prefixes (by this very function when they exceed one tile), the results
-template <class SRC>
-static hipError_t rt_scan(hipStream_t st, SRC src, RtPair *scratch)
-{
-    const long long blocks = (src.n + WA_RT_TILE - 1) / WA_RT_TILE;
-    if (blocks <= 1) {
-        k_rt_scan<SRC, true><<<1, 256, 0, st>>>(src, nullptr, nullptr);
-        return hipGetLastError();
-    }
-    k_rt_scan<SRC, false><<<(unsigned)blocks, 256, 0, st>>>(src, nullptr, scratch);
-    hipError_t e = hipGetLastError();
-    RtPairs up = {scratch, blocks};
-    e = e ? e : rt_scan(st, up, scratch + blocks);
-    if (e != hipSuccess) return e;
-    k_rt_scan<SRC, true><<<(unsigned)blocks, 256, 0, st>>>(src, scratch, nullptr);
-    return hipGetLastError();
-}
 
 __device__ __forceinline__ double rt_speed(long long b) { return __dsqrt_rn((double)b / WA_RT_Q); }
 

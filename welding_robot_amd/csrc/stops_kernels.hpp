@@ -1,7 +1,8 @@
 // stops_kernels.hpp -- device side of the weld passes in a timed trajectory (wa_traj_retime_stops, wa_traj_tick_axes_stops,
 // wa_traj_axes_dwells; include/weldacs.h rules 40 - 42 hold the definition, DESIGN 4y the reasoning, tests/stops_ref.py restates it in
 // numpy).  A stop is a segment without length that has a duration; the algorithm of the retime section carries it as it stands: a cap
-// of 0 inside the trajectory resets the prefix and the suffix minimum of rule 3, so the scans, k_rt_segments and k_rt_ticks are reused.
+// of 0 inside the trajectory resets the prefix and the suffix minimum of rule 3, so the scans (k_scan, scan_kernels.hpp), k_rt_segments
+// and k_rt_ticks are reused.
 //   k_st_caps        k_rt_caps with the kind-0 cap on both samples of a stop (rt_caps<true>)
 //   k_st_times       k_rt_times with T_i = dq_i on a stop; a stop that has a length goes into the record (rt_times<true>)
 //   k_tk_axes_stops  k_tk_axes with the turn in place during a dwell, a tag per tick and the dwell counters (tk_axes<true>)

@@ -1,8 +1,8 @@
 // ticks_kernels.hpp -- device side of the tool poses at controller ticks (wa_traj_axes_smooth, wa_traj_axes_limits, wa_traj_tick_axes;
 // include/weldacs.h rules 24 - 26 hold the definition, DESIGN 4u the reasoning, tests/ticks_ref.py restates it in numpy).
 //   k_ax_lengths   one lane per sample: L of retime rule 1 for the segment behind it, the sum of L, non-finite coordinates
-//   k_ax_scan3     inclusive prefix sums of the three axis components (int64 each): the tiled reduce - scan - add of k_rt_scan with a
-//                  three-component element and plain addition
+//   k_scan         (scan_kernels.hpp) over Ax3Samples: inclusive prefix sums of the three axis components (int64 each) under plain
+//                  addition
 //   k_ax_level0    rule 24, one lane per sample: its leg, level 0; the few samples whose level-0 candidate is blocked are compacted
 //   k_ax_climb     rule 24, one lane per compacted sample: levels 1 .. max_level until one is clear
 //   k_ax_summary   rule 24's counters over the finished arrays
@@ -100,20 +100,17 @@ __global__ __launch_bounds__(256) void k_ax_lengths(const float *__restrict__ xy
     if ((threadIdx.x & 63) == 0) rt_acc_split(rec->sumL, sl);
 }
 
-// ---- the three-component prefix sum
+// ---- the three-component prefix sum: the operator of its scan (scan_kernels.hpp)
 struct Ax3 { long long x, y, z; };
-__device__ __forceinline__ Ax3 ax3_add(Ax3 a, Ax3 b)
-{
-    Ax3 r = {a.x + b.x, a.y + b.y, a.z + b.z};
-    return r;
-}
-__device__ __forceinline__ Ax3 ax3_shfl_up(Ax3 a, int o)
-{
-    Ax3 r = {__shfl_up(a.x, o, 64), __shfl_up(a.y, o, 64), __shfl_up(a.z, o, 64)};
-    return r;
-}
-// A source hands out element e and takes its result.  Samples: the element is q[e], the result the INCLUSIVE prefix.
+struct Ax3Sum {
+    typedef Ax3 T;
+    static __device__ __forceinline__ Ax3 id() { return Ax3{0, 0, 0}; }
+    static __device__ __forceinline__ Ax3 comb(Ax3 a, Ax3 b) { return Ax3{a.x + b.x, a.y + b.y, a.z + b.z}; }
+    static __device__ __forceinline__ Ax3 up(Ax3 a, int o) { return Ax3{__shfl_up(a.x, o, 64), __shfl_up(a.y, o, 64), __shfl_up(a.z, o, 64)}; }
+};
+// Samples: the element is q[e], the result the INCLUSIVE prefix.
 struct Ax3Samples {
+    typedef Ax3Sum Op;
     const short4 *q;
     Ax3 *out;
     long long n;
@@ -123,72 +120,8 @@ struct Ax3Samples {
         Ax3 r = {v.x, v.y, v.z};
         return r;
     }
-    __device__ __forceinline__ void store(long long e, Ax3 excl, Ax3 v) const { out[e] = ax3_add(excl, v); }
+    __device__ __forceinline__ void store(long long e, Ax3 excl, Ax3 v) const { out[e] = Ax3Sum::comb(excl, v); }
 };
-// Tile aggregates of a level below: scanned in place into their exclusive prefixes.
-struct Ax3Aggs {
-    Ax3 *p;
-    long long n;
-    __device__ __forceinline__ Ax3 load(long long e) const { return p[e]; }
-    __device__ __forceinline__ void store(long long e, Ax3 excl, Ax3) const { p[e] = excl; }
-};
-
-// One workgroup per tile of WA_RT_TILE elements, a lane takes WA_RT_ITEMS consecutive ones (the layout of k_rt_scan).
-template <class SRC, bool WRITE>
-__global__ __launch_bounds__(256) void k_ax_scan3(SRC src, const Ax3 *__restrict__ prefix, Ax3 *__restrict__ agg)
-{
-    __shared__ Ax3 wtot[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long base = (long long)blockIdx.x * WA_RT_TILE + (long long)threadIdx.x * WA_RT_ITEMS;
-    const Ax3 zero = {0, 0, 0};
-    Ax3 v[WA_RT_ITEMS], t = zero;
-#pragma unroll
-    for (int k = 0; k < WA_RT_ITEMS; k++) {
-        v[k] = base + k < src.n ? src.load(base + k) : zero;
-        t = ax3_add(t, v[k]);
-    }
-    Ax3 inc = t;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const Ax3 u = ax3_shfl_up(inc, o);
-        if (lane >= o) inc = ax3_add(u, inc);
-    }
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    Ax3 before = zero;
-    for (int w = 0; w < wave; w++) before = ax3_add(before, wtot[w]);
-    if (!WRITE) {
-        if (threadIdx.x == 255) agg[blockIdx.x] = ax3_add(before, inc);
-        return;
-    }
-    Ax3 prev = ax3_shfl_up(inc, 1);
-    if (lane == 0) prev = zero;
-    Ax3 run = ax3_add(before, prev);
-    if (prefix) run = ax3_add(prefix[blockIdx.x], run);
-#pragma unroll
-    for (int k = 0; k < WA_RT_ITEMS; k++) {
-        if (base + k < src.n) src.store(base + k, run, v[k]);
-        run = ax3_add(run, v[k]);
-    }
-}
-
-// host side: reduce - scan - add, as rt_scan; scratch holds rt_scratch_pairs(n) elements
-template <class SRC>
-static hipError_t ax_scan3(hipStream_t st, SRC src, Ax3 *scratch)
-{
-    const long long blocks = (src.n + WA_RT_TILE - 1) / WA_RT_TILE;
-    if (blocks <= 1) {
-        k_ax_scan3<SRC, true><<<1, 256, 0, st>>>(src, nullptr, nullptr);
-        return hipGetLastError();
-    }
-    k_ax_scan3<SRC, false><<<(unsigned)blocks, 256, 0, st>>>(src, nullptr, scratch);
-    hipError_t e = hipGetLastError();
-    Ax3Aggs up = {scratch, blocks};
-    e = e ? e : ax_scan3(st, up, scratch + blocks);
-    if (e != hipSuccess) return e;
-    k_ax_scan3<SRC, true><<<(unsigned)blocks, 256, 0, st>>>(src, scratch, nullptr);
-    return hipGetLastError();
-}
 
 // ---- rule 24
 struct WaAxSmooth {
