@@ -587,6 +587,27 @@ def tick_pose_stage(ctx, metal, xyz, limits, tick, omega, h, duration_free):
     return info
 
 
+def jerk_pose_stage(ctx, metal, xyz, limits, tick, omega, h, jerk):
+    """Tool poses at the jerk-limited ticks (--jerk-poses): tick_pose_stage's chain -- the chosen directions smoothed
+    (wa_traj_axes_smooth) and turned into a per-sample speed limit for the turn rate omega (wa_traj_axes_limits) -- ending in ONE call
+    that times the curve under that limit, filters the ticks over the window of the jerk limit and gives every filtered tick its
+    checked axis (wa_traj_retime_jerk_axes).  Neither the filtered arc lengths nor the axes pass through the host."""
+    off, chosen, dirs, tool = torch_stage.last
+    v_max, acc, dec, a_lat, v_near, near_d2 = limits
+    curve = api.Trajectory.from_points(ctx, xyz)
+    sm = curve.smooth_axes(api.quantise_axes(dirs)[chosen], h, 8, metal, tool, off)
+    v_limit, ls = curve.axis_limits(sm["q"], omega, v_max, v_max * 1e-3)
+    window = api.jerk_window(acc, dec, jerk, tick)
+    _, _, _, _, _, _, rs, _, sj, axes, _, sa = curve.retime_jerk_axes(sm["q"], v_max, acc, dec, tick, window, grid=metal, tool=tool, near_add=8,
+                                                                      a_lat=a_lat, v_near=v_near, near_d2=int(near_d2), v_limit=v_limit,
+                                                                      ticks=False, blocked=False)
+    if axes is not None:
+        axes.close()
+    return dict(omega=omega, h=h, jerk_limit=jerk, window=window, smooth=sm["summary"], limits=ls,
+                duration_turn_limited=rs["time_q"] / api.RETIME_Q, duration_s=(sj["n_ticks"] - 1) * tick, n_back=sj["n_back"],
+                n_short_rests=sj["n_short_rests"], ticks=sa, max_tick_turn=sa["max_tick_turn"], blocked_ticks=sa["n_blocked"])
+
+
 def jerk_report(ctx, metal, sj, filtered, tick, plain_ticks, plain_time_q, jerk):
     """what --jerk adds to the JSON: the summary of wa_traj_retime_jerk, the filtered duration against the unfiltered one and the
     clearance check of the filtered ticks"""
@@ -735,6 +756,10 @@ def main():
                     help="after --fit or --retime: the torch axis at every sample of the trajectory, one of K directions (1 .. 256) of a cone "
                          "around +z, so that the torch body clears the metal (wa_traj_tool_axes); prints the summary and the check of the "
                          "interpolated axes between samples")
+    ap.add_argument("--jerk-poses", action="store_true",
+                    help="--jerk J with --tick-poses OMEGA: the torch axes at the jerk-limited ticks (wa_traj_retime_jerk_axes) -- the smoothed "
+                         "axes and their speed limit as for --tick-poses, then one call that times, filters and gives every filtered tick "
+                         "its checked axis; reported under jerk_poses")
     ap.add_argument("--tick-poses", type=float, nargs="+", default=None, metavar=("OMEGA", "H"),
                     help="--retime --torch K: the torch axis at every controller tick, on the device: the chosen directions smoothed over windows "
                          "of half-width H along the path (default: 8 voxels) where the body stays clear, the timing limited to OMEGA (chord of "
@@ -835,9 +860,12 @@ def main():
         ap.error("--fit needs the waypoints of --shortcut")
     if args.seams and (args.points % 2 or args.points < 2):
         ap.error("--seams needs an even number of --points (two per seam)")
+    if args.jerk_poses and (args.jerk is None or args.tick_poses is None):
+        ap.error("--jerk-poses needs --jerk J and --tick-poses OMEGA")
     if args.jerk is not None:
-        if args.tick_poses is not None:
-            ap.error("--jerk does not go together with --tick-poses yet: the torch axes at filtered ticks are not built")
+        if args.tick_poses is not None and not args.jerk_poses:
+            ap.error("--jerk with --tick-poses needs --jerk-poses: the ticks of --tick-poses are the unfiltered ones, the torch axes at "
+                     "the jerk-limited ticks are --jerk-poses'")
         if not args.retime and args.weld_passes is None:
             ap.error("--jerk needs --retime, or --seams --weld-passes")
         if not (args.jerk > 0 and np.isfinite(args.jerk)):
@@ -1078,7 +1106,13 @@ def main():
                        t_torch_s=time.perf_counter() - t4)
             if args.pose_paths is not None:
                 out.update(n_no_dir=out["torch"]["n_no_dir"], n_over_turn=out["torch"]["n_over_turn"])
-            if args.tick_poses is not None:
+            if args.jerk_poses:
+                t5 = time.perf_counter()
+                h = args.tick_poses[1] if len(args.tick_poses) > 1 else 8.0 * float(metal.precision)
+                out.update(jerk_poses=jerk_pose_stage(ctx, metal, np.ascontiguousarray(traj[ok.astype(bool)], np.float32), args.retime_limits,
+                                                      args.retime_tick, args.tick_poses[0], h, args.jerk),
+                           t_jerk_poses_s=time.perf_counter() - t5)
+            elif args.tick_poses is not None:
                 t5 = time.perf_counter()
                 h = args.tick_poses[1] if len(args.tick_poses) > 1 else 8.0 * float(metal.precision)
                 out.update(tick_poses=tick_pose_stage(ctx, metal, np.ascontiguousarray(traj[ok.astype(bool)], np.float32), args.retime_limits,

@@ -1435,8 +1435,9 @@ int wa_grid_pose_diag_paths(const wa_grid *g, const float *dirs, int32_t K, cons
  * time_q_out, w_q_out, bound_out (n entries, host), ticks_out (a device-resident wa_traj of the filtered positions, owned by the
  * caller), s_q_out (int64 per output tick, host), tag_out (one byte per output tick, host), dwell, v_limit, seg_tag (n - 1 bytes, host)
  * and g may be NULL; s_q_out and tag_out hold jerk->n_ticks entries, which a call without them reports.  Same bytes on every call; everything runs on the context's stream; g and t are not modified.  The range minima of
- * rule 49 take 8 * n bytes per power of two in the widest window; WA_ERR_ALLOC where that cannot be had.  Not covered: torch axes at
- * filtered ticks, a reach tighter than rule 48's, cascaded windows (a bound on the snap), per-stop tags for stops in a row. */
+ * rule 49 take 8 * n bytes per power of two in the widest window; WA_ERR_ALLOC where that cannot be had.  Not covered: a reach
+ * tighter than rule 48's, cascaded windows (a bound on the snap), per-stop tags for stops in a row.  (Torch axes at the filtered ticks:
+ * wa_traj_retime_jerk_axes, rules 56 - 60 below.) */
 typedef struct {
     int64_t window, reach_q, n_lowered, n_in, n_ticks;
     int64_t max_d1, max_d2, max_d3, in_max_d2;
@@ -1449,6 +1450,51 @@ int wa_traj_retime_jerk(const wa_grid *g, const wa_traj *t, const wa_retime_limi
                         int64_t *s_q_out /* n_ticks, host, may be NULL */, uint8_t *tag_out /* n_ticks, host, may be NULL */,
                         wa_retime_summary *sum, wa_stops_summary *stops, wa_jerk_summary *jerk);
 int wa_traj_jerk_window(const wa_traj *t /* may be NULL */, double acc, double dec, double jerk, double tick, int32_t *window_out);
+
+/* ---- torch axes at jerk-limited ticks: poses for the filtered trajectory (not in the reference) ----
+ *      wa_traj_tick_axes and wa_traj_tick_axes_stops locate a tick by TIME (retime rule 6); the ticks of wa_traj_retime_jerk are a moving
+ *      average along the ARC LENGTH: they lie at other places, under other tick numbers, and there are W - 1 more of them.
+ *      wa_traj_retime_jerk_axes is wa_traj_retime_jerk with one checked torch axis per filtered tick; S of rule 53 never leaves the
+ *      device.  The rules continue the numbering above; q, U(a, b), wa_tool_beads and "blocked" are those of rules 1 and 2, the axes
+ *      travel as quantised integers as in rule 24's preamble, GL, S_k and rule 54 are those of the section above.
+ * 56. Every output wa_traj_retime_jerk has is returned with that call's bytes, *ticks_out included, and everything it refuses is
+ *     refused.  q (int32, n x 3, host): every |q_c| <= 16384 and no triple all zero; tool and near_add as rule 9; g and tool may both be
+ *     NULL (no check: nothing is blocked, n_outside is 0), one alone is WA_ERR_ARG; a NULL q or a NULL axes summary is WA_ERR_ARG.  g
+ *     serves both the caps of retime rule 2 and the check of rule 59.  Every WA_ERR_ARG is answered before anything is written.  More
+ *     than 2^31 output ticks: WA_ERR_CAPACITY as in rule 53, and *axes_out = NULL, blocked_out untouched, *axes all zero.
+ * 57. Moving tick (rule 54 (b) gave segment i).  lambda = 1 where the tick is p_(i+1) exactly, 0 where L_i = 0, else rule 54's
+ *     (double)(S_k - GL_i) / (double)L_i.  The axis is rule 26's expression: v_c = (double)q_i,c + ((double)q_(i+1),c - (double)q_i,c) * lambda;
+ *     if v is all zero the axis is q_i, else v quantised by rule 1 to qt.  The axis belongs to the POSITION the tick has on the
+ *     polyline: the set of (position, axis) pairs is the one rule 26 visits, only the pace along it changes.
+ * 58. Rest tick (rule 54 (a) gave the head stop f).  a = the lowest and e = the highest sample index with GL = GL_f (e <= n - 1): the
+ *     whole run of coincident samples turns as one, whatever un-stopped segments without length it holds, so the moving tick in front
+ *     of the rest approaches q_a and the one behind it leaves from q_e.  first_f = the lowest tick index that is a rest tick of f,
+ *     R_f = the number of rest ticks of f -- both by counting, not by assuming that S never falls (n_back exists because that is not
+ *     proved).  lambda = (double)(k - first_f) / (double)R_f clamped into [0, 1]; the axis is rule 57's expression between q_a and q_e, q_a
+ *     where v is all zero.  The position stays rule 54's p_f.  The torch turns in place, linear in the tick number, over exactly the
+ *     ticks during which the filtered position rests; rule 50's extension gives a stop of dq at least floor(dq / tick_q) of them unless
+ *     n_short_rests says otherwise.
+ * 59. Check.  blocked_out[k] (one byte per tick, 0 or 1, host, may be NULL) = rule 2 with qt at the voxel of the tick's fp32 position (the
+ *     lookup of wa_traj_clearance).  *axes_out (may be NULL) is a device-resident wa_traj of n_ticks points (float)(qt_c / 16384.0), owned
+ *     by the caller.
+ * 60. wa_jerk_axes_summary.  n_ticks, n_outside, n_blocked, first_blocked (-1: none), n_near, max_tick_turn as wa_tick_axes_summary, over
+ *     the filtered ticks.  n_rest_ticks = jerk->n_rest_ticks.  n_turning_rests = groups of stops sharing one GL with q_a != q_e;
+ *     min_turn_ticks = the smallest R_f among them (0 without one): psi / (R_f * tick) is the chord rate of that turn.  max_rest_turn =
+ *     the largest U between the axes of tick k - 1 and tick k over the rest ticks k > 0.
+ * Same bytes on every call; everything runs on the context's stream; g and t are not modified.  Not covered: a limit on the angular
+ * acceleration at the ends of a rest, slerp, cascaded windows. */
+typedef struct {
+    int64_t n_ticks, n_outside, n_blocked, first_blocked, n_near, max_tick_turn;
+    int64_t n_rest_ticks, n_turning_rests, min_turn_ticks, max_rest_turn;
+} wa_jerk_axes_summary;
+int wa_traj_retime_jerk_axes(const wa_grid *g, const wa_traj *t, const wa_retime_limits *lim, const float *v_limit,
+                             const double *dwell /* n-1, host, may be NULL */, double tick, int32_t window,
+                             const uint8_t *seg_tag /* n-1, host, may be NULL */,
+                             const int32_t *q /* n x 3, host */, const wa_tool_beads *tool, int32_t near_add,
+                             int64_t *time_q_out, int64_t *w_q_out, uint8_t *bound_out, wa_traj **ticks_out,
+                             int64_t *s_q_out /* n_ticks, host, may be NULL */, uint8_t *tag_out /* n_ticks, host, may be NULL */,
+                             wa_traj **axes_out, uint8_t *blocked_out /* n_ticks, host, may be NULL */,
+                             wa_retime_summary *sum, wa_stops_summary *stops, wa_jerk_summary *jerk, wa_jerk_axes_summary *axes);
 
 #ifdef __cplusplus
 }

@@ -146,6 +146,12 @@ class JerkSummary(C.Structure):
                 ("n_rest_ticks", C.c_int64), ("n_short_rests", C.c_int64), ("n_back", C.c_int64)]
 
 
+class JerkAxesSummary(C.Structure):
+    _fields_ = [("n_ticks", C.c_int64), ("n_outside", C.c_int64), ("n_blocked", C.c_int64), ("first_blocked", C.c_int64),
+                ("n_near", C.c_int64), ("max_tick_turn", C.c_int64), ("n_rest_ticks", C.c_int64), ("n_turning_rests", C.c_int64),
+                ("min_turn_ticks", C.c_int64), ("max_rest_turn", C.c_int64)]
+
+
 WA_PEN_MAX = 31
 
 # every symbol include/weldacs.h declares: name -> (restype, argtypes)
@@ -302,6 +308,10 @@ SYMBOLS = {
     "wa_traj_retime_jerk": (C.c_int, [_V, _V, C.POINTER(RetimeLimits), _P, _P, C.c_double, _I, _P, _P, _P, _P, C.POINTER(_V), _P, _P,
                                       C.POINTER(RetimeSummary), C.POINTER(StopsSummary), C.POINTER(JerkSummary)]),
     "wa_traj_jerk_window": (C.c_int, [_V, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int32)]),
+    "wa_traj_retime_jerk_axes": (C.c_int, [_V, _V, C.POINTER(RetimeLimits), _P, _P, C.c_double, _I, _P, _P, C.POINTER(ToolBeads), _I,
+                                           _P, _P, _P, C.POINTER(_V), _P, _P, C.POINTER(_V), _P,
+                                           C.POINTER(RetimeSummary), C.POINTER(StopsSummary), C.POINTER(JerkSummary),
+                                           C.POINTER(JerkAxesSummary)]),
 }
 
 _libs = {}

@@ -1193,6 +1193,57 @@ class Trajectory:
         return (time_q, w_q, bound, Trajectory(self.ctx, th) if th.value else None, sq, tg, summary,
                 {k: int(getattr(s2, k)) for k, _ in L.StopsSummary._fields_}, {k: int(getattr(s3, k)) for k, _ in L.JerkSummary._fields_})
 
+    def retime_jerk_axes(self, q, v_max, acc, dec, tick, window, dwell=None, seg_tag=None, grid=None, tool=None, near_add=-1,
+                         a_lat=float("inf"), v_near=0.0, near_d2=-1, v_limit=None, ticks=True, s_q=False, tags=None, axes=True, blocked=True):
+        """wa_traj_retime_jerk_axes: retime_jerk() with one torch axis per filtered tick.  `q`: the quantised sample axes (quantise_axes).
+        A moving tick takes the axis of its place on the polyline, interpolated along its segment like tick_axes(); while the filtered
+        position rests at a stop the torch turns in place from the first to the last axis of the coincident samples, linear in the
+        tick number.  Every axis is checked against `grid` with `tool` at the tick's position (both or neither).
+        Returns retime_jerk()'s tuple plus (axes Trajectory or None, blocked uint8[n_ticks] or None, axes dict)."""
+        n = len(self)
+        q = self._axes(q)
+        lim = L.RetimeLimits(v_max, acc, dec, a_lat, v_near, near_d2)
+        if v_limit is not None:
+            v_limit = np.ascontiguousarray(v_limit, np.float32).reshape(-1)
+            if len(v_limit) != n:
+                raise ValueError("v_limit needs one entry per sample")
+        dwell = self._dwells(dwell, "dwell")
+        if seg_tag is not None:
+            seg_tag = np.ascontiguousarray(seg_tag, np.uint8).reshape(-1)
+            if len(seg_tag) != n - 1:
+                raise ValueError("seg_tag needs one entry per segment")
+        tags = seg_tag is not None if tags is None else tags
+        if tags and seg_tag is None:
+            raise ValueError("tags need seg_tag")
+        if tool is not None:
+            tool = tool if isinstance(tool, L.ToolBeads) else torch_tool(*tool)
+        g = grid.h if grid is not None else None
+        s, s2, s3, s4 = L.RetimeSummary(), L.StopsSummary(), L.JerkSummary(), L.JerkAxesSummary()
+
+        def call(time_q, w_q, bound, th, sq, tg, ah, bl):
+            rc = self.ctx.lib.wa_traj_retime_jerk_axes(g, self.h, C.byref(lim), _ptr(v_limit), _ptr(dwell), C.c_double(tick), int(window),
+                                                       _ptr(seg_tag), _ptr(q), C.byref(tool) if tool is not None else None, near_add,
+                                                       _ptr(time_q), _ptr(w_q), _ptr(bound), C.byref(th) if th is not None else None,
+                                                       _ptr(sq), _ptr(tg), C.byref(ah) if ah is not None else None, _ptr(bl),
+                                                       C.byref(s), C.byref(s2), C.byref(s3), C.byref(s4))
+            if rc != 7:   # WA_ERR_CAPACITY: everything but the ticks is there
+                self.ctx.check(rc)
+            return rc
+
+        sq = tg = bl = None
+        if s_q or tags or blocked:   # (the host arrays are sized by a first call without outputs: the same bytes on every call)
+            if call(None, None, None, None, None, None, None, None) == 0:
+                sq = np.empty(int(s3.n_ticks), np.int64) if s_q else None
+                tg = np.empty(int(s3.n_ticks), np.uint8) if tags else None
+                bl = np.empty(int(s3.n_ticks), np.uint8) if blocked else None
+        time_q, w_q, bound = np.empty(n, np.int64), np.empty(n, np.int64), np.empty(n, np.uint8)
+        th, ah = C.c_void_p(), C.c_void_p()
+        call(time_q, w_q, bound, th if ticks else None, sq, tg, ah if axes else None, bl)
+        summary = {k: (list(getattr(s, k)) if k == "n_bound" else int(getattr(s, k))) for k, _ in L.RetimeSummary._fields_}
+        return (time_q, w_q, bound, Trajectory(self.ctx, th) if th.value else None, sq, tg, summary,
+                {k: int(getattr(s2, k)) for k, _ in L.StopsSummary._fields_}, {k: int(getattr(s3, k)) for k, _ in L.JerkSummary._fields_},
+                Trajectory(self.ctx, ah) if ah.value else None, bl, {k: int(getattr(s4, k)) for k, _ in L.JerkAxesSummary._fields_})
+
     def axis_dwells(self, q, omega, dwell=None):
         """wa_traj_axes_dwells: the dwell every change of direction on a segment without length needs at the turn rate `omega` (chord of
         the unit axes per second), never below the caller's own `dwell` there.  Returns (float64[n-1] for retime_stops(dwell=...),

@@ -15,7 +15,7 @@ static int jk_ticks(wa_ctx *ctx, const wa_traj *t, double acc, double dec, const
 static long long jk_n_out(const JerkRun &jk, long long n_u);
 static int jk_length_check(wa_ctx *ctx, const JerkRun &jk, int64_t length_q);
 static hipError_t jk_copy_out(wa_ctx *ctx, long long n_out, JerkRun &jk, WaJkRec *host_rec);
-static void jk_summary(const JerkRun &jk, const WaJkRec &r, long long n_u, long long n_out);
+static void jk_summary(JerkRun &jk, const WaJkRec &r, long long n_u, long long n_out);
 struct RetimeBuffers {
     DevBuf<long long> A, D, C, F, B, T, time_q, dq;
     DevBuf<uint8_t> kind, bound;

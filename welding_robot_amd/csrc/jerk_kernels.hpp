@@ -225,7 +225,10 @@ __device__ __forceinline__ unsigned long long jk_wave_max(unsigned long long v)
 // another workgroup writes.  S rises along a wave (n_back counts where it does not), so the first sample at or behind the wave's first S
 // brackets every lane's search from below; a lane whose S lies in front of it searches the samples in front.  A run of samples
 // that share one GL is crossed by galloping, never sample by sample; the stop that takes a rest tick comes from next[].
-__global__ __launch_bounds__(256) void k_jk_ticks(WaJkTicks T)
+// FIRST (wa_traj_retime_jerk_axes, rule 58): the same kernel, which also leaves the lowest rest tick of every stop in first[]; what it
+// adds is compiled in only there (jerk_axes_kernels.hpp holds that instantiation).
+template <bool FIRST>
+__device__ __forceinline__ void jk_ticks(const WaJkTicks &T, unsigned long long *__restrict__ first)
 {
     __shared__ float stage[256 * 3];
     __shared__ uint32_t st_tag[64];
@@ -309,7 +312,10 @@ __global__ __launch_bounds__(256) void k_jk_ticks(WaJkTicks T)
         while (todo) {
             const long long who = __shfl(seg, __builtin_ctzll(todo), 64);
             const unsigned long long same = __ballot(rest && seg == who);
-            if (lane == 0) atomicAdd(&T.rest_cnt[who], (unsigned long long)__popcll(same));
+            if (lane == 0) {
+                atomicAdd(&T.rest_cnt[who], (unsigned long long)__popcll(same));
+                if (FIRST) atomicMin(&first[who], (unsigned long long)(k_first + __builtin_ctzll(same)));
+            }
             todo &= ~same;
         }
         const unsigned long long mr = __ballot(rest), mb = __ballot(back);
@@ -342,6 +348,11 @@ __global__ __launch_bounds__(256) void k_jk_ticks(WaJkTicks T)
                 if (first + b < T.n_ticks) T.tag[first + b] = ((const uint8_t *)st_tag)[4 * threadIdx.x + b];
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k_jk_ticks(WaJkTicks T)
+{
+    jk_ticks<false>(T, nullptr);
 }
 
 // Rule 55, n_short_rests: the head of a group holds the group's rest ticks and the dwells its stops were given.

@@ -48,6 +48,7 @@
 #include "ticks_kernels.hpp"
 #include "stops_kernels.hpp"
 #include "jerk_kernels.hpp"
+#include "jerk_axes_kernels.hpp"
 #include "stl_text.hpp"
 #include "acs_plan.hpp"
 
@@ -1042,5 +1043,6 @@ void *wa_ctx_stream(wa_ctx *c) { return c ? (void *)c->stream : nullptr; }
 #include "host_pose_fit.inc"
 #include "host_ticks.inc"
 #include "host_stops.inc"
+#include "host_jerk_axes.inc"
 
 }  // extern "C"
