@@ -1496,6 +1496,74 @@ int wa_traj_retime_jerk_axes(const wa_grid *g, const wa_traj *t, const wa_retime
                              wa_traj **axes_out, uint8_t *blocked_out /* n_ticks, host, may be NULL */,
                              wa_retime_summary *sum, wa_stops_summary *stops, wa_jerk_summary *jerk, wa_jerk_axes_summary *axes);
 
+/* ---- tool frames and the weld weave at jerk-limited ticks (not in the reference) ----
+ *      An axis fixes two of a tool frame's three rotational degrees of freedom; the third is the direction ACROSS the seam,
+ *      perpendicular to the torch and to the direction of travel (the lateral).  A weave is a small periodic offset along the lateral
+ *      during a weld pass, tapered in at arc start and out at crater fill.  It moves the tip OFF the polyline that wa_traj_clearance and
+ *      the fit stages proved clear, so the offset and the bead check at the displaced position belong where the tick's place on the path
+ *      is known: wa_traj_retime_jerk_frames is wa_traj_retime_jerk_axes with a lateral per tick and, with a weave, woven positions
+ *      checked where they are.  With window = 1 it covers the unfiltered ticks of wa_traj_retime_stops.  The rules continue the numbering
+ *      above; Q = 2^30, GL, S_k, rules 54, 57 and 58 are those of the two sections above, rule 1 and U(a, b) those of the tool section
+ *      (DESIGN 4ad).  Integers and individually rounded doubles only, no contraction.
+ * 61. Bytes that stay.  With weave == NULL, amp_q = 0 or no weaving segment every output of wa_traj_retime_jerk_axes has that call's
+ *     bytes and *lat_out is the only new array.  With a weave only *ticks_out, blocked_out and n_outside, n_blocked, first_blocked and
+ *     n_near of *axes may differ; time_q_out, w_q_out, bound_out, s_q_out, tag_out, *axes_out, *sum, *stops, *jerk, max_tick_turn and
+ *     the rest counters of rule 60 keep their bytes.  Refused with WA_ERR_ARG before anything is written, beyond rule 56: a NULL frames;
+ *     a weave without seg_tag; an amplitude or a taper that is not finite or < 0; a wavelength that is not finite; wl_q outside
+ *     1 .. 2^50 (so phi < 2^50 is a double as it stands and phi * P < 2^62); amp_q or taper_q >= 2^61; P outside 2 .. 4096; a NULL
+ *     pattern; a pattern entry outside -16384 .. 16384; pattern[0] != 0; tag_mask == 0.  More than 2^31 output ticks: as rule 56, and
+ *     *lat_out = NULL, *frames all zero.
+ * 62. Travel direction per sample.  lo(j) = the highest m < j with GL_m < GL_j, hi(j) = the lowest m > j with GL_m > GL_j; a = p_lo if
+ *     it exists, else p_j; b = p_hi if it exists, else p_j; T_j = (double)b_c - (double)a_c per axis; tau_j = T_j quantised by rule 1,
+ *     and (0, 0, 0) where T_j is all zero.  All samples of a run of coincident samples share lo and hi, so they share tau.
+ * 63. Lateral per tick.  Moving tick (rule 54 (b), segment i, rule 57's lambda): t = rule 57's expression between tau_i and tau_(i+1),
+ *     tau_i where it is all zero.  Rest tick (rule 58, run a .. e): t = tau_a.  z = the tick's own quantised axis qt of rule 57 / 58.
+ *     y = z x t = (z_y t_z - z_z t_y, z_z t_x - z_x t_z, z_x t_y - z_y t_x), every product and difference rounded on its own (they
+ *     are integers below 2^30: exact).  If y is all zero the lateral is undefined: ql = (0, 0, 0), counted in n_no_lateral; else
+ *     ql = rule 1 of y.  *lat_out (may be NULL) is a device-resident wa_traj of n_ticks points (float)(ql_c / 16384.0), owned by the
+ *     caller.  The third frame axis is ql x qt and is left to the caller.  Sign: with the torch body up (+z) and travel along +x the
+ *     lateral is +y, left of travel.
+ * 64. Runs.  Segment i weaves iff (seg_tag[i] & tag_mask) == tag_value.  A run r is a maximal stretch of consecutive weaving segments
+ *     lo_r .. hi_r; O_r = GL_(lo_r), E_r = GL_(hi_r + 1).  A tick weaves iff the segment rule 54 gave it weaves (a rest tick: its head
+ *     stop) and belongs to that segment's run.  A stop inside a pass must carry a weaving tag to keep the run whole: that is the
+ *     caller's business.
+ * 65. Offset.  amp_q, wl_q, taper_q = rint(amplitude * Q), rint(wavelength * Q), rint(taper * Q).  For a weaving tick with S = S_k:
+ *     d = S - O_r, phi = d mod wl_q; x = ((double)phi * (double)P) / (double)wl_q, j = floor(x) capped at P - 1, f = x - j;
+ *     w = pat[j] + (pat[(j+1) mod P] - pat[j]) * f in doubles.  Envelope: m = min(d, E_r - S); env = 1 if taper_q = 0 or m >= taper_q,
+ *     else (double)m / (double)taper_q.  off = ((((double)amp_q / Q) * env) * w) / 16384; off_q = (int64)rint(off * Q).  A tick that
+ *     does not weave has off = 0.  pattern[0] = 0: with a taper the offset is 0 at both ends of a run, so the position is continuous
+ *     into the stops of rule 40.  |off| <= amp_q / Q.
+ * 66. Position and check.  If off != 0 and ql is not all zero: out_c = (float)((double)tick_c + ((double)ql_c / 16384.0) * off), tick_c
+ *     rule 54's fp32 position; otherwise the position is rule 54's bytes.  *ticks_out holds the woven positions, and rule 59's voxel
+ *     lookup and bead check run at the WOVEN position.
+ * 67. wa_frames_summary.  n_ticks; n_no_lateral; n_weave_runs; n_weave_ticks; n_weave_blocked = weaving ticks that are blocked;
+ *     max_offset_q = the largest |off_q|; max_offset_step_q = the largest |off_q_k - off_q_(k-1)|, k > 0: the lateral speed the weave
+ *     adds, which the jerk filter knows nothing of; max_lat_turn = the largest U between the laterals of consecutive ticks where both
+ *     are defined.
+ * Same bytes on every call; everything runs on the context's stream; g and t are not modified; the pattern is read during the call
+ * only.  Not covered: slerp, Euler angles or quaternions, inverse kinematics, a limit on the lateral acceleration of the weave. */
+typedef struct {
+    double amplitude, wavelength, taper;
+    const int16_t *pattern; /* P entries, host, one period; pattern[0] = 0 */
+    int32_t P;
+    uint8_t tag_mask, tag_value;
+} wa_weave;
+typedef struct {
+    int64_t n_ticks, n_no_lateral, n_weave_runs, n_weave_ticks, n_weave_blocked;
+    int64_t max_offset_q, max_offset_step_q, max_lat_turn;
+} wa_frames_summary;
+int wa_traj_retime_jerk_frames(const wa_grid *g, const wa_traj *t, const wa_retime_limits *lim, const float *v_limit,
+                               const double *dwell /* n-1, host, may be NULL */, double tick, int32_t window,
+                               const uint8_t *seg_tag /* n-1, host, may be NULL without a weave */,
+                               const int32_t *q /* n x 3, host */, const wa_tool_beads *tool, int32_t near_add,
+                               const wa_weave *weave /* may be NULL */,
+                               int64_t *time_q_out, int64_t *w_q_out, uint8_t *bound_out, wa_traj **ticks_out,
+                               int64_t *s_q_out /* n_ticks, host, may be NULL */, uint8_t *tag_out /* n_ticks, host, may be NULL */,
+                               wa_traj **axes_out, uint8_t *blocked_out /* n_ticks, host, may be NULL */,
+                               wa_traj **lat_out /* may be NULL */,
+                               wa_retime_summary *sum, wa_stops_summary *stops, wa_jerk_summary *jerk, wa_jerk_axes_summary *axes,
+                               wa_frames_summary *frames);
+
 #ifdef __cplusplus
 }
 #endif

@@ -152,6 +152,16 @@ class JerkAxesSummary(C.Structure):
                 ("min_turn_ticks", C.c_int64), ("max_rest_turn", C.c_int64)]
 
 
+class Weave(C.Structure):
+    _fields_ = [("amplitude", C.c_double), ("wavelength", C.c_double), ("taper", C.c_double), ("pattern", C.c_void_p), ("P", C.c_int32),
+                ("tag_mask", C.c_uint8), ("tag_value", C.c_uint8)]
+
+
+class FramesSummary(C.Structure):
+    _fields_ = [("n_ticks", C.c_int64), ("n_no_lateral", C.c_int64), ("n_weave_runs", C.c_int64), ("n_weave_ticks", C.c_int64),
+                ("n_weave_blocked", C.c_int64), ("max_offset_q", C.c_int64), ("max_offset_step_q", C.c_int64), ("max_lat_turn", C.c_int64)]
+
+
 WA_PEN_MAX = 31
 
 # every symbol include/weldacs.h declares: name -> (restype, argtypes)
@@ -312,6 +322,10 @@ SYMBOLS = {
                                            _P, _P, _P, C.POINTER(_V), _P, _P, C.POINTER(_V), _P,
                                            C.POINTER(RetimeSummary), C.POINTER(StopsSummary), C.POINTER(JerkSummary),
                                            C.POINTER(JerkAxesSummary)]),
+    "wa_traj_retime_jerk_frames": (C.c_int, [_V, _V, C.POINTER(RetimeLimits), _P, _P, C.c_double, _I, _P, _P, C.POINTER(ToolBeads), _I,
+                                             C.POINTER(Weave), _P, _P, _P, C.POINTER(_V), _P, _P, C.POINTER(_V), _P, C.POINTER(_V),
+                                             C.POINTER(RetimeSummary), C.POINTER(StopsSummary), C.POINTER(JerkSummary),
+                                             C.POINTER(JerkAxesSummary), C.POINTER(FramesSummary)]),
 }
 
 _libs = {}

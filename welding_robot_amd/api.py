@@ -1244,6 +1244,62 @@ class Trajectory:
                 {k: int(getattr(s2, k)) for k, _ in L.StopsSummary._fields_}, {k: int(getattr(s3, k)) for k, _ in L.JerkSummary._fields_},
                 Trajectory(self.ctx, ah) if ah.value else None, bl, {k: int(getattr(s4, k)) for k, _ in L.JerkAxesSummary._fields_})
 
+    def retime_jerk_frames(self, q, v_max, acc, dec, tick, window, dwell=None, seg_tag=None, grid=None, tool=None, near_add=-1, weave=None,
+                           a_lat=float("inf"), v_near=0.0, near_d2=-1, v_limit=None, ticks=True, s_q=False, tags=None, axes=True, blocked=True,
+                           lat=True):
+        """wa_traj_retime_jerk_frames: retime_jerk_axes() with the lateral of every tick (the direction across the seam: torch axis x
+        direction of travel, left of travel with the torch body up) and, with `weave` (make_weave() or its keywords as a dict), a periodic offset along the lateral
+        on the segments whose tag matches, tapered at both ends of a run.  The ticks then hold the woven positions and the bead check
+        runs where they are.  Returns retime_jerk_axes()'s tuple plus (lat Trajectory or None, frames dict)."""
+        n = len(self)
+        q = self._axes(q)
+        lim = L.RetimeLimits(v_max, acc, dec, a_lat, v_near, near_d2)
+        if v_limit is not None:
+            v_limit = np.ascontiguousarray(v_limit, np.float32).reshape(-1)
+            if len(v_limit) != n:
+                raise ValueError("v_limit needs one entry per sample")
+        dwell = self._dwells(dwell, "dwell")
+        if seg_tag is not None:
+            seg_tag = np.ascontiguousarray(seg_tag, np.uint8).reshape(-1)
+            if len(seg_tag) != n - 1:
+                raise ValueError("seg_tag needs one entry per segment")
+        tags = seg_tag is not None if tags is None else tags
+        if tags and seg_tag is None:
+            raise ValueError("tags need seg_tag")
+        if tool is not None:
+            tool = tool if isinstance(tool, L.ToolBeads) else torch_tool(*tool)
+        if weave is not None and not isinstance(weave, L.Weave):
+            weave = make_weave(**weave)
+        g = grid.h if grid is not None else None
+        s, s2, s3, s4, s5 = L.RetimeSummary(), L.StopsSummary(), L.JerkSummary(), L.JerkAxesSummary(), L.FramesSummary()
+
+        def call(time_q, w_q, bound, th, sq, tg, ah, bl, lh):
+            rc = self.ctx.lib.wa_traj_retime_jerk_frames(g, self.h, C.byref(lim), _ptr(v_limit), _ptr(dwell), C.c_double(tick), int(window),
+                                                         _ptr(seg_tag), _ptr(q), C.byref(tool) if tool is not None else None, near_add,
+                                                         C.byref(weave) if weave is not None else None,
+                                                         _ptr(time_q), _ptr(w_q), _ptr(bound), C.byref(th) if th is not None else None,
+                                                         _ptr(sq), _ptr(tg), C.byref(ah) if ah is not None else None, _ptr(bl),
+                                                         C.byref(lh) if lh is not None else None,
+                                                         C.byref(s), C.byref(s2), C.byref(s3), C.byref(s4), C.byref(s5))
+            if rc != 7:   # WA_ERR_CAPACITY: everything but the ticks is there
+                self.ctx.check(rc)
+            return rc
+
+        sq = tg = bl = None
+        if s_q or tags or blocked:   # (the host arrays are sized by a first call without outputs: the same bytes on every call)
+            if call(None, None, None, None, None, None, None, None, None) == 0:
+                sq = np.empty(int(s3.n_ticks), np.int64) if s_q else None
+                tg = np.empty(int(s3.n_ticks), np.uint8) if tags else None
+                bl = np.empty(int(s3.n_ticks), np.uint8) if blocked else None
+        time_q, w_q, bound = np.empty(n, np.int64), np.empty(n, np.int64), np.empty(n, np.uint8)
+        th, ah, lh = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        call(time_q, w_q, bound, th if ticks else None, sq, tg, ah if axes else None, bl, lh if lat else None)
+        summary = {k: (list(getattr(s, k)) if k == "n_bound" else int(getattr(s, k))) for k, _ in L.RetimeSummary._fields_}
+        return (time_q, w_q, bound, Trajectory(self.ctx, th) if th.value else None, sq, tg, summary,
+                {k: int(getattr(s2, k)) for k, _ in L.StopsSummary._fields_}, {k: int(getattr(s3, k)) for k, _ in L.JerkSummary._fields_},
+                Trajectory(self.ctx, ah) if ah.value else None, bl, {k: int(getattr(s4, k)) for k, _ in L.JerkAxesSummary._fields_},
+                Trajectory(self.ctx, lh) if lh.value else None, {k: int(getattr(s5, k)) for k, _ in L.FramesSummary._fields_})
+
     def axis_dwells(self, q, omega, dwell=None):
         """wa_traj_axes_dwells: the dwell every change of direction on a segment without length needs at the turn rate `omega` (chord of
         the unit axes per second), never below the caller's own `dwell` there.  Returns (float64[n-1] for retime_stops(dwell=...),
@@ -1489,6 +1545,38 @@ def jerk_window(acc, dec, jerk, tick):
     if rc:
         raise ValueError("wa_traj_jerk_window: acc, dec, jerk and tick must be finite and > 0, the window at most 2^20 ticks (status %d)" % rc)
     return int(w.value)
+
+
+def weave_pattern(kind, P):
+    """one period of a weave as the int16 table of wa_weave (P entries in -16384 .. 16384, entry 0 is 0, the table is interpolated
+    linearly and wraps): "triangle" (0, +1 at a quarter, -1 at three quarters), "sine", or "trapezoid" (a triangle of twice the height
+    cut at +-1: the torch lingers at both toes of the weld).  numpy on the host; the table is the caller's data and may be anything."""
+    P = int(P)
+    if not 2 <= P <= 4096:
+        raise ValueError("a pattern has 2 .. 4096 entries")
+    u = np.arange(P, dtype=np.float64) / P
+    tri = np.where(u < 0.25, 4.0 * u, np.where(u < 0.75, 2.0 - 4.0 * u, 4.0 * u - 4.0))
+    if kind == "triangle":
+        w = tri
+    elif kind == "sine":
+        w = np.sin(2.0 * np.pi * u)
+    elif kind == "trapezoid":
+        w = np.clip(2.0 * tri, -1.0, 1.0)
+    else:
+        raise ValueError("kind is 'triangle', 'sine' or 'trapezoid'")
+    out = np.rint(w * 16384.0).astype(np.int16)
+    out[0] = 0
+    return out
+
+
+def make_weave(amplitude, wavelength, pattern, taper=0.0, tag_mask=0xff, tag_value=1):
+    """a wa_weave for Trajectory.retime_jerk_frames: an offset of at most `amplitude` along the lateral, one period of `pattern`
+    (weave_pattern) per `wavelength` of arc length, on every segment with (seg_tag & tag_mask) == tag_value, rising from 0 over `taper`
+    at both ends of a run of such segments"""
+    pattern = np.ascontiguousarray(pattern, np.int16).reshape(-1)
+    w = L.Weave(float(amplitude), float(wavelength), float(taper), pattern.ctypes.data, len(pattern), int(tag_mask), int(tag_value))
+    w._pattern = pattern   # (the table lives as long as the structure)
+    return w
 
 
 TORCH_INF = L.TORCH_INF   # leg cost of a one-sample leg whose two pins differ (wa_traj_tool_axes, rule 5)

@@ -2,7 +2,13 @@
 // behind host_jerk.inc, host_torch.inc and host_ticks.inc).  The call is wa_traj_retime_jerk's body (jerk_run) with one more stage: the
 // host checks the axes and the tool before anything is enqueued, jk_ticks launches k_jk_axes behind its own kernels while the prefix
 // sums of the arc lengths are still on the device, and the two records come back with that call's outputs.
+struct FramesRun;   // host_frames.inc: what wa_traj_retime_jerk_frames adds, nullptr in a plain wa_traj_retime_jerk_axes
+static int fr_launch(wa_ctx *ctx, const WaJkTicks &T, long long n, const WaJkAxes &A, JerkRun &jk, FramesRun &Fr, const WaField &F,
+                     const WaTorchTool *dtool, WaAxRec *drec);
+static hipError_t fr_copy_out(wa_ctx *ctx, FramesRun &Fr);
+static void fr_summary(FramesRun &Fr, long long n_out, bool too_many);
 struct JerkAxesRun {
+    FramesRun *fr;
     std::vector<short4> hq;   // the quantised axes, packed
     WaTorchTool tool;
     WaField F;
@@ -55,7 +61,12 @@ static int jx_launch(wa_ctx *ctx, const WaJkTicks &T, long long n, const long lo
         WaJkAxes A;
         A.q = X.q; A.first = jk.J.first; A.check = X.check ? 1 : 0; A.axes = X.axes ? X.axes->xyz : nullptr; A.blocked = X.blocked;
         A.rec = X.dxrec;
-        k_jk_axes<<<(unsigned)((T.n_ticks + 255) / 256), 256, 0, st>>>(T, A, X.F, X.dtool, X.drec);
+        if (X.fr) {   // rules 61 - 67: the same body with the frames policy
+            int rc = fr_launch(ctx, T, n, A, jk, *X.fr, X.F, X.dtool, X.drec);
+            if (rc) return rc;
+        } else {
+            k_jk_axes<<<(unsigned)((T.n_ticks + 255) / 256), 256, 0, st>>>(T, A, X.F, X.dtool, X.drec);
+        }
         if (jk.any_stop)
             k_jx_groups<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(jk.J.GL, n, dq, jk.J.next, X.q, jk.J.rest_cnt, X.dxrec);
         e = hipGetLastError();
@@ -72,6 +83,7 @@ static hipError_t jx_copy_out(wa_ctx *ctx, long long n_out, JerkRun &jk)
     hipError_t e = hipMemcpyAsync(&X.rec, X.drec, sizeof X.rec, hipMemcpyDeviceToHost, ctx->stream);
     e = e ? e : hipMemcpyAsync(&X.xrec, X.dxrec, sizeof X.xrec, hipMemcpyDeviceToHost, ctx->stream);
     if (X.blocked_out) e = e ? e : hipMemcpyAsync(X.blocked_out, X.blocked, (size_t)n_out, hipMemcpyDeviceToHost, ctx->stream);
+    if (X.fr) e = e ? e : fr_copy_out(ctx, *X.fr);
     return e;
 }
 
@@ -96,15 +108,17 @@ static void jx_summary(JerkRun &jk, const WaJkRec &r, long long n_out, bool too_
     }
     if (X.axes_out) *X.axes_out = X.axes.release();   // (NULL above 2^31 ticks)
     *X.out = s;
+    if (X.fr) fr_summary(*X.fr, n_out, too_many);
 }
 
-int wa_traj_retime_jerk_axes(const wa_grid *g, const wa_traj *t, const wa_retime_limits *lim, const float *v_limit, const double *dwell,
-                             double tick, int32_t window, const uint8_t *seg_tag, const int32_t *q, const wa_tool_beads *tool,
-                             int32_t near_add, int64_t *time_q_out, int64_t *w_q_out, uint8_t *bound_out, wa_traj **ticks_out,
-                             int64_t *s_q_out, uint8_t *tag_out, wa_traj **axes_out, uint8_t *blocked_out, wa_retime_summary *sum,
-                             wa_stops_summary *stops, wa_jerk_summary *jerk, wa_jerk_axes_summary *axes)
+// One body for wa_traj_retime_jerk_axes and wa_traj_retime_jerk_frames (host_frames.inc): fr == nullptr enqueues what
+// wa_traj_retime_jerk_axes always enqueued.
+static int jerk_axes_run(const char *who, const wa_grid *g, const wa_traj *t, const wa_retime_limits *lim, const float *v_limit,
+                         const double *dwell, double tick, int32_t window, const uint8_t *seg_tag, const int32_t *q, const wa_tool_beads *tool,
+                         int32_t near_add, int64_t *time_q_out, int64_t *w_q_out, uint8_t *bound_out, wa_traj **ticks_out, int64_t *s_q_out,
+                         uint8_t *tag_out, wa_traj **axes_out, uint8_t *blocked_out, wa_retime_summary *sum, wa_stops_summary *stops,
+                         wa_jerk_summary *jerk, wa_jerk_axes_summary *axes, FramesRun *fr)
 {
-    static const char *who = "wa_traj_retime_jerk_axes";
     WaDevGuard dev_guard_(t ? t->ctx : nullptr);
     if (!dev_guard_.ok) return WA_ERR_DEVICE;   // the context's device could not be made current
     if (!t) return WA_ERR_ARG;
@@ -115,6 +129,7 @@ int wa_traj_retime_jerk_axes(const wa_grid *g, const wa_traj *t, const wa_retime
     const int64_t n = t->n;
     if (n < 2 || n > WA_RT_MAX_N) return fail(ctx, WA_ERR_ARG, "%s: a trajectory needs 2 .. 2^31 samples", who);
     JerkAxesRun X;
+    X.fr = fr;
     X.check = g != nullptr;
     X.axes_out = axes_out;
     X.blocked_out = blocked_out;
@@ -128,4 +143,14 @@ int wa_traj_retime_jerk_axes(const wa_grid *g, const wa_traj *t, const wa_retime
     }
     return jerk_run(who, g, t, lim, v_limit, dwell, tick, window, seg_tag, time_q_out, w_q_out, bound_out, ticks_out, s_q_out, tag_out, sum,
                     stops, jerk, &X);
+}
+
+int wa_traj_retime_jerk_axes(const wa_grid *g, const wa_traj *t, const wa_retime_limits *lim, const float *v_limit, const double *dwell,
+                             double tick, int32_t window, const uint8_t *seg_tag, const int32_t *q, const wa_tool_beads *tool,
+                             int32_t near_add, int64_t *time_q_out, int64_t *w_q_out, uint8_t *bound_out, wa_traj **ticks_out,
+                             int64_t *s_q_out, uint8_t *tag_out, wa_traj **axes_out, uint8_t *blocked_out, wa_retime_summary *sum,
+                             wa_stops_summary *stops, wa_jerk_summary *jerk, wa_jerk_axes_summary *axes)
+{
+    return jerk_axes_run("wa_traj_retime_jerk_axes", g, t, lim, v_limit, dwell, tick, window, seg_tag, q, tool, near_add, time_q_out, w_q_out,
+                         bound_out, ticks_out, s_q_out, tag_out, axes_out, blocked_out, sum, stops, jerk, axes, nullptr);
 }

@@ -110,8 +110,17 @@ __device__ __forceinline__ JxTick jx_tick(const WaJkTicks &T, const WaJkAxes &A,
 // search in every lane: one address per step); that tick's last sample below S brackets every lane's own search, and its axis is what
 // lane 0 needs for the turn -- nothing is read that another workgroup writes.  The tool sits in LDS, the block's 256 axes go through
 // LDS so that consecutive lanes store consecutive floats, its counters are added up in LDS and leave as one atomic each.
-__global__ __launch_bounds__(256) void k_jk_axes(WaJkTicks T, WaJkAxes A, WaField F, const WaTorchTool *__restrict__ tool,
-                                                 WaAxRec *__restrict__ rec)
+// FR (wa_traj_retime_jerk_frames, rules 61 - 67): the same body, which also forms the lateral, the weave's offset and the woven
+// position of the tick it has just located; what that adds is compiled in only where FR::on (frames_kernels.hpp holds that
+// instantiation and FR's members), so k_jk_axes keeps its registers, its LDS and its occupancy.
+struct JxNoFrames {
+    static constexpr bool on = false;
+    struct State {};
+};
+
+template <class FR>
+__device__ __forceinline__ void jx_axes(const WaJkTicks &T, const WaJkAxes &A, const WaField &F, const WaTorchTool *__restrict__ tool,
+                                        WaAxRec *__restrict__ rec, const FR &fr)
 {
     __shared__ float stage[256 * 3];
     __shared__ int32_t tl[192];
@@ -123,6 +132,8 @@ __global__ __launch_bounds__(256) void k_jk_axes(WaJkTicks T, WaJkAxes A, WaFiel
         blk_turn = blk_rest_turn = 0;
         blk_first = ~0ull;
     }
+    typename FR::State fs;
+    if constexpr (FR::on) fr.begin(fs);
     __syncthreads();
     const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63;
@@ -135,13 +146,16 @@ __global__ __launch_bounds__(256) void k_jk_axes(WaJkTicks T, WaJkAxes A, WaFiel
         const long long k_front = k_first > 0 ? k_first - 1 : 0, S_front = jk_s(T, k_front);
         const JxTick front = jx_tick(T, A, k_front, S_front, jk_last_below(T.GL, 0, T.n - 2, S_front), S_front);
         if (live) {
-            const JxTick t = jx_tick(T, A, k, jk_s(T, k), front.below, S_front);
+            const long long S = jk_s(T, k);
+            const JxTick t = jx_tick(T, A, k, S, front.below, S_front);
             rest = t.rest;
             mine = tk_pack(t.qt);
             for (int c = 0; c < 3; c++) stage[3 * threadIdx.x + c] = (float)((double)(c == 0 ? t.qt.x : (c == 1 ? t.qt.y : t.qt.z)) / 16384.0);
+            float px = rt_tick_pos(T.xyz, t.r, 0), py = rt_tick_pos(T.xyz, t.r, 1), pz = rt_tick_pos(T.xyz, t.r, 2);
+            if constexpr (FR::on) fr.tick(fs, T, t, S, &px, &py, &pz);   // rule 66: the check below runs at the woven position
             if (A.check) {
                 int64_t id;
-                const int3 v = field_voxel(F, rt_tick_pos(T.xyz, t.r, 0), rt_tick_pos(T.xyz, t.r, 1), rt_tick_pos(T.xyz, t.r, 2), &id, &outside);
+                const int3 v = field_voxel(F, px, py, pz, &id, &outside);
                 const int32_t res = ax_beads(F, v, t.qt, tl, tool->n_beads);
                 blocked = res & 1;
                 near = !blocked && (res >> 8) > 0;
@@ -151,6 +165,7 @@ __global__ __launch_bounds__(256) void k_jk_axes(WaJkTicks T, WaJkAxes A, WaFiel
         long long before = __shfl_up(mine, 1, 64);
         if (lane == 0) before = tk_pack(front.qt);
         if (live && k > 0) turn = ax_chord2(tk_unpack(before), tk_unpack(mine)) >> 10;
+        if constexpr (FR::on) fr.steps(fs, T, front, S_front, live, k, blocked);
     }
     const unsigned long long mo = __ballot(outside), mb = __ballot(blocked), mn = __ballot(near);
     unsigned long long rturn = rest ? turn : 0;
@@ -187,6 +202,13 @@ __global__ __launch_bounds__(256) void k_jk_axes(WaJkTicks T, WaJkAxes A, WaFiel
         for (int e = threadIdx.x; e < 256 * 3; e += 256)
             if (first + e < end) A.axes[first + e] = stage[e];
     }
+    if constexpr (FR::on) fr.end(T);
+}
+
+__global__ __launch_bounds__(256) void k_jk_axes(WaJkTicks T, WaJkAxes A, WaField F, const WaTorchTool *__restrict__ tool,
+                                                 WaAxRec *__restrict__ rec)
+{
+    jx_axes(T, A, F, tool, rec, JxNoFrames());
 }
 
 // Rule 60: a group of stops is every stop with one GL; its head (k_jk_groups) holds the group's rest ticks.  The run of samples at that

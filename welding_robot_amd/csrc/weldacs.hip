@@ -49,6 +49,7 @@
 #include "stops_kernels.hpp"
 #include "jerk_kernels.hpp"
 #include "jerk_axes_kernels.hpp"
+#include "frames_kernels.hpp"
 #include "stl_text.hpp"
 #include "acs_plan.hpp"
 
@@ -1044,5 +1045,6 @@ void *wa_ctx_stream(wa_ctx *c) { return c ? (void *)c->stream : nullptr; }
 #include "host_ticks.inc"
 #include "host_stops.inc"
 #include "host_jerk_axes.inc"
+#include "host_frames.inc"
 
 }  // extern "C"
