@@ -2,7 +2,7 @@
 """Time the penalised 26-neighbour fields on the C5-sized job: the 256^3 synth_grid and its 64 weld points.  Prints the median and range
 of --reps whole calls after a warm-up (buffers, penalty upload and packing, searches, copies out; HIP events on the context's stream)
 for, alternating in one run: wa_grid_chamfer_matrix with --step (default 3 4 5), the yardstick, and wa_grid_chamfer_weighted_matrix with
-zero penalties (the same answers and the same levels: k_chm_level against k_cw_level like for like); then the matrix and the paths of
+zero penalties (the same answers and the same levels: k_chm_ring_level<false> against k_chm_ring_level<true> like for like); then the matrix and the paths of
 all 2 016 pairs with penalties gain * (clearance cost - 1), bands 1, 4, 9, gain 3; and for each the launches of the longest search, the
 largest distance and the bytes a source costs.  Kernel times (mean and longest level): run it alone under
 `rocprofv3 --kernel-trace --stats -d <dir> -- python tools/chamfer_weighted_time.py --reps 3`.

@@ -23,7 +23,7 @@ LATE_READ_LIB_PATH = os.path.join(LIB_DIR, "libweldacs_knobs_late_read.so")
 SOURCES = ["weldacs.hip"]
 DEPS = ["wa_device.h", "acs_kernels.hpp", "acs_dev.hpp", "acs_plan.hpp", "acs_walk.hpp", "acs_update.hpp", "acs_nb26.hpp", "acs_converged.hpp", "walk_loop_gfx950.hpp", "grid_kernels.hpp", "gtsp_kernels.hpp", "traj_kernels.hpp",
         "stl_text.hpp", "host_grid.inc", "host_acs.inc", "host_gtsp.inc", "host_traj.inc", "host_comm.inc",
-        "clearance_kernels.hpp", "host_clearance.inc", "shortcut_kernels.hpp", "host_shortcut.inc", "geodesic_kernels.hpp", "host_geodesic.inc", "weighted_kernels.hpp", "host_weighted.inc", "chamfer_kernels.hpp", "host_chamfer.inc", "chamfer_weighted_kernels.hpp", "host_chamfer_weighted.inc", "scan_kernels.hpp", "fit_kernels.hpp", "host_fit.inc", "retime_kernels.hpp", "host_retime.inc",
+        "clearance_kernels.hpp", "host_clearance.inc", "shortcut_kernels.hpp", "host_shortcut.inc", "geodesic_kernels.hpp", "host_geodesic.inc", "weighted_kernels.hpp", "host_weighted.inc", "chamfer_kernels.hpp", "host_chamfer.inc", "scan_kernels.hpp", "fit_kernels.hpp", "host_fit.inc", "retime_kernels.hpp", "host_retime.inc",
         "seamtour_kernels.hpp", "host_seamtour.inc", "seamrules_kernels.hpp", "host_seamrules.inc", "torch_kernels.hpp", "host_torch.inc", "reach_kernels.hpp", "host_reach.inc", "pose_kernels.hpp", "host_pose.inc", "pose_weighted_kernels.hpp", "host_pose_weighted.inc", "pose_shortcut_kernels.hpp", "host_pose_shortcut.inc", "pose_fit_kernels.hpp", "host_pose_fit.inc", "ticks_kernels.hpp", "host_ticks.inc", "stops_kernels.hpp", "host_stops.inc", "jerk_kernels.hpp", "host_jerk.inc", "jerk_axes_kernels.hpp", "host_jerk_axes.inc", "frames_kernels.hpp", "host_frames.inc"]
 HEADER = os.path.join(os.path.dirname(HERE), "include", "weldacs.h")
 

@@ -8,12 +8,23 @@
 // every word a lane writes is its own.
 // The move-allowed masks are built in the launch from the free words of the lane's row and its eight neighbour rows, which all sources of
 // a call share (DESIGN 4q says why they are not precomputed).
+// wa_grid_chamfer_weighted_fields / _matrix / _paths run on the same kernels: the move u -> v costs step[class - 1] + pen[v], pen a
+// per-voxel penalty in 0 .. WA_PEN_MAX paid once per voxel entered.  The step belongs to the move, so a level still pulls from the
+// settled sets of earlier levels; the penalty is paid on entry, so the first pull that reaches a voxel fixes its distance
+// (weighted_kernels.hpp's push, into the lane's own word).  `done` becomes `arrived`, the ring has R = M + P + 1 slots (P = the largest
+// penalty present on a free voxel).  Levels ascend and a pull reads only S_{L - step}, complete since the launch of level L - 1, so the
+// first level A at which a pull reaches a voxel is the least dist(u) + step over its moves, and the voxel's distance is A + pen: it goes
+// into slot A + pen at once and gets A + pen in the field.  One 26-offset gather per level, whatever the penalties.
+// The penalties travel as five bit planes (plane j, bit b of word w = bit j of pen of that voxel; 0 on occupied voxels and padding),
+// shared by all sources of a call; a lane reads them only when voxels of its word arrive.
 #pragma once
 #include "geodesic_kernels.hpp"
 
 #define WA_STEP_MAX_DEV 16
+#define WA_PEN_MAX_DEV 31
+#define WA_PEN_PLANES 5
 
-struct WaChmStep { int32_t s[3]; int32_t M; };   // M = the largest of the three
+struct WaChmStep { int32_t s[3]; int32_t M, P; };   // M = the largest step, P = the largest penalty present on a free voxel (0 without penalties)
 
 // a bitmap row seen from word w: m / c / p hold, at bit b, the row's bit at x - 1 / x / x + 1 (x = 64 wx + b); nothing beyond the row's ends
 struct ChmRow { unsigned long long m, c, p; };
@@ -28,61 +39,43 @@ __device__ __forceinline__ ChmRow chm_row(const unsigned long long *__restrict__
     return o;
 }
 
-// level 0 of every source of a chunk: its bit in `done` and in ring slot 0 (both zeroed before, the whole ring), 0 in its field, last[s] = 0
-// (the last level that settled a voxel), stop[s] = 0
-__global__ __launch_bounds__(256) void k_chm_seed(const long long *__restrict__ src, int32_t n_src, WaGeoDims g, int32_t R,
-                                                  unsigned long long *__restrict__ done, unsigned long long *__restrict__ ring,
-                                                  int32_t *__restrict__ field, int32_t *__restrict__ last, int32_t *__restrict__ stop)
+// penalty bytes to the five bit planes, like k_wgt_planes: one wavefront per word, the ballots are the words.  The same pass validates:
+// info[0] = 1 when a free voxel holds more than WA_PEN_MAX, info[1 + q] = 1 when penalty q is present on a free voxel (info is zeroed
+// before; every writer of a word stores the same value).  Bytes of occupied voxels are ignored.
+__global__ __launch_bounds__(256) void k_cw_planes(const uint8_t *__restrict__ free_, const uint8_t *__restrict__ pen, WaGeoDims g,
+                                                   unsigned long long *__restrict__ planes, int32_t *__restrict__ info)
 {
-    const int32_t s = (int32_t)(blockIdx.x * 256 + threadIdx.x);
-    if (s >= n_src) return;
-    const long long v = src[s];
-    int32_t bit;
-    const int64_t w = geo_word_of(v, g, &bit);
-    const unsigned long long b = 1ull << bit;
-    done[(int64_t)s * g.nw + w] = b;
-    ring[(int64_t)s * R * g.nw + w] = b;
-    if (field) field[(int64_t)s * g.n + v] = 0;
-    last[s] = 0;
-    stop[s] = 0;
+    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (w >= g.nw) return;   // (whole waves)
+    const int64_t row = w / g.W;
+    const int32_t x = (int32_t)(w - row * g.W) * 64 + lane;
+    const bool fr = x < g.nx && free_[row * g.nx + x] != 0;
+    const int32_t q = fr ? (int32_t)pen[row * g.nx + x] : 0;
+    const bool bad = q > WA_PEN_MAX_DEV;
+    const int32_t m = bad ? 0 : q;
+    unsigned long long p[WA_PEN_PLANES];
+#pragma unroll
+    for (int j = 0; j < WA_PEN_PLANES; j++) p[j] = __ballot((m >> j) & 1);
+    if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < WA_PEN_PLANES; j++) planes[(int64_t)j * g.nw + w] = p[j];
+    }
+    if (bad) info[0] = 1;
+    else if (fr) info[1 + q] = 1;
 }
 
-// The launch of level L >= 1 for every source of a chunk (ring of R = M + 1 slots per source, slot = L mod R).  The lane of word w, whose
-// voxels p are the TARGETS of the moves:
-//   cand = for every offset o of class a with L >= step[a - 1]: (S_{L - step[a - 1]} seen at p + o) & (every other voxel of the box of p and
-//          p + o is free); a row outside the grid has no voxels, and a source voxel in S is free by construction:
+// The 26-offset gather of level L for the lane of word w, whose voxels p are the TARGETS of the moves: for every offset o of class a with
+// L >= step[a - 1], (S_{L - step[a - 1]} seen at p + o) & (every other voxel of the box of p and p + o is free); a row outside the grid
+// has no voxels, and a source voxel in S is free by construction:
 //     face   -+x: S1 at x -+ 1;  +-y, +-z: S1 of that row
 //     edge   (sx, sy, 0): S2 of row y + sy at x + sx  &  free(x + sx, y)  &  free(x, y + sy); likewise (sx, 0, sz);
 //            (0, sy, sz): S2 of row (y + sy, z + sz)  &  free(x, y + sy)  &  free(x, z + sz)
 //     corner (sx, sy, sz): S3 of row (y + sy, z + sz) at x + sx  &  the six free bits of the box's other voxels
-//   S = cand & free[w] & ~done[w] is STORED into slot L mod R on every level: that slot held S_{L - R}, which nothing reads any more.
-//   Where S is not empty: done[w] |= S, L goes to the field at S's voxels (when one is kept), last[s] = L.
-// A word with nothing left to settle (free & ~done empty) stores 0 without reading its neighbourhood.
-// A source whose last M levels settled nothing has nothing left in reach of a pull and returns at once, and so does one whose targets are
-// all reached (stop[s], matrix only).  Blocks of one launch may disagree on stop[s]; that only changes bitmaps nobody reads again.
-// Matrix (tgt != NULL): the first block of each source looks its n_tgt targets up in S_{L - 1}, which the launch before completed (the seed
-// for L = 1), and stores L - 1 in the source's row for those in it; the launch after the last productive level sees that level's set.
-__global__ __launch_bounds__(256) void k_chm_level(const unsigned long long *__restrict__ freeb, WaGeoDims g, int32_t level, int32_t slot,
-                                                   WaChmStep st, unsigned long long *__restrict__ done, unsigned long long *__restrict__ ring,
-                                                   int32_t *__restrict__ field, int32_t *__restrict__ last, int32_t *__restrict__ stop,
-                                                   const long long *__restrict__ tgt, int32_t n_tgt, int32_t *__restrict__ mat)
+// rs = the source's ring of R > M slots, slot = L mod R.  Not yet masked by the word's own free and settled bits.
+__device__ __forceinline__ unsigned long long chm_gather(const unsigned long long *__restrict__ freeb, const unsigned long long *__restrict__ rs,
+                                                         const WaGeoDims &g, const WaChmStep &st, int32_t R, int32_t level, int32_t slot, int64_t w)
 {
-    const int32_t s = (int32_t)blockIdx.y;
-    if (last[s] < level - st.M || stop[s]) return;   // (blocks of this launch may already have stored `level`: never !=)
-    const int32_t R = st.M + 1;
-    unsigned long long *rs = ring + (int64_t)s * R * g.nw;
-    if (tgt && blockIdx.x == 0)
-        geo_lookup_targets(rs + (int64_t)(slot == 0 ? st.M : slot - 1) * g.nw, g, tgt, n_tgt, mat + (int64_t)s * n_tgt, level - 1, stop + s);
-    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (w >= g.nw) return;
-    const int64_t sw = (int64_t)s * g.nw + w;
-    const unsigned long long dn = done[sw];
-    const unsigned long long open = freeb[w] & ~dn;
-    unsigned long long *mine = rs + (int64_t)slot * g.nw + w;
-    if (!open) {
-        *mine = 0ull;
-        return;
-    }
     const int64_t row = w / g.W;
     const int32_t wx = (int32_t)(w - row * g.W);
     const int32_t z = (int32_t)(row / g.ny), y = (int32_t)(row - (int64_t)z * g.ny);
@@ -137,16 +130,98 @@ __global__ __launch_bounds__(256) void k_chm_level(const unsigned long long *__r
                 if (vy[i] && vz[j]) {
                     const int64_t wc = w + oy[i] + oz[j];
                     const ChmRow r = chm_row(S, wc, hl, hr);
-                    cand |= fy[i].c & fz[j].c & freeb[wc] &((r.m & f0.m & fy[i].m & fz[j].m) | (r.p & f0.p & fy[i].p & fz[j].p));
+                    cand |= fy[i].c & fz[j].c & freeb[wc] & ((r.m & f0.m & fy[i].m & fz[j].m) | (r.p & f0.p & fy[i].p & fz[j].p));
                 }
     }
-    const unsigned long long S = cand & open;
-    *mine = S;
-    if (S) {
-        done[sw] = dn | S;
-        last[s] = level;
-        if (field) geo_store_level(field + (int64_t)s * g.n + row * g.nx + (int64_t)wx * 64, S, level);
+    return cand;
+}
+
+// source s's field at the first voxel of word w (the word's x index as 32 bits: what k_chm_ring_level<false>'s registers were measured with)
+__device__ __forceinline__ int32_t *chm_field_word(int32_t *__restrict__ field, int32_t s, const WaGeoDims &g, int64_t w)
+{
+    const int64_t row = w / g.W;
+    const int32_t wx = (int32_t)(w - row * g.W);
+    return field + (int64_t)s * g.n + row * g.nx + (int64_t)wx * 64;
+}
+
+// The launch of level L >= 1 for every source of a chunk (ring of R = M + P + 1 slots per source, slot = L mod R).  The lane of word w:
+//   A = chm_gather & free[w] & ~arrived[w]: the voxels a pull reaches for the first time; arrived[w] |= A, last[s] = L where A is not empty.
+//   A's voxels of penalty P are STORED into slot (L + P) mod R on every level and in every word, the early-returning ones included.
+//   A's voxels of penalty q < P are ORed into slot (L + q) mod R where there are any; the field (when one is kept) gets L + q at once, so
+//   no word is visited again when its voxels settle.
+// Which slots a launch touches, and why no lane reads what another lane of the launch writes: level L reads, from other words, only
+// slots L - step with 1 <= step <= M, and writes, in its own word only, slots L .. L + P.  R = M + P + 1 keeps the two sets apart.  The
+// top slot (L + P) mod R held S_{L - M - 1}, which no launch reads again (level L reads L - step >= L - M), and no earlier level can
+// have put anything there (L' + q = L + P with q <= P needs L' >= L): so a plain store is right, and since every word of a live source
+// stores there on every level, that store is also the clearing of the ring.
+// A word with nothing left to arrive (free & ~arrived empty) stores its 0 without reading its neighbourhood or the planes.
+// An arrival at level L settles by L + P and is pulled from by L + P + M, so a source whose last M + P levels had no arrival is
+// finished and returns at once, and so does one whose targets are all reached (stop[s], matrix only).  Blocks of one launch may
+// disagree on stop[s]; that only changes bitmaps nobody reads again.
+// Matrix (tgt != NULL): the first block of each source looks its n_tgt targets up in S_{L - 1}, complete since the launch before (only
+// levels <= L - 1 write it; the seed for L = 1), and stores L - 1 in the source's row for those in it; the launch after the last
+// productive level sees that level's set.
+// PEN == false is the search without penalties: P is the constant 0 whatever st.P holds, `planes` is not read and there is no penalty
+// loop.  The top slot is then the lane's own slot L mod R, R = M + 1, arrived = done = settled, and A is S_L, stored whole.
+template <bool PEN>
+__global__ __launch_bounds__(256) void k_chm_ring_level(const unsigned long long *__restrict__ freeb, const unsigned long long *__restrict__ planes,
+                                                        WaGeoDims g, int32_t level, int32_t slot, WaChmStep st,
+                                                        unsigned long long *__restrict__ arrived, unsigned long long *__restrict__ ring,
+                                                        int32_t *__restrict__ field, int32_t *__restrict__ last, int32_t *__restrict__ stop,
+                                                        const long long *__restrict__ tgt, int32_t n_tgt, int32_t *__restrict__ mat)
+{
+    const int32_t s = (int32_t)blockIdx.y;
+    const int32_t P = PEN ? st.P : 0;
+    if (last[s] < level - (st.M + P) || stop[s]) return;   // (blocks of this launch may already have stored `level`: never !=)
+    const int32_t R = st.M + P + 1;
+    unsigned long long *rs = ring + (int64_t)s * R * g.nw;
+    if (tgt && blockIdx.x == 0)
+        geo_lookup_targets(rs + (int64_t)(slot == 0 ? R - 1 : slot - 1) * g.nw, g, tgt, n_tgt, mat + (int64_t)s * n_tgt, level - 1, stop + s);
+    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (w >= g.nw) return;
+    const int64_t sw = (int64_t)s * g.nw + w;
+    const unsigned long long arr = arrived[sw];
+    const unsigned long long open = freeb[w] & ~arr;
+    const int32_t tp = slot + P;
+    unsigned long long *top = rs + (int64_t)(PEN && tp >= R ? tp - R : tp) * g.nw + w;   // (L + P) mod R
+    if (!open) {
+        *top = 0ull;
+        return;
     }
+    unsigned long long A = chm_gather(freeb, rs, g, st, R, level, slot, w) & open;
+    if (!PEN || !A) *top = A;   // (without penalties A is S_L; with them an empty A still clears the top slot)
+    if (!A) return;
+    arrived[sw] = arr | A;
+    last[s] = level;
+    if (!PEN) {
+        if (field) geo_store_level(chm_field_word(field, s, g, w), A, level);
+        return;
+    }
+    unsigned long long p[WA_PEN_PLANES];
+#pragma unroll
+    for (int j = 0; j < WA_PEN_PLANES; j++) p[j] = planes[(int64_t)j * g.nw + w];
+    int32_t *f = field ? chm_field_word(field, s, g, w) : nullptr;
+    // one trip per penalty value present among A's voxels: q of A's lowest voxel, then every voxel of A with that q
+    unsigned long long of_top = 0ull;
+    do {
+        const int b = __builtin_ctzll(A);
+        int32_t q = 0;
+        unsigned long long m = A;
+#pragma unroll
+        for (int j = 0; j < WA_PEN_PLANES; j++) {
+            const bool on = (p[j] >> b) & 1ull;
+            q |= on ? (1 << j) : 0;
+            m &= on ? p[j] : ~p[j];
+        }
+        A &= ~m;
+        if (f) geo_store_level(f, m, level + q);
+        if (q == P) of_top = m;
+        else {
+            const int32_t sl = slot + q;
+            rs[(int64_t)(sl >= R ? sl - R : sl) * g.nw + w] |= m;
+        }
+    } while (A);
+    *top = of_top;
 }
 
 // the walk-backs' predecessor of v = (x, y, z) with distance D in the field f: the first offset o, in the order -x, +x, -y, +y, -z, +z,
@@ -189,12 +264,16 @@ __device__ __forceinline__ long long chm_predecessor(const int32_t *__restrict__
     return -1;
 }
 
-// Walk back, one lane per pair, from the end to the start of the pair's field (slot[p] within the chunk) by chm_predecessor.
+// Walk back, one lane per pair, from the end to the start of the pair's field (slot[p] within the chunk) by chm_predecessor.  With
+// penalties (PEN; `pen` is not read otherwise) the predecessor of a node v with distance D > 0 is chm_predecessor's for D - pen[v],
+// that is the first offset o in its order for which the move exists and the voxel holds D - pen[v] - step[class(o) - 1] >= 0, which is
+// then the distance to go on with.
 // Counting pass (out == NULL): dist[p] = the field at the end, len[p] = the nodes of the path (0 when unreachable).
 // Writing pass: the i-th node from the end goes to out[dst[p] + len[p] - 1 - i], so the path reads start -> end; dst[p] < 0: nothing to
 // write (unreachable, or the caller's range is too small).  The field is exact, so a predecessor always exists; the loop still ends if not.
-__global__ __launch_bounds__(256) void k_chm_walkback(const int32_t *__restrict__ field, const uint8_t *__restrict__ free_, WaGeoDims g,
-                                                      WaChmStep st, const int32_t *__restrict__ slot, const long long *__restrict__ end,
+template <bool PEN>
+__global__ __launch_bounds__(256) void k_chm_walkback(const int32_t *__restrict__ field, const uint8_t *__restrict__ free_, const uint8_t *__restrict__ pen,
+                                                      WaGeoDims g, WaChmStep st, const int32_t *__restrict__ slot, const long long *__restrict__ end,
                                                       const long long *__restrict__ dst, int32_t n_pairs, int32_t *__restrict__ dist,
                                                       int32_t *__restrict__ len, long long *__restrict__ out)
 {
@@ -215,10 +294,11 @@ __global__ __launch_bounds__(256) void k_chm_walkback(const int32_t *__restrict_
         }
         cnt++;
         if (D == 0) break;
+        const int32_t moved = PEN ? D - (int32_t)pen[v] : D;
         int32_t paid = 0;
-        v = chm_predecessor(f, free_, g, st, v, D, &paid);
+        v = chm_predecessor(f, free_, g, st, v, moved, &paid);
         if (v < 0) break;
-        D -= paid;
+        D = moved - paid;
     }
     if (!out) len[p] = cnt;
 }

@@ -24,6 +24,26 @@ __device__ __forceinline__ int64_t geo_word_of(long long v, const WaGeoDims &g, 
     return row * g.W + (x >> 6);
 }
 
+// level 0 of every source of a chunk for the searches that keep a ring of R bitmaps per source (weighted_kernels.hpp and
+// chamfer_kernels.hpp): its bit in `seen` and in ring slot 0 (both zeroed before, the whole ring), 0 in its field when one is given (the
+// start is not paid for), last[s] = 0, stop[s] = 0.  The weighted search gives none: its field gets the 0 from the launch of level 0.
+__global__ __launch_bounds__(256) void k_geo_ring_seed(const long long *__restrict__ src, int32_t n_src, WaGeoDims g, int32_t R,
+                                                       unsigned long long *__restrict__ seen, unsigned long long *__restrict__ ring,
+                                                       int32_t *__restrict__ field, int32_t *__restrict__ last, int32_t *__restrict__ stop)
+{
+    const int32_t s = (int32_t)(blockIdx.x * 256 + threadIdx.x);
+    if (s >= n_src) return;
+    const long long v = src[s];
+    int32_t bit;
+    const int64_t w = geo_word_of(v, g, &bit);
+    const unsigned long long b = 1ull << bit;
+    seen[(int64_t)s * g.nw + w] = b;
+    ring[(int64_t)s * R * g.nw + w] = b;
+    if (field) field[(int64_t)s * g.n + v] = 0;
+    last[s] = 0;
+    stop[s] = 0;
+}
+
 // The matrix's targets, by all 256 threads of the first block of a source: `value` goes to row_out[t] for every target t in the frontier
 // cur (which the launch before completed); once no entry of the row is missing, stop[s] = 1.
 __device__ __forceinline__ void geo_lookup_targets(const unsigned long long *__restrict__ cur, const WaGeoDims &g, const long long *__restrict__ tgt,

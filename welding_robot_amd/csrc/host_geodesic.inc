@@ -196,6 +196,33 @@ struct PathSteps {
     std::function<hipError_t(const SearchChunk &, const int32_t *, const long long *, const long long *, int32_t, long long *)> write;   // (c, d_slot, d_end, d_dst, np, d_out)
 };
 
+// The PathSteps of a walk-back kernel that is both passes (host_weighted.inc, host_chamfer.inc): launch(c, d_slot, d_end, d_dst, np,
+// d_dist, d_len, d_out) enqueues it, as the counting pass with d_dst = d_out = NULL.  The counts stay on the device in *counts, which the
+// caller keeps until search_paths returns: the writing pass reads them there.
+struct WalkbackCounts { DevBuf<int32_t> dist, len; };
+typedef std::function<void(const SearchChunk &, const int32_t *, const long long *, const long long *, int32_t, int32_t *, int32_t *, long long *)> WalkbackLaunch;
+
+static PathSteps walkback_steps(wa_ctx *ctx, WalkbackCounts *counts, const WalkbackLaunch &launch)
+{
+    PathSteps steps;
+    steps.need = "len_out";
+    steps.count = [=](const SearchChunk &c, const int32_t *d_slot, const long long *d_end, int32_t np, int32_t *dist, int32_t *len) {
+        hipError_t e = counts->dist.alloc((size_t)np);
+        e = e ? e : counts->len.alloc((size_t)np);
+        if (e != hipSuccess) return e;
+        launch(c, d_slot, d_end, nullptr, np, counts->dist, counts->len, nullptr);
+        e = hipGetLastError();
+        e = e ? e : hipMemcpyAsync(dist, counts->dist, sizeof(int32_t) * np, hipMemcpyDeviceToHost, ctx->stream);
+        e = e ? e : hipMemcpyAsync(len, counts->len, sizeof(int32_t) * np, hipMemcpyDeviceToHost, ctx->stream);
+        return e ? e : hipStreamSynchronize(ctx->stream);
+    };
+    steps.write = [=](const SearchChunk &c, const int32_t *d_slot, const long long *d_end, const long long *d_dst, int32_t np, long long *d_out) {
+        launch(c, d_slot, d_end, d_dst, np, counts->dist, counts->len, d_out);
+        return hipGetLastError();
+    };
+    return steps;
+}
+
 // the _paths calls behind their checks: one field per distinct start; dist_out (and len_out, when not NULL) of every pair, then the nodes of
 // the pairs whose range [off[p], off[p + 1]) holds them
 static int search_paths(const wa_grid *g, const WaGeoDims &d, const SearchKind &k, const PathSteps &steps, const int64_t *start_ids,
@@ -293,28 +320,27 @@ static SearchKind geo_kind(const wa_grid *g, const WaGeoDims &d, const char *fn)
     return k;
 }
 
-int wa_grid_geodesic_fields(const wa_grid *g, const int64_t *src_ids, int32_t n_src, int32_t *hops_out)
+// wa_grid_geodesic_fields (points == false) and _matrix behind their names
+static int geo_rows_call(const char *fn, const wa_grid *g, const int64_t *ids, int32_t n, bool points, int32_t *hops_out)
 {
     WaDevGuard dev_guard_(g ? g->ctx : nullptr);
     if (!dev_guard_.ok) return WA_ERR_DEVICE;   // the context's device could not be made current
     if (!g) return WA_ERR_ARG;
-    if (!src_ids || !hops_out || n_src < 0) return fail(g->ctx, WA_ERR_ARG, "wa_grid_geodesic_fields: bad argument");
+    if (!ids || !hops_out || n < 0) return fail(g->ctx, WA_ERR_ARG, "%s: bad argument", fn);
     WaGeoDims d;
-    const int rc = search_begin(g, "wa_grid_geodesic_fields", &src_ids, 1, n_src, &d);
-    if (rc || n_src == 0) return rc;
-    return search_rows(g, d, geo_kind(g, d, "wa_grid_geodesic_fields"), src_ids, n_src, false, hops_out);
+    const int rc = search_begin(g, fn, &ids, 1, n, &d);
+    if (rc || n == 0) return rc;
+    return search_rows(g, d, geo_kind(g, d, fn), ids, n, points, hops_out);
+}
+
+int wa_grid_geodesic_fields(const wa_grid *g, const int64_t *src_ids, int32_t n_src, int32_t *hops_out)
+{
+    return geo_rows_call("wa_grid_geodesic_fields", g, src_ids, n_src, false, hops_out);
 }
 
 int wa_grid_geodesic_matrix(const wa_grid *g, const int64_t *point_ids, int32_t n_pts, int32_t *hops_out)
 {
-    WaDevGuard dev_guard_(g ? g->ctx : nullptr);
-    if (!dev_guard_.ok) return WA_ERR_DEVICE;   // the context's device could not be made current
-    if (!g) return WA_ERR_ARG;
-    if (!point_ids || !hops_out || n_pts < 0) return fail(g->ctx, WA_ERR_ARG, "wa_grid_geodesic_matrix: bad argument");
-    WaGeoDims d;
-    const int rc = search_begin(g, "wa_grid_geodesic_matrix", &point_ids, 1, n_pts, &d);
-    if (rc || n_pts == 0) return rc;
-    return search_rows(g, d, geo_kind(g, d, "wa_grid_geodesic_matrix"), point_ids, n_pts, true, hops_out);
+    return geo_rows_call("wa_grid_geodesic_matrix", g, point_ids, n_pts, true, hops_out);
 }
 
 int wa_grid_geodesic_paths(const wa_grid *g, const int64_t *start_ids, const int64_t *end_ids, int32_t n_pairs,

@@ -2,7 +2,7 @@
 // host_pose.inc, whose three call shapes they run on).  wa_grid_pose_weighted_fields / _matrix / _paths: cheapest paths over (voxel,
 // torch direction) where a step costs hop_cost + turn_cost[class] + pen.  wa_grid_pose_diag_fields / _matrix / _paths: the same on the
 // 26-neighbour lattice, face steps of step[0] plus diagonal moves that keep the direction.  Both are one ring search (a ring of R
-// settled sets as for host_chamfer_weighted.inc, pose_weighted_kernels.hpp), told apart by the lattice: posew_kind and posew_steps take
+// settled sets as for host_chamfer.inc's weighted calls, pose_weighted_kernels.hpp), told apart by the lattice: posew_kind and posew_steps take
 // it as a parameter.  The calls are stateless: the masks, the step matrices and the device copy of pen are rebuilt by every call.
 
 // what a call keeps on the device besides pose_prepare's: one adjacency matrix per distinct face weight, the penalty bytes (NULL: none)

@@ -79,7 +79,7 @@ static SearchKind wgt_kind(const wa_grid *g, const WaGeoDims &d, const WgtCosts 
     hipStream_t st = g->ctx->stream;
     const unsigned long long *planes = wc.planes;
     k.seed = [=](const SearchChunk &c, int32_t ns) {
-        k_wgt_seed<<<(unsigned)((ns + 255) / 256), 256, 0, st>>>(c.src, ns, d, R, c.seen, c.fronts, c.last, c.stop);
+        k_geo_ring_seed<<<(unsigned)((ns + 255) / 256), 256, 0, st>>>(c.src, ns, d, R, c.seen, c.fronts, nullptr, c.last, c.stop);   // (level 0 writes the field's 0)
     };
     k.level = [=](const SearchChunk &c, int32_t ns, int64_t level, const long long *d_tgt, int32_t n_tgt) {
         const dim3 grid((unsigned)((d.nw + 255) / 256), (unsigned)ns);
@@ -88,34 +88,30 @@ static SearchKind wgt_kind(const wa_grid *g, const WaGeoDims &d, const WgtCosts 
     return k;
 }
 
-int wa_grid_weighted_fields(const wa_grid *g, const uint8_t *cost, const int64_t *src_ids, int32_t n_src, int32_t *dist_out)
+// wa_grid_weighted_fields (points == false) and _matrix behind their names
+static int wgt_rows_call(const char *fn, const wa_grid *g, const uint8_t *cost, const int64_t *ids, int32_t n, bool points, int32_t *dist_out)
 {
     WaDevGuard dev_guard_(g ? g->ctx : nullptr);
     if (!dev_guard_.ok) return WA_ERR_DEVICE;   // the context's device could not be made current
     if (!g) return WA_ERR_ARG;
-    if (!cost || !src_ids || !dist_out || n_src < 0) return fail(g->ctx, WA_ERR_ARG, "wa_grid_weighted_fields: bad argument");
+    if (!cost || !ids || !dist_out || n < 0) return fail(g->ctx, WA_ERR_ARG, "%s: bad argument", fn);
     WaGeoDims d;
-    int rc = search_begin(g, "wa_grid_weighted_fields", &src_ids, 1, n_src, &d);
-    if (rc || n_src == 0) return rc;
+    int rc = search_begin(g, fn, &ids, 1, n, &d);
+    if (rc || n == 0) return rc;
     WgtCosts wc;
-    rc = wgt_costs(g, d, cost, "wa_grid_weighted_fields", &wc);
+    rc = wgt_costs(g, d, cost, fn, &wc);
     if (rc) return rc;
-    return search_rows(g, d, wgt_kind(g, d, wc, "wa_grid_weighted_fields"), src_ids, n_src, false, dist_out);
+    return search_rows(g, d, wgt_kind(g, d, wc, fn), ids, n, points, dist_out);
+}
+
+int wa_grid_weighted_fields(const wa_grid *g, const uint8_t *cost, const int64_t *src_ids, int32_t n_src, int32_t *dist_out)
+{
+    return wgt_rows_call("wa_grid_weighted_fields", g, cost, src_ids, n_src, false, dist_out);
 }
 
 int wa_grid_weighted_matrix(const wa_grid *g, const uint8_t *cost, const int64_t *point_ids, int32_t n_pts, int32_t *dist_out)
 {
-    WaDevGuard dev_guard_(g ? g->ctx : nullptr);
-    if (!dev_guard_.ok) return WA_ERR_DEVICE;   // the context's device could not be made current
-    if (!g) return WA_ERR_ARG;
-    if (!cost || !point_ids || !dist_out || n_pts < 0) return fail(g->ctx, WA_ERR_ARG, "wa_grid_weighted_matrix: bad argument");
-    WaGeoDims d;
-    int rc = search_begin(g, "wa_grid_weighted_matrix", &point_ids, 1, n_pts, &d);
-    if (rc || n_pts == 0) return rc;
-    WgtCosts wc;
-    rc = wgt_costs(g, d, cost, "wa_grid_weighted_matrix", &wc);
-    if (rc) return rc;
-    return search_rows(g, d, wgt_kind(g, d, wc, "wa_grid_weighted_matrix"), point_ids, n_pts, true, dist_out);
+    return wgt_rows_call("wa_grid_weighted_matrix", g, cost, point_ids, n_pts, true, dist_out);
 }
 
 int wa_grid_weighted_paths(const wa_grid *g, const uint8_t *cost, const int64_t *start_ids, const int64_t *end_ids, int32_t n_pairs,
@@ -133,23 +129,10 @@ int wa_grid_weighted_paths(const wa_grid *g, const uint8_t *cost, const int64_t 
     WgtCosts wc;
     rc = wgt_costs(g, d, cost, "wa_grid_weighted_paths", &wc);
     if (rc) return rc;
-    // both passes are k_wgt_walkback; the writing pass reads the counts the counting pass left on the device
-    DevBuf<int32_t> d_dist, d_len;
-    PathSteps steps;
-    steps.need = "len_out";
-    steps.count = [&](const SearchChunk &c, const int32_t *d_slot, const long long *d_end, int32_t np, int32_t *dist, int32_t *len) {
-        hipError_t e = d_dist.alloc((size_t)np);
-        e = e ? e : d_len.alloc((size_t)np);
-        if (e != hipSuccess) return e;
-        k_wgt_walkback<<<(unsigned)((np + 255) / 256), 256, 0, ctx->stream>>>(c.field, wc.bytes, d, d_slot, d_end, nullptr, np, d_dist, d_len, nullptr);
-        e = hipGetLastError();
-        e = e ? e : hipMemcpyAsync(dist, d_dist, sizeof(int32_t) * np, hipMemcpyDeviceToHost, ctx->stream);
-        e = e ? e : hipMemcpyAsync(len, d_len, sizeof(int32_t) * np, hipMemcpyDeviceToHost, ctx->stream);
-        return e ? e : hipStreamSynchronize(ctx->stream);
-    };
-    steps.write = [&](const SearchChunk &c, const int32_t *d_slot, const long long *d_end, const long long *d_dst, int32_t np, long long *d_out) {
+    WalkbackCounts counts;
+    const PathSteps steps = walkback_steps(ctx, &counts, [&](const SearchChunk &c, const int32_t *d_slot, const long long *d_end, const long long *d_dst,
+                                                             int32_t np, int32_t *d_dist, int32_t *d_len, long long *d_out) {
         k_wgt_walkback<<<(unsigned)((np + 255) / 256), 256, 0, ctx->stream>>>(c.field, wc.bytes, d, d_slot, d_end, d_dst, np, d_dist, d_len, d_out);
-        return hipGetLastError();
-    };
+    });
     return search_paths(g, d, wgt_kind(g, d, wc, "wa_grid_weighted_paths"), steps, start_ids, end_ids, n_pairs, off, ids_out, dist_out, len_out);
 }

@@ -65,23 +65,8 @@ __global__ __launch_bounds__(256) void k_wgt_planes(const uint8_t *__restrict__ 
     else if (fr) info[c] = 1;
 }
 
-// level 0 of every source of a chunk: its bit in `touched` and in ring slot 0 (both zeroed before, the whole ring), last[s] = 0 (the
-// last launch that saw a frontier or touched a voxel), stop[s] = 0.  The field gets its 0 from the launch of level 0.
-__global__ __launch_bounds__(256) void k_wgt_seed(const long long *__restrict__ src, int32_t n_src, WaGeoDims g, int32_t R,
-                                                  unsigned long long *__restrict__ touched, unsigned long long *__restrict__ ring,
-                                                  int32_t *__restrict__ last, int32_t *__restrict__ stop)
-{
-    const int32_t s = (int32_t)(blockIdx.x * 256 + threadIdx.x);
-    if (s >= n_src) return;
-    int32_t bit;
-    const int64_t w = geo_word_of(src[s], g, &bit);
-    const unsigned long long b = 1ull << bit;
-    touched[(int64_t)s * g.nw + w] = b;
-    ring[(int64_t)s * R * g.nw + w] = b;
-    last[s] = 0;
-    stop[s] = 0;
-}
-
+// Level 0 is k_geo_ring_seed without a field: the source's bit in `touched` and in ring slot 0, last[s] = 0 (the last launch that saw a
+// frontier or touched a voxel).
 // The launch of level L for every source of a chunk (ring of R = W + 1 slots per source, slot = L mod R):
 //   1. F = ring[slot] at the lane's word and its six neighbour words (nobody writes that slot in this launch); the voxels of the own word
 //      get L in the field, when one is kept (a voxel is in exactly one frontier, so every field entry is written at most once);

@@ -34,7 +34,6 @@
 #include "geodesic_kernels.hpp"
 #include "weighted_kernels.hpp"
 #include "chamfer_kernels.hpp"
-#include "chamfer_weighted_kernels.hpp"
 #include "fit_kernels.hpp"
 #include "retime_kernels.hpp"
 #include "seamtour_kernels.hpp"
@@ -1030,7 +1029,6 @@ void *wa_ctx_stream(wa_ctx *c) { return c ? (void *)c->stream : nullptr; }
 #include "host_geodesic.inc"
 #include "host_weighted.inc"
 #include "host_chamfer.inc"
-#include "host_chamfer_weighted.inc"
 #include "host_fit.inc"
 #include "host_retime.inc"
 #include "host_jerk.inc"
